@@ -11,8 +11,15 @@ articles, 33-token captions.  One "step" = the complete optimisation step on one
 (batch-stat BN) + RoBERTa-large (24 layers, 512 tokens) forward, 4-context 4-layer DynamicConv decoder forward +
 adaptive-softmax loss + backward, gradient all-reduce (N > 1, RCCL) and BertAdam.  bf16 compute, fp32 master weights,
 random-init weights, synthetic data of NYTimes800k shape (no network for datasets / checkpoints).
-`--model flattened --batch 16` is configs[1]; at N = 1 it is also measured as the `secondary` block of the same line.
+`--model flattened --batch 16` is configs[1].
 Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps (+ --burn-in untimed clock-settling
+steps), exactly K timed steps (one window), the outputs of the last timed step if --dump-outputs DIR is given, and the
+line (`value`, `ms_per_step` = milliseconds per timed step).  `--full` adds every other measurement: 5 timed windows of K
+steps (median window = headline), the roofline instrumentation and its single-stream and decoder-alone legs with the
+rocprofv3 --pmc passes, and at N = 1 the configs[1] `secondary` block, the configs[4] `generation` block, the data-plane
+`loader` legs, the 1-rank RCCL `dp_selftest` and the CPU `cpu_baseline` (each can still be dropped with its --no-* flag).
 """
 import argparse
 import json
@@ -38,6 +45,33 @@ WORKLOAD = {
                  'contexts: ResNet-152 image regions + RoBERTa-large article), batch %d/GPU, 512-token articles, 32 '
                  'caption steps; full step = frozen encoders fwd + decoder fwd/loss/bwd + BertAdam',
 }
+
+
+DUMP_WEIGHT_SAMPLE = 1 << 22          # fp32 master weights written by --dump-outputs (a fixed, seeded sample: 16 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float32 or float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def training_outputs(trainer, loss):
+    """What the last timed training step hands back: its loss, and its product - the fp32 master weights after its
+    BertAdam update - as a fixed sample of DUMP_WEIGHT_SAMPLE elements (seed 0, sorted offsets into the flat buffer)."""
+    import numpy as np
+    trainer.finish_update()
+    torch.cuda.synchronize()
+    flat = trainer.flat.flat
+    n = flat.numel()
+    idx = np.arange(n) if n <= DUMP_WEIGHT_SAMPLE else np.sort(np.random.default_rng(0).integers(0, n, DUMP_WEIGHT_SAMPLE))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    return {'loss': np.array([float(loss)], dtype=np.float64), 'weights_sample': sample}
 
 
 def _cpu_model():
@@ -209,7 +243,7 @@ def dp_selftest(args):
     sock.close()
     env = dict(os.environ, TELL_DP_SELFTEST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK='0', WORLD_SIZE='1',
                LOCAL_RANK='0')
-    cmd = [sys.executable, os.path.abspath(__file__), '--steps', '10', '--warmup', '4', '--no-cpu-baseline', '--no-secondary',
+    cmd = [sys.executable, os.path.abspath(__file__), '--steps', '10', '--warmup', '4', '--full', '--no-cpu-baseline', '--no-secondary',
            '--no-generation', '--no-loader', '--no-roofline', '--no-dp-selftest']
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -261,8 +295,9 @@ def relaunch(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
-def measure(args, model_name, batch_size, dev, world, rank, dist, roofline=True):
-    """Build the model, run warmup + timed steps (+ the single-stream roofline leg, + the decoder-alone leg)."""
+def measure(args, model_name, batch_size, dev, world, rank, dist, roofline=True, dump=None):
+    """Build the model, run warmup + timed steps (+ with --full: the single-stream roofline leg, the decoder-alone leg).
+    dump: a directory for the outputs of the last timed step (dump_outputs / training_outputs)."""
     import tell_amd
     from tell_amd import prof
     from tell_amd.build import build_model
@@ -305,7 +340,7 @@ def measure(args, model_name, batch_size, dev, world, rank, dist, roofline=True)
     # every step trains batch i and launches the frozen encoders of batch i+1 underneath it (what a training loop
     # with a data loader does); each timed step therefore contains exactly one encoder pass and one decoder pass
     nxt = lambda i: None if no_pipeline else batches[(i + 1) % 2]     # noqa: E731
-    want_prof = roofline and not args.no_roofline
+    want_prof = roofline and args.full and not args.no_roofline
     if want_prof:
         # enabled BEFORE the warm-up: the encoder / decoder hipGraphs are recorded there, and a launch inside a captured
         # graph can only be timed by what is captured with it (device timestamps around every 4th large GEMM, prof.py)
@@ -358,6 +393,8 @@ def measure(args, model_name, batch_size, dev, world, rank, dist, roofline=True)
         issued_w = time.perf_counter() - t0       # host finished issuing; the rest of `elapsed` is GPU backlog
         sync()
         wins.append((time.perf_counter() - t0, issued_w))
+    if dump:                                                 # (before any later leg trains on)
+        dump_outputs(dump, training_outputs(trainer, loss))
     legs.append('timed_region')
     tw = torch.tensor([e for e, _ in wins], dtype=torch.float64, device=dev)
     if world > 1:
@@ -727,6 +764,9 @@ def generate_bench(args, dev, world, rank, dist):
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if getattr(args, 'dump_outputs', None) and rank == 0:      # the captions of the last timed batch
+            dump_outputs(args.dump_outputs, {k: out[k].detach().cpu().double().numpy() for k in ('gen_ids', 'log_probs')
+                                             if torch.is_tensor(out.get(k))})
         serial_elapsed = None
         if pipelined:                              # the round-4 flow beside it: encoders, then the decode loop, per batch
             torch.cuda.synchronize()
@@ -803,8 +843,15 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--windows', type=int, default=5, help='timed windows of --steps steps each (barrier + synchronize around '
-                    'every one); the median window is the headline value')
+    ap.add_argument('--full', action='store_true',
+                    help='training line: also run every measurement beyond the headline (see the module docstring); '
+                         'off: set-up, warm-up, the timed steps, --dump-outputs and the result line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64): the loss and a '
+                         'fixed sample of the updated fp32 master weights; with --generate the captions\' ids and '
+                         'log-probabilities')
+    ap.add_argument('--windows', type=int, default=None, help='timed windows of --steps steps each (barrier + synchronize '
+                    'around every one); the median window is the headline value (default 1; 5 with --full)')
     ap.add_argument('--burn-in', dest='burn_in', type=int, default=40, help='untimed clock-settling steps after the warm-up')
     ap.add_argument('--batch', type=int, default=None, help='samples per GPU (configs[2]: 32, configs[1]: 16)')
     ap.add_argument('--model', default='faces_objects', choices=['flattened', 'faces_objects'])
@@ -839,6 +886,8 @@ def main():
         return hog_child(args.hog_child)
     if args.batch is None:
         args.batch = 32 if args.model == 'faces_objects' else 16
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
     args.warmup = max(args.warmup, 0)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -871,7 +920,8 @@ def main():
         if dist.is_initialized():
             dist.destroy_process_group()
         return
-    res, trainer = measure(args, args.model, args.batch, dev, world, rank, dist)
+    res, trainer = measure(args, args.model, args.batch, dev, world, rank, dist,
+                           dump=args.dump_outputs if rank == 0 else None)
     if rank == 0:
         result = {
             'metric': 'training samples/sec (img+article->caption)', 'value': res.pop('value'),
@@ -885,8 +935,8 @@ def main():
                        'step_graph_replays': res.pop('step_graph_replays'), 'skipped_steps': res.pop('skipped_steps'),
                        'resnet_hipgraph': res.pop('resnet_hipgraph')},
         }
-        result.update(res)                       # roofline, step_mfma, decoder_step
-        if world == 1 and args.model == 'faces_objects' and not args.no_secondary and not args.serial \
+        result.update(res)                       # step_mfma (+ roofline, decoder_step with --full)
+        if args.full and world == 1 and args.model == 'faces_objects' and not args.no_secondary and not args.serial \
                 and args.dtype == 'bf16':
             # configs[1] in the same line (round-1 headline; kept as a secondary measurement)
             del trainer
@@ -900,7 +950,7 @@ def main():
                                    'host_issue_ms_per_step': sec['host_issue_ms_per_step'],
                                    'step_mfma': sec['step_mfma'], 'steps': args.steps, 'warmup': args.warmup}
             del tr2
-        if world == 1 and args.model == 'faces_objects' and not args.no_generation and not args.serial \
+        if args.full and world == 1 and args.model == 'faces_objects' and not args.no_generation and not args.serial \
                 and args.dtype == 'bf16':
             # configs[4] in the same line: beam-4 (the config's metric) and greedy (what the reference decodes) caption
             # generation of the full model, encoders included, 3 timed batches of 32 captions x 100 steps each
@@ -917,6 +967,7 @@ def main():
             for beam, gb, ln in ((4, 32, 1), (1, 32, 1), (4, 128, 1), (1, 128, 1), (4, 32, 2), (1, 32, 2), (4, 128, 2), (1, 128, 2)):
                 ga = argparse.Namespace(**vars(args))
                 ga.batch, ga.beam, ga.steps, ga.warmup, ga.lanes = gb, beam, (4 if gb == 32 else 3) * ln, 2 * ln, ln
+                ga.dump_outputs = None
                 g = generate_bench(ga, dev, world, rank, dist)
                 key = ('beam%d' % beam if beam > 1 else 'greedy') + ('' if gb == 32 else '_b%d' % gb) + ('' if ln == 1 else '_lanes%d' % ln)
                 result['generation'][key] = {
@@ -927,7 +978,8 @@ def main():
                 gc.collect()
                 tell_amd.ops.clear_weight_cache()
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_loader and not args.serial and args.model == 'faces_objects' and args.dtype == 'bf16':
+        if args.full and world == 1 and not args.no_loader and not args.serial and args.model == 'faces_objects' and \
+                args.dtype == 'bf16':
             trainer = None
             import gc
             gc.collect()
@@ -947,13 +999,13 @@ def main():
                 tell_amd.ops.clear_weight_cache()
                 torch.cuda.empty_cache()
                 result['loader_many_signatures'] = loader_bench(args, dev, n_batches=38, warm=2, variable='wide')
-        if world == 1 and not args.no_dp_selftest and not args.serial and args.model == 'faces_objects' and \
+        if args.full and world == 1 and not args.no_dp_selftest and not args.serial and args.model == 'faces_objects' and \
                 os.environ.get('TELL_DP_SELFTEST') is None and not args.cu_hog:
             # the data-parallel code path's own cost at N = 1: the same step with a 1-rank RCCL group and every
             # collective, cast and the wire-reading BertAdam of the DP schedule, in its own process (an RCCL communicator
             # takes a hardware queue; the headline above runs without one)
             result['dp_selftest'] = dp_selftest(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(args.model, args.cpu_sample)
         print(json.dumps(result))
     if dist.is_initialized():

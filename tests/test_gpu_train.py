@@ -543,7 +543,7 @@ def test_bench_two_ranks_through_the_real_launcher():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'TELL_DP_SELFTEST'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--windows', '2',
-           '--burn-in', '0', '--roofline-steps', '1', '--no-pmc']
+           '--burn-in', '0', '--full', '--roofline-steps', '1', '--no-pmc']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]     # rank 0 alone prints
@@ -560,3 +560,38 @@ def test_bench_two_ranks_through_the_real_launcher():
     assert dp['ranks'][0]['legs'] == ['timed_region', 'roofline_leg'], dp['ranks']
     assert j['config']['skipped_steps'] == 0 and j['roofline']['frac'] > 0
     assert 'cpu_baseline' not in j and 'generation' not in j          # single-GPU legs stay out of a multi-rank line
+
+
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: one window of exactly K timed steps, the headline keys, none of
+    the --full blocks, and --dump-outputs DIR holding the last timed step's loss and weight sample as float .npy files
+    (64 MB at most); two runs with the same arguments write the same loss."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    losses = []
+    for run in ('a', 'b'):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2',
+               '--burn-in', '0', '--dump-outputs', str(out_dir)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
+        j = json.loads(lines[0])
+        assert j['steps'] == 3 and j['warmup'] == 2 and j['windows'] == 1 and len(j['windows_ms_per_step']) == 1
+        assert j['unit'] == 'samples/s' and j['higher_is_better'] is True and j['dtype'] == 'bf16'
+        assert abs(j['value'] - 32 * 3 / (j['ms_per_step'] * 3e-3)) <= 0.01 * j['value']
+        for key in ('roofline', 'decoder_step', 'secondary', 'generation', 'loader', 'dp_selftest', 'cpu_baseline'):
+            assert key not in j, key
+        files = sorted(os.listdir(out_dir))
+        assert files == ['loss.npy', 'weights_sample.npy'], files
+        arrays = {f: np.load(out_dir / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert np.isfinite(arrays['loss.npy']).all() and np.isfinite(arrays['weights_sample.npy']).all()
+        assert abs(float(arrays['loss.npy'][0]) - j['config']['final_loss_bits']) <= 1e-3 * abs(j['config']['final_loss_bits'])
+        losses.append(float(arrays['loss.npy'][0]))
+    assert abs(losses[0] - losses[1]) <= 1e-3 * abs(losses[0]), losses

@@ -2,8 +2,9 @@
 # Round-4 evidence in one GPU-box call (repo root): bash tools/r04_profiles.sh  -> gpurun_out/r04_*
 # (copied into profiles/ by hand afterwards; every file names the command that produced it)
 set +e
-bash tools/profile_bench.sh r04 --steps 9 --warmup 1 --no-cpu-baseline --no-secondary --no-generation --no-loader
-bash tools/profile_bench.sh r04_serial --serial --steps 4 --warmup 1 --no-cpu-baseline --no-secondary
+res=${RESULTS_DIR:-results}; mkdir -p "$res"   # the bench lines' results
+bash tools/profile_bench.sh r04 --full --steps 9 --warmup 1 --no-cpu-baseline --no-secondary --no-generation --no-loader
+bash tools/profile_bench.sh r04_serial --full --serial --steps 4 --warmup 1 --no-cpu-baseline --no-secondary
 SEQ_ANCHOR=bertadam bash tools/profile_cmd.sh r04_decoder "decoder half of the step alone (fwd + loss + bwd + BertAdam), B=32, step graph: python tools/decoder_profile.py faces_objects 32 20" python tools/decoder_profile.py faces_objects 32 20
 bash tools/profile_cmd.sh r04_resnet "ResNet-152 alone, B=32, train-mode BatchNorm: python tools/resnet_profile.py 32 20 train" python tools/resnet_profile.py 32 20 train
 bash tools/profile_cmd.sh r04_resnet_eval "ResNet-152 alone, B=32, eval (BatchNorm folded): python tools/resnet_profile.py 32 20 eval" python tools/resnet_profile.py 32 20 eval
@@ -16,7 +17,7 @@ python tools/bench_skinny.py 32 > gpurun_out/r04_skinny_bench.txt 2>&1
 python tools/bench_skinny.py 128 >> gpurun_out/r04_skinny_bench.txt 2>&1
 python tools/bench_roberta_gemms.py > gpurun_out/r04_roberta_gemms.txt 2>&1
 for b in 1 4; do python bench.py --generate --beam $b 2>/dev/null | tail -1 > gpurun_out/r04_generate_beam$b.json; done
-python bench.py 2> gpurun_out/r04_bench.err | tail -1 > gpurun_out/r04_bench.json
+python bench.py --full 2> "$res"/r04_bench.err | tail -1 > "$res"/r04_bench.json
 python tools/bench_dynconv.py 2>&1 | grep -v amdgpu.ids > gpurun_out/r04_dynconv.txt
 bash tools/pmc_kernel.sh gemm_nt_q4 gpurun_out/r04_pmc_gemm_mfma.txt SQ_BUSY_CYCLES,SQ_ACTIVE_INST_ANY,SQ_ACTIVE_INST_VALU,SQ_ACTIVE_INST_LDS,SQ_INST_CYCLES_VMEM,SQ_VALU_MFMA_BUSY_CYCLES,SQ_WAVE_CYCLES,SQ_WAIT_ANY -- python tools/bench_roberta_gemms.py > /dev/null
 LDSC=SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE,SQ_INSTS_LDS,SQ_INST_CYCLES_VMEM,SQ_WAVE_CYCLES,SQ_WAIT_INST_LDS,SQ_VALU_MFMA_BUSY_CYCLES,SQ_BUSY_CYCLES
