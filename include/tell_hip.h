@@ -74,6 +74,8 @@ int tell_set_pos_step_ptr(const void* counter, tell_stream_t stream);
  * tell_greedy_update / tell_beam_update - its last - write the following offset back (their `counter` argument) */
 int tell_set_pos_next_ptr(void* next, tell_stream_t stream);
 uint32_t tell_drop_threshold_host(float p);
+/* host evaluation of the sampling uniform u(seed, row, step) in [0, 1) (tell_adaptive_logprob_sample, step 3) */
+float tell_sample_uniform_host(uint32_t seed, uint32_t row, uint32_t step);
 /* measurement aid (bench.py roofline): rate of the device wall clock in kHz (100 000 on MI355X) */
 int tell_wall_clock_khz(void);
 /* measurement aid (bench.py --cu-hog, the single-GPU rehearsal of what RCCL's channel kernels do to a step whose dominant
@@ -489,6 +491,30 @@ int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,
                                  float* token_lp, tell_stream_t stream);
+/* top-k sampling with a temperature (transformer_faces_objects.py:38-55, 443-470: lprobs.topk(k), / T, torch.multinomial).
+ * Per row r at step i with seed s:
+ *   1. candidates: the k (1..64) largest log-probs of the full adaptive softmax, each computed as in
+ *      tell_adaptive_logprob_argmax (v = logit - lse_head; a tail adds head_lsm[c0 + c] - lse_tail), ordered by value
+ *      descending, lower token id first on ties - k = 1 is the arg-max token, k <= 8 the list of tell_adaptive_logprob_topk;
+ *   2. weights w_j = exp((lp_j - lp_0) * inv_temp) in fp32, cumulative sums c_j added in candidate order (the distribution
+ *      of multinomial(exp(topk_lp / T)): multinomial normalises);
+ *   3. u in [0, 1): 24 bits of a 32-bit counter-based hash of (s, row, step) (tell_sample_uniform_host);
+ *   4. the pick: the smallest j with u * c_{k-1} < c_j, clamped to k - 1;
+ *   5. out: tokens[r] = id_j, lps[r] = lp_j WITHOUT the temperature (tell_greedy_update multiplies by inv_temp).
+ * row = row_ids[r] (the ORIGINAL batch row of a compacted row) or r when row_ids is NULL; step = *step_dev + 1 when step_dev
+ * is given (the device counter of a captured decode step, which holds i - 1 during step i), else `step`; the seed is read
+ * from DEVICE memory (*seed_dev), so a captured graph never bakes it in.  The draws are not torch.multinomial's: the
+ * distribution and the reported log-probs match the reference, the sampled ids do not match draw for draw.
+ * tokens int32 [rows], lps fp32 [rows].  Register-resident rows (the capacity and alignment of the register arg-max) take one
+ * kernel; any other row (or option argmax_regs = 0) a streaming kernel with the arithmetic of the full-row arg-max. */
+int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                 int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                 int rows, int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids, int step,
+                                 const int* step_dev, int* tokens, float* lps, tell_stream_t stream);
+/* steps 2-5 above on given candidates: cand_tokens int32 / cand_lps fp32 [rows, k], each row sorted best first */
+int tell_sample_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp,
+                           const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,
+                           float* lps, tell_stream_t stream);
 
 /* per-token bookkeeping of the greedy decode loop (transformer_faces_objects.py:443-494) for all B rows in one launch:
    unfinished rows record tok / lp * inv_temp at step i, rows emitting eos are marked finished (done_step = i + 1),

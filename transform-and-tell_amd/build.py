@@ -43,9 +43,11 @@ def build_decoder(kind='faces_objects', vocab_size=50265, dim=1024, heads=16, ff
     return DynamicConvDecoder(None, emb, article_embed_size=article_dim, **kw)
 
 
-def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=25, **decoder_kw):
+def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=25, sampling_topk=1, sampling_temp=1.0,
+                **decoder_kw):
     dec = build_decoder(kind, **decoder_kw)
     cls = {'faces_objects': TransformerFacesObjectModel, 'faces': TransformerFacesModel,
            'faces_parallel': TransformerFacesModel}.get(kind, TransformerFlattenedModel)
     return cls(None, dec, AdaptiveLoss(padding_idx=1), weigh_bert=weigh_bert, vocab_size=decoder_kw.get('vocab_size', 50265),
-               resnet=resnet, roberta=roberta, n_bert_layers=n_bert_layers)
+               resnet=resnet, roberta=roberta, n_bert_layers=n_bert_layers, sampling_topk=sampling_topk,
+               sampling_temp=sampling_temp)

@@ -674,6 +674,370 @@ extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int
   return tell_check_launch("logprob_argmax");
 }
 
+// ------------------------------------------------------------------ top-k sampling with a temperature
+// transformer_faces_objects.py:443-470 with sampling_topk = k: lprobs.topk(k), / T, torch.multinomial.  Per row, exactly
+// (include/tell_hip.h, DESIGN.md "Top-k sampling"): the k largest log-probs of the full adaptive softmax (value descending,
+// lower token id first on ties; the log-probs are those of the arg-max kernels), the uniform u of (seed, row, step)
+// (common.h tell_sample_u), the pick of tell_sample_pick; out: the token and its log-prob WITHOUT the temperature (the
+// bookkeeping launch divides).  One 1024-thread workgroup per row.
+//
+// The exact top-k is a radix select on order-preserving 32-bit keys (0 = not a token: padding, cluster columns):
+//  1. tau = the k-th largest of the 1024 per-thread maxima (4 passes of 8 bits over one key per thread).  The k threads
+//     that own the k largest maxima hold k elements >= tau, so every element of the top k is >= tau;
+//  2. the k-th largest key K over the elements >= tau (4 passes; typically a few times k elements take part, so the LDS
+//     histogram atomics stay few), and how many elements tie at K;
+//  3. only if more elements tie at K than the top k takes: the lowest token ids among the ties (3 passes over the ids);
+//  4. the k winners are compacted into LDS, ranked (value, id) by k threads, and thread 0 draws.
+// Every pass walks the row's elements through `each` - the registers of the row (logprob_sample_regs_kernel) or the
+// logits in memory (logprob_sample_stream_kernel) - so the register form never reads the row twice.
+struct SampleArgs {
+  int k; float inv_temp;
+  const uint32_t* seed_dev; const int* row_ids; int step; const int* step_dev;
+  int* tokens; float* lps;
+};
+struct SampleSmem {
+  int hist[256];
+  uint32_t cand_key[64]; int cand_idx[64];
+  float sort_v[64]; int sort_i[64];
+  int sel, above, count, n_cand;
+  uint32_t ref;                       // the filter's reference value, read from LDS in every pass (see sample_radix_select)
+};
+__device__ __forceinline__ uint32_t lp_key(float v) {          // order-preserving: larger float -> larger key
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_lp(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// one radix pass's decision (hist complete after the first barrier): the digit whose bin holds the need-th largest of the
+// counted values, how many lie in the bins above it and how many in the bin itself.  Wave 0 decides, everyone reads.
+__device__ __forceinline__ void sample_radix_decide(SampleSmem& sm, int need, int& d, int& above, int& count) {
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const int h[4] = {sm.hist[4 * lane], sm.hist[4 * lane + 1], sm.hist[4 * lane + 2], sm.hist[4 * lane + 3]};
+    const int tot = h[0] + h[1] + h[2] + h[3];
+    int suf = tot;                                            // sum over lanes >= lane (higher digits)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_down(suf, o, 64);
+      if (lane + o < 64) suf += v;
+    }
+    int cum = suf - tot;
+#pragma unroll
+    for (int b = 3; b >= 0; --b) {
+      if (cum < need && cum + h[b] >= need) { sm.sel = 4 * lane + b; sm.above = cum; sm.count = h[b]; }
+      cum += h[b];
+    }
+  }
+  __syncthreads();
+  d = sm.sel; above = sm.above; count = sm.count;
+}
+// the need-th largest value v among the elements for which val(key, idx, ref, v) holds, digits from bit top_shift + 7 down
+// (higher bits of v must be equal for all participants); on return need = how many elements equal to the result it takes,
+// count = how many there are.  ref = sm.ref, loaded after each pass's barrier: a filter on a register value would be
+// loop-invariant, and the compiler hoists the 64 per-element masks / values of the register form out of the pass loop
+// (54 VGPRs and 117 SGPRs spilled); the caller sets sm.ref before the call.
+template <class Each, class Val>
+__device__ __forceinline__ uint32_t sample_radix_select(const Each& each, const Val& val, int top_shift, int& need, int& count,
+                                                        SampleSmem& sm) {
+  uint32_t pre = 0, msk = 0;
+  for (int sh = top_shift; sh >= 0; sh -= 8) {
+    if (threadIdx.x < 256) sm.hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t ref = sm.ref;
+    each([&](uint32_t key, int idx) {
+      uint32_t v;
+      if (val(key, idx, ref, v) && (v & msk) == pre) atomicAdd(&sm.hist[(v >> sh) & 255], 1);
+    });
+    int d, above;
+    sample_radix_decide(sm, need, d, above, count);
+    pre |= (uint32_t)d << sh;
+    msk |= 0xFFu << sh;
+    need -= above;
+  }
+  return pre;
+}
+// each_ties: the same elements with the same keys, for the tie pass (3) only - the register form hands in a walk over memory
+// there, because ids kept live through the pass loop spill half of its registers
+template <class Each, class EachTies>
+__device__ __forceinline__ void sample_row(const Each& each, const EachTies& each_ties, uint32_t thread_max, int row,
+                                           const SampleArgs& a, SampleSmem& sm) {
+  const int tid = threadIdx.x, k = a.k;
+  int need = k, count = 0;
+  // 1. tau: the k-th largest per-thread maximum
+  const uint32_t tau = sample_radix_select([&](auto f) { f(thread_max, 0); },
+                                          [](uint32_t key, int, uint32_t, uint32_t& v) { v = key; return true; }, 24, need,
+                                          count, sm);
+  // 2. the k-th largest key
+  need = k;
+  if (tid == 0) sm.ref = tau;
+  const uint32_t kth = sample_radix_select(
+      each, [](uint32_t key, int, uint32_t ref, uint32_t& v) { v = key; return key >= ref; }, 24, need, count, sm);
+  // 3. more ties at kth than places left: the `need` lowest ids among them (largest 0xFFFFFF - id; `key ^ ref` is 0 for a
+  //    participant and keeps the value inside the pass)
+  int last = 0xFFFFFF;
+  if (count > need) {                                         // (uniform)
+    if (tid == 0) sm.ref = kth;
+    const uint32_t inv = sample_radix_select(
+        each_ties,
+        [](uint32_t key, int idx, uint32_t ref, uint32_t& v) {
+          v = (key ^ ref) | (0xFFFFFFu - (uint32_t)idx);
+          return key == ref;
+        },
+        16, need, count, sm);
+    last = 0xFFFFFF - (int)inv;
+  }
+  // 4. compact the k winners, rank them, draw
+  if (tid == 0) sm.n_cand = 0;
+  __syncthreads();
+  each([&](uint32_t key, int idx) {
+    if (key > kth || (key == kth && idx <= last)) {
+      const int s = atomicAdd(&sm.n_cand, 1);
+      if (s < 64) { sm.cand_key[s] = key; sm.cand_idx[s] = idx; }
+    }
+  });
+  __syncthreads();
+  if (tid < k) {
+    const uint32_t mk = sm.cand_key[tid];
+    const int mi = sm.cand_idx[tid];
+    int rank = 0;
+    for (int j = 0; j < k; ++j) {
+      const uint32_t ok = sm.cand_key[j];
+      rank += (ok > mk || (ok == mk && sm.cand_idx[j] < mi)) ? 1 : 0;
+    }
+    sm.sort_v[rank] = key_lp(mk);
+    sm.sort_i[rank] = mi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t r = a.row_ids ? (uint32_t)a.row_ids[row] : (uint32_t)row;
+    const uint32_t step = a.step_dev ? (uint32_t)(*a.step_dev + 1) : (uint32_t)a.step;   // (captured: the counter holds i - 1)
+    const float u = tell_sample_u(*a.seed_dev, r, step);
+    const int j = tell_sample_pick(sm.sort_v, k, a.inv_temp, u);
+    a.tokens[row] = sm.sort_i[j];
+    a.lps[row] = sm.sort_v[j];
+  }
+}
+// The register-resident form: loads, maxima, sums and log-probs exactly as logprob_regs_kernel (so k = 1 is its arg-max bit
+// for bit), then the log-probs become keys in place and every pass of the select runs over registers.  Same capacity and
+// alignment rules.
+__global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p, SampleArgs a) {
+  __shared__ float red[4][16];
+  __shared__ SampleSmem sm;
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nseg = 1 + p.n_tails;
+  const float* rowp[4]; int n[4];
+  rowp[0] = p.head + (long)i * p.ld_head; n[0] = p.head_n;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    rowp[c + 1] = c < p.n_tails ? p.tail[c] + (long)i * p.ld_tail[c] : rowp[0];
+    n[c + 1] = c < p.n_tails ? p.tail_n[c] : 0;
+  }
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  f4 x[16];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const int j = (q * 1024 + tid) * 4;
+      f4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      if (j + 3 < n[s]) v = *reinterpret_cast<const f4*>(rowp[s] + j);
+      else if (j < n[s]) {
+        v.x = rowp[s][j];
+        if (j + 1 < n[s]) v.y = rowp[s][j + 1];
+        if (j + 2 < n[s]) v.z = rowp[s][j + 2];
+      }
+      x[LPF_OFF[s] + q] = v;
+    }
+  float mx[4], sm_[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const f4 v = x[LPF_OFF[s] + q];
+      m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+    m = wave_max(m);
+    if (lane == 0) red[s][wave] = m;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float m = red[s][0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) m = fmaxf(m, red[s][w]);
+    mx[s] = m;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float t = 0.f;
+    if (s < nseg) {
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q) {
+        const f4 v = x[LPF_OFF[s] + q];
+        t += (__expf(v.x - mx[s]) + __expf(v.y - mx[s])) + (__expf(v.z - mx[s]) + __expf(v.w - mx[s]));
+      }
+    }
+    t = wave_sum(t);
+    if (lane == 0) red[s][wave] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) t += red[s][w];
+    sm_[s] = t;
+  }
+  const float lse_h = mx[0] + __logf(sm_[0]);
+  float off[4];
+  int base[4];
+  off[0] = -lse_h; base[0] = 0;
+  base[1] = p.c0;
+#pragma unroll
+  for (int s = 1; s < 4; ++s) {
+    off[s] = s < nseg ? (rowp[0][p.c0 + s - 1] - lse_h) - (mx[s] + __logf(sm_[s])) : 0.f;
+    if (s < 3) base[s + 1] = base[s] + n[s];
+  }
+  const int lim[4] = {p.c0, n[1], n[2], n[3]};               // (segments past n_tails have n = 0)
+  uint32_t key[64];
+  uint32_t tmax = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const int j = (q * 1024 + tid) * 4, e0 = (LPF_OFF[s] + q) * 4;
+      const f4 v = x[LPF_OFF[s] + q];
+      // head: v - lse_h (the argmax kernels' `x - lse_h`); tails: v + off
+      const float l0 = s == 0 ? v.x - lse_h : v.x + off[s], l1 = s == 0 ? v.y - lse_h : v.y + off[s];
+      const float l2 = s == 0 ? v.z - lse_h : v.z + off[s], l3 = s == 0 ? v.w - lse_h : v.w + off[s];
+      key[e0] = j < lim[s] ? lp_key(l0) : 0u;
+      key[e0 + 1] = j + 1 < lim[s] ? lp_key(l1) : 0u;
+      key[e0 + 2] = j + 2 < lim[s] ? lp_key(l2) : 0u;
+      key[e0 + 3] = j + 3 < lim[s] ? lp_key(l3) : 0u;
+      tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
+    }
+  auto each = [&](auto f) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f(key[(LPF_OFF[s] + q) * 4 + e], base[s] + (q * 1024 + tid) * 4 + e);
+  };
+  auto each_mem = [&](auto f) {                               // (the same keys: the same operations on the same logits)
+    for (int j = tid; j < p.c0; j += 1024) f(lp_key(rowp[0][j] - lse_h), j);
+    for (int s = 1; s < nseg; ++s)
+      for (int j = tid; j < n[s]; j += 1024) f(lp_key(rowp[s][j] + off[s]), base[s] + j);
+  };
+  sample_row(each, each_mem, tmax, i, a, sm);
+}
+// Any row: the log-probs with the arithmetic of logprob_argmax_kernel (the three-pass form; its full-row output is what the
+// tests take top-k of), read from memory in every pass of the select.
+__global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs p, SampleArgs a) {
+  __shared__ float red[16];
+  __shared__ SampleSmem sm;
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const float* hrow = p.head + (long)i * p.ld_head;
+  float mx = -INFINITY;
+#pragma unroll 4
+  for (int j = tid; j < p.head_n; j += 1024) mx = fmaxf(mx, hrow[j]);
+  mx = block_max(mx, red);
+  float s = 0.f;
+#pragma unroll 4
+  for (int j = tid; j < p.head_n; j += 1024) s += __expf(hrow[j] - mx);
+  s = block_sum(s, red);
+  const float lse_h = mx + __logf(s);
+  float off[3] = {0.f, 0.f, 0.f};
+  for (int c = 0; c < p.n_tails; ++c) {
+    const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+    const int n = p.tail_n[c];
+    float m2 = -INFINITY;
+#pragma unroll 4
+    for (int j = tid; j < n; j += 1024) m2 = fmaxf(m2, trow[j]);
+    m2 = block_max(m2, red);
+    float s2 = 0.f;
+#pragma unroll 4
+    for (int j = tid; j < n; j += 1024) s2 += __expf(trow[j] - m2);
+    s2 = block_sum(s2, red);
+    off[c] = (hrow[p.c0 + c] - lse_h) - (m2 + __logf(s2));
+  }
+  auto each = [&](auto f) {
+    for (int j = tid; j < p.c0; j += 1024) f(lp_key(hrow[j] - lse_h), j);
+    int base = p.c0;
+    for (int c = 0; c < p.n_tails; ++c) {
+      const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+      for (int j = tid; j < p.tail_n[c]; j += 1024) f(lp_key(trow[j] + off[c]), base + j);
+      base += p.tail_n[c];
+    }
+  };
+  uint32_t tmax = 0;
+  each([&](uint32_t key, int) { tmax = max(tmax, key); });
+  sample_row(each, each, tmax, i, a, sm);
+}
+extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                            int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                            int rows, int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids,
+                                            int step, const int* step_dev, int* tokens, float* lps, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_sample: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample: 1 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_sample: inv_temp > 0");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample: seed_dev, tokens and lps are required");
+  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(vocab >= k && vocab < (1L << 24), "logprob_sample: k <= vocab < 2^24");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps;
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    hipLaunchKernelGGL(logprob_sample_regs_kernel, dim3(rows), dim3(1024), 0, stream, p, a);
+    return tell_check_launch("logprob_sample (registers)");
+  }
+  hipLaunchKernelGGL(logprob_sample_stream_kernel, dim3(rows), dim3(1024), 0, stream, p, a);
+  return tell_check_launch("logprob_sample");
+}
+
+// steps 2-5 of the sampling semantics on given candidates (sorted best first): one thread per row
+__global__ __launch_bounds__(256) void sample_candidates_kernel(const int* __restrict__ cand_tokens,
+                                                                const float* __restrict__ cand_lps, int rows, SampleArgs a) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const uint32_t row = a.row_ids ? (uint32_t)a.row_ids[r] : (uint32_t)r;
+  const uint32_t step = a.step_dev ? (uint32_t)(*a.step_dev + 1) : (uint32_t)a.step;
+  const float u = tell_sample_u(*a.seed_dev, row, step);
+  const int j = tell_sample_pick(cand_lps + (long)r * a.k, a.k, a.inv_temp, u);
+  a.tokens[r] = cand_tokens[(long)r * a.k + j];
+  a.lps[r] = cand_lps[(long)r * a.k + j];
+}
+extern "C" int tell_sample_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp,
+                                      const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,
+                                      float* lps, hipStream_t stream) {
+  TELL_REQUIRE(k >= 1 && k <= 64, "sample_candidates: 1 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "sample_candidates: inv_temp > 0");
+  TELL_REQUIRE(seed_dev && cand_tokens && cand_lps && tokens && lps, "sample_candidates: null pointer");
+  if (rows <= 0) return TELL_OK;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps;
+  hipLaunchKernelGGL(sample_candidates_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, cand_tokens, cand_lps, rows, a);
+  return tell_check_launch("sample_candidates");
+}
+
 // ------------------------------------------------------------------ greedy generation: one step's bookkeeping
 // What the loop of transformer_faces_objects.py:443-494 does per token after the arg-max, for all rows at once: a row
 // that has not finished records token and log-prob (divided by the sampling temperature), a row that emits EOS now is

@@ -103,6 +103,7 @@ extern "C" int tell_set_pos_next_ptr(void* next, hipStream_t) {
 }
 extern "C" uint32_t tell_keep_field_host(uint32_t seed, uint32_t salt, uint64_t idx) { return tell_keep_field(seed, salt, idx); }
 extern "C" uint32_t tell_drop_threshold_host(float p) { return tell_drop_threshold(p); }
+extern "C" float tell_sample_uniform_host(uint32_t seed, uint32_t row, uint32_t step) { return tell_sample_u(seed, row, step); }
 
 // rate of the device wall clock (wall_clock64) that the GEMM kernels' execution-span stamps use (bench.py roofline)
 extern "C" int tell_wall_clock_khz(void) {

@@ -189,3 +189,30 @@ __device__ __forceinline__ void tell_keep4_bits(uint32_t x, uint32_t y, uint32_t
   k2 = (b & 0xffffu) >= thr;
   k3 = (b >> 16) >= thr;
 }
+
+// ---------------------------------------------------------------- top-k sampling (include/tell_hip.h tell_adaptive_logprob_sample)
+// The uniform of one draw: two rounds of the quad mix over (seed, row) and the step, 24 bits of the result as u in [0, 1).
+// `row` is the ORIGINAL batch row, `step` the logical step index.  Restated in numpy (tell_amd/rng.py sample_uniform);
+// tests/test_sampling_host.py checks the restatement against tell_sample_uniform_host and the statistics.
+__device__ __host__ __forceinline__ uint32_t tell_sample_bits(uint32_t seed, uint32_t row, uint32_t step) {
+  const uint32_t h = tell_quad_mix(tell_quad_x(seed, row), tell_quad_y(step, row));
+  return tell_quad_mix(h, 0x27D4EB2Fu);
+}
+__device__ __host__ __forceinline__ float tell_sample_u(uint32_t seed, uint32_t row, uint32_t step) {
+  return (float)(tell_sample_bits(seed, row, step) >> 8) * (1.0f / 16777216.0f);
+}
+// The pick over k candidates sorted best first (lp[0] largest): w_j = exp((lp_j - lp_0) * inv_temp), c_j their running sum
+// in candidate order, the smallest j with u * c_{k-1} < c_j (k - 1 if none) - multinomial(exp(lp / T)) up to the RNG.
+// (The weights are recomputed in the second loop instead of stored: the same operations give the same values.)
+__device__ __host__ __forceinline__ int tell_sample_pick(const float* lp, int k, float inv_temp, float u) {
+  const float l0 = lp[0];
+  float c = 0.f;
+  for (int j = 0; j < k; ++j) c += expf((lp[j] - l0) * inv_temp);
+  const float t = u * c;
+  float r = 0.f;
+  for (int j = 0; j < k; ++j) {
+    r += expf((lp[j] - l0) * inv_temp);
+    if (t < r) return j;
+  }
+  return k - 1;
+}

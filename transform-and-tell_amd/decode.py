@@ -208,12 +208,13 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
     -> (token int32 [N], log-prob fp32 [N], None); topk = k > 0 (beam search): the k best of every row, best first,
-    (tokens int32 [N,k], log-probs fp32 [N,k], None)."""
+    (tokens int32 [N,k], log-probs fp32 [N,k], None); sample = (k, inv_temp, seed_dev, row_ids, step): the last launch is
+    the top-k draw instead of the arg-max (ops.logprob_sample)."""
     N, E = x2.shape
     dev = x2.device
     c0, n_tails = cutoffs[0], len(tails) // 2
@@ -254,6 +255,8 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0):
         ns = [e.shape[0] for e in embs] + [0] * (3 - n_tails)
         tl = [logits[:, offs[1 + i]:] if i < n_tails else None for i in range(3)]
         lds = [LD if i < n_tails else 0 for i in range(3)]
+        if sample is not None:
+            return ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample)
         if topk:
             tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
             lps = torch.empty(N, topk, dtype=torch.float32, device=dev)
@@ -295,6 +298,8 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0):
         ops.gemm(big[0]['a'], big[0]['b'], out=big[0]['out'])
     elif big:       # two dependent launches of 235 / 473 column tiles (12 + 16 us) -> one launch of 708
         ops.gemm_grouped(big)
+    if sample is not None:
+        return ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample)
     if topk:
         tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
         lps = torch.empty(N, topk, dtype=torch.float32, device=dev)

@@ -9,7 +9,7 @@ import math
 import torch
 
 from .. import ops
-from .transformer import CaptionModel, Model
+from .transformer import CaptionModel, Model, check_sampling, draw_seed
 
 
 @Model.register('baseline_glove')
@@ -25,9 +25,8 @@ class BaselineGloveModel(Model):
             resnet = resnet152()
         self.resnet = resnet
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
-        if sampling_topk != 1:
-            raise NotImplementedError('generation is greedy (sampling_topk: 1 in every config)')
-        self.sampling_topk, self.sampling_temp, self.max_caption_len = sampling_topk, sampling_temp, max_caption_len
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
+        self.max_caption_len = max_caption_len
         self.n_batches = self.n_samples = 0
 
     @staticmethod
@@ -88,8 +87,14 @@ class BaselineGloveModel(Model):
         """Greedy decode of :247-320.  The reference re-decodes the whole prefix for the still-active rows at every
         step; rows are independent and the decoder is recurrent, so carrying the LSTM state forward and keeping the
         batch at its full size (finished rows masked) gives the same token ids: pad after <eos>, length = 1 + steps
-        until the last row has finished."""
+        until the last row has finished.  sampling_topk = k > 1 (:247-320 with topk + multinomial): the k best of the full
+        log-prob row, sorted, and the draw of tell_sample_candidates keyed on (seed, row, step) - one seed per call from
+        torch's default CPU generator."""
         B, dev = caption_ids.shape[0], caption_ids.device
+        k = int(self.sampling_topk)
+        if k > 1:
+            seed_word = torch.full((1,), draw_seed(), dtype=torch.int32, device=dev)
+            inv_temp = 1.0 / float(self.sampling_temp)
         cur = caption_ids[:, 0:1].contiguous()
         finished = cur[:, 0] == eos
         ids = torch.full((B, gen_len + 1), self.padding_idx, dtype=torch.long, device=dev)
@@ -99,7 +104,15 @@ class BaselineGloveModel(Model):
         for i in range(gen_len):
             out = self.decoder({self.index: cur}, contexts, incremental_state=state)
             lp_all = self.decoder.get_normalized_probs((out[0][:, -1:], None), log_probs=True).squeeze(1).float()
-            lp, tok = lp_all.max(dim=-1)
+            if k == 1:
+                lp, tok = lp_all.max(dim=-1)
+            else:
+                top_lp, top_ix = lp_all.topk(k, dim=-1)                            # sorted, best first
+                tok32 = torch.empty(B, dtype=torch.int32, device=dev)
+                lp = torch.empty(B, dtype=torch.float32, device=dev)
+                ops.call('tell_sample_candidates', top_ix.to(torch.int32).contiguous(), top_lp.contiguous(), B, k, inv_temp,
+                         seed_word, None, i, None, tok32, lp)
+                tok = tok32.long()
             ids[:, i + 1] = torch.where(finished, ids[:, i + 1], tok)
             lps[:, i] = torch.where(finished, lps[:, i], lp / self.sampling_temp)
             finished = finished | (tok == eos)
@@ -127,9 +140,7 @@ class TransformerGloveModel(CaptionModel):
             resnet = resnet152()
         self.resnet = resnet
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
-        if sampling_topk != 1:
-            raise NotImplementedError('generation is greedy (sampling_topk: 1 in every config)')
-        self.sampling_topk, self.sampling_temp = sampling_topk, sampling_temp
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0

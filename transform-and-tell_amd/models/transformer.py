@@ -64,6 +64,27 @@ class Model(nn.Module, Registrable):
         return output_dict
 
 
+MAX_SAMPLING_TOPK = 64          # tell_adaptive_logprob_sample's exact top-k
+
+
+def check_sampling(sampling_topk, sampling_temp):
+    """The caption models' `sampling_topk` / `sampling_temp` (transformer_faces_objects.py:38-55): top-k sampling with a
+    temperature, 1 <= k <= 64 (k = 1: the arg-max token) and T > 0.  -> (k, T); ValueError otherwise."""
+    if isinstance(sampling_topk, bool) or not isinstance(sampling_topk, (int, float)) or int(sampling_topk) != sampling_topk \
+            or not 1 <= int(sampling_topk) <= MAX_SAMPLING_TOPK:
+        raise ValueError('sampling_topk must be an integer in 1..%d (got %r)' % (MAX_SAMPLING_TOPK, sampling_topk))
+    if isinstance(sampling_temp, bool) or not isinstance(sampling_temp, (int, float)) or not float(sampling_temp) > 0.0 \
+            or float(sampling_temp) == float('inf'):
+        raise ValueError('sampling_temp must be a finite number > 0 (got %r)' % (sampling_temp,))
+    return int(sampling_topk), float(sampling_temp)
+
+
+def draw_seed():
+    """The seed of one batch's sampled decode: 31 bits from torch's default CPU generator (torch.manual_seed makes the
+    captions reproducible)."""
+    return int(torch.randint(0, 1 << 31, (1,)).item())
+
+
 class CaptionModel(Model):
     USE_FACES_OBJECTS = False
     EXTRA_CONTEXTS = ()          # which of ('faces', 'obj') the model feeds to its decoder
@@ -85,9 +106,7 @@ class CaptionModel(Model):
         self.use_context = use_context
         self.padding_idx = padding_value
         self.evaluate_mode = evaluate_mode
-        self.sampling_topk, self.sampling_temp = sampling_topk, sampling_temp
-        if sampling_topk != 1:
-            raise NotImplementedError('generation is greedy (sampling_topk: 1 in every config)')
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -97,6 +116,16 @@ class CaptionModel(Model):
         # captured encoder / decode graphs bake in the addresses of working copies of the weights: anything that can
         # re-home those copies (a checkpoint load, a trainer re-flagging requires_grad) drops the captures
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.reset_graphs())
+
+    def _sampling(self):
+        """-> (k, T) when generation samples (sampling_topk > 1), None for the arg-max decode (sampling_topk = 1)."""
+        k = int(self.sampling_topk)
+        return (k, float(self.sampling_temp)) if k > 1 else None
+
+    def _check_beam(self, beam_size):
+        if int(beam_size) > 1 and self._sampling() is not None:
+            raise ValueError('beam search (beam_size %d) and top-k sampling (sampling_topk %d) do not combine: the reference '
+                             'samples without a beam' % (int(beam_size), int(self.sampling_topk)))
 
     def reset_graphs(self):
         """Forget every captured hipGraph of this model (encoders, decode steps); they are re-recorded on next use."""
@@ -354,6 +383,7 @@ class CaptionModel(Model):
             if self.training or not self.evaluate_mode or not self.lanes_usable():
                 yield from self.generate_stream(batches, forward=True)  # nothing to decode / no static-batch decode loop
                 return
+        self._check_beam(beam_size)
         it = iter(batches)
         main = torch.cuda.current_stream()
         lane_streams = [streams.get('decode_lane_%d' % i) for i in range(lanes)]
@@ -373,12 +403,14 @@ class CaptionModel(Model):
                     heads.append((od, b.get('metadata'), caption_ids.shape[0]))
                 else:
                     caption_ids, _, contexts = self._forward(**f)
+                # (sampling: the batch's seed is drawn here, in batch order - the draws of `generate` batch by batch)
+                seed = draw_seed() if self._sampling() is not None else None
                 ev = torch.cuda.Event()
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
                     g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln) if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln))
+                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -451,6 +483,7 @@ class CaptionModel(Model):
             from .baseline_glove import BaselineGloveModel
             lps, ids = BaselineGloveModel._generate(self, caption_ids, contexts, gen_len, eos)
             return lps, ids, []
+        self._check_beam(beam_size)
         if beam_size > 1:
             return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos)
         if self.fast_generation:
@@ -470,19 +503,24 @@ class CaptionModel(Model):
     def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0):
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane))
 
-    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0):
+    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
         per-step gather of the contexts and no per-step host synchronisation (the all-finished test
         runs every `check_every` steps), (3) fused arg-max over the adaptive softmax.  Rows are
         independent, so every row sees exactly the arithmetic of the reference flow: token ids are
-        identical, pad=1 after EOS, output length = 1 + steps until the last row finished."""
+        identical, pad=1 after EOS, output length = 1 + steps until the last row finished.
+        sampling_topk > 1: the head's last launch draws from the top k instead (tell_adaptive_logprob_sample), keyed on
+        (seed, row, step) - `seed` (default: drawn now, draw_seed) goes into the stepper's device word before the first step."""
         dec = self.decoder
         B = caption_ids.shape[0]
         dev = caption_ids.device
         kv = dec.project_contexts(contexts)
-        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane)
+        sampling = self._sampling()
+        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling)
+        if sampling is not None:
+            step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous()
         finished = cur[:, 0] == eos
         fused = caption_ids.is_cuda and hasattr(step, 'cur')      # one bookkeeping launch per token (tell_greedy_update)
@@ -545,7 +583,7 @@ class CaptionModel(Model):
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), []
         return lps[:, :steps], ids[:, :steps + 1], []
 
-    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0):
+    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None):
         """-> step(i, cur [B,1]) -> (token [B,1], log-prob [B,1]) - or, with topk=k, the k best (tokens [B,1,k],
         log-probs [B,1,k]) of every row - for the cached greedy / beam generators; step.reorder(rows) permutes the
         rows of the incremental state (beam search).
@@ -554,23 +592,38 @@ class CaptionModel(Model):
         one by one) is captured ONCE per (batch, context shapes) signature and replayed: every tensor it touches is
         static - the DynamicConv input buffers have their final K-1 rows from the start (zero history), the
         projected K/V and masks are copied into fixed buffers per caption batch, and the position offset comes from
-        the graph's device step counter (embed_finalize reads it, like the dropout kernels)."""
+        the graph's device step counter (embed_finalize reads it, like the dropout kernels).
+
+        sample = (k, T): every step draws from the top k at temperature T (AdaptiveSoftmax.sample) with the seed in the
+        device word step.seed and the step index from the host (eager) or from the device counter (captured: every replay of
+        the single-step and the multi-step graphs draws fresh numbers); (k, T) is part of the capture's signature."""
         dec = self.decoder
         names = [n for layer_kv in kv[:1] for n in layer_kv]
+
+        def make_head(seed_dev):
+            if sample is not None:
+                return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx)
+            if topk:
+                return lambda x, sidx: dec.adaptive_softmax.topk(x, topk)
+            return lambda x, sidx: dec.adaptive_softmax.greedy(x)
         if not graphs.ENABLED or self.training or not torch.is_tensor(kv[0][names[0]][0]) or \
                 not kv[0][names[0]][0].is_cuda:
             state = {}
-            head = (lambda x: dec.adaptive_softmax.topk(x, topk)) if topk else dec.adaptive_softmax.greedy
+            seed_word = torch.zeros(1, dtype=torch.int32, device=next(dec.parameters()).device)
+            head = make_head(seed_word)
 
             def eager_step(i, cur):
-                return head(dec({self.index: cur}, contexts, incremental_state=state, kv_cache=kv)[0][:, -1:])
+                return head(dec({self.index: cur}, contexts, incremental_state=state, kv_cache=kv)[0][:, -1:], int(i))
             eager_step.reorder = lambda rows: dec.reorder_incremental_state(state, rows)
+            eager_step.seed = seed_word
             return eager_step
         dev, dtype = kv[0][names[0]][0].device, kv[0][names[0]][0].dtype
         # lane: decode loops that are in flight TOGETHER (generate_lanes: two caption batches decoded on two streams) own
         # their graphs, static buffers, counters and split-reduction workspace
         sig = (B, dtype, topk, int(gen_len), tuple((n, tuple(kv[0][n][0].shape), tuple(kv[0][n][1].shape)) for n in names),
                dec.embedder.token_embedder_position.weights.data_ptr(), int(lane))
+        if sample is not None:                                    # (greedy and beam signatures are unchanged)
+            sig = sig + (('sample', int(sample[0]), float(sample[1])),)
         cache = self.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -587,6 +640,7 @@ class CaptionModel(Model):
                 # counter[0]: the position offset the kernels of a replay read; counter[1]: the NEXT step's offset when
                 # the bookkeeping launch is part of the captured step (`ig`, below)
                 'graph': None, 'counter': torch.zeros(2, dtype=torch.int32, device=dev), 'book': {},
+                'seed': torch.zeros(1, dtype=torch.int32, device=dev),      # the sampling seed (written per caption batch)
                 'cur': torch.zeros(B, 1, dtype=torch.long, device=dev),
                 'kv': None,
                 # (key-padding masks as the uint8 the attention kernels read: converted once per caption batch)
@@ -641,25 +695,26 @@ class CaptionModel(Model):
         pos_key = dec.embedder.token_embedder_position._state_key
         h['state'].pop(pos_key, None)
 
-        head = (lambda x: dec.adaptive_softmax.topk(x, topk)) if topk else dec.adaptive_softmax.greedy
+        head = make_head(h['seed'])
 
         c_cur, c_next = h['counter'][0:1], h['counter'][1:2]
         # where a bookkeeping launch leaves the next step's offset: the word the embedder's kernel reads (in-graph
         # bookkeeping), or the counter itself
         c_out = c_next if h['ig'] else c_cur
 
-        def run():
+        def run(sidx):
+            """sidx: the step index for a sampling head - the host's int, or c_cur inside a captured step (i - 1 there)."""
             from .. import decode as _dec2
             prev_lane = _dec2.CUR_LANE[0]
             _dec2.CUR_LANE[0] = int(lane)
             try:
                 out = dec({self.index: h['cur']}, h['ctx'], incremental_state=h['state'], kv_cache=h['kv'])
-                return head(out[0][:, -1:])
+                return head(out[0][:, -1:], sidx)
             finally:
                 _dec2.CUR_LANE[0] = prev_lane
 
         def eager(i, post):
-            res = run()
+            res = run(int(i))
             if post is not None:
                 post(res, i, None)
             return res
@@ -687,7 +742,7 @@ class CaptionModel(Model):
                         #  dropped - `held` gives them back, like StepGraph / GraphedCall do)
                         with graphs.no_gc(), ops.hip.tile_slots() as held, torch.cuda.graph(g):
                             with ops.hip.bound_stream():
-                                h['out'] = run()
+                                h['out'] = run(c_cur)
                                 if inside:
                                     post(h['out'], i, c_cur)
                         h['tile_slots'] = held
@@ -731,7 +786,7 @@ class CaptionModel(Model):
                             with ops.hip.bound_stream():
                                 for j in range(int(n)):
                                     h['state'].update(h['host_ints'])   # the constants of the single-step capture
-                                    post(run(), i + j, c_cur)
+                                    post(run(c_cur), i + j, c_cur)
                         h[key + ('slots',)] = held
                     finally:
                         ops.call('tell_set_rng_step_ptr', None)
@@ -769,6 +824,7 @@ class CaptionModel(Model):
         step.multi = multi
         step.cur = h['cur']
         step.book = book
+        step.seed = h['seed']
         step.counter_out = c_out                                  # (base 1: the offset of step i is i - 1)
         step.back = h['state'].get('_back')                       # ancestor table of the DynamicConv rings, or None
         return step
@@ -883,17 +939,21 @@ class CaptionModel(Model):
     def _generate_reference_flow(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2):
         """Greedy decoding with the reference's semantics (finished rows leave the batch, pad=1 after
         EOS, loop ends when no row is active).  The arg-max over the 50 265-way adaptive softmax is
-        fused (no [B, vocab] log-prob tensor)."""
+        fused (no [B, vocab] log-prob tensor).  sampling_topk > 1: the fused top-k draw keyed on the alive rows' ORIGINAL
+        batch rows, so the captions equal the cached flow's under the same seed."""
         state = {}
         B = caption_ids.shape[0]
         dev = caption_ids.device
+        sampling = self._sampling()
+        if sampling is not None:
+            seed_word = torch.full((1,), draw_seed(), dtype=torch.int32, device=dev)
         seed = caption_ids[:, 0:1]
         alive = seed[:, -1] != eos
         keep = alive
         cur = seed
         log_probs, paths, attns = [], [seed], []
         names = [k for k in contexts if not k.endswith('_mask') and not k.startswith('_')]
-        for _ in range(gen_len):
+        for i in range(gen_len):
             self.decoder.filter_incremental_state(state, keep)                      # :417
             ctx_i = {}
             for n in names:                                                         # :420-431
@@ -901,7 +961,12 @@ class CaptionModel(Model):
                 ctx_i[n + '_mask'] = contexts[n + '_mask'][alive]
             dec_out = self.decoder({self.index: cur[:, -1:]}, ctx_i, incremental_state=state)
             attns.append(dec_out[1]['attn'])
-            tok, lp = self.decoder.adaptive_softmax.greedy(dec_out[0][:, -1:])      # :443-464
+            if sampling is None:
+                tok, lp = self.decoder.adaptive_softmax.greedy(dec_out[0][:, -1:])  # :443-464
+            else:                                                                   # :443-470, topk + multinomial
+                rows = alive.nonzero().squeeze(1).to(torch.int32)
+                tok, lp = self.decoder.adaptive_softmax.sample(dec_out[0][:, -1:], sampling[0], sampling[1], seed_word, i,
+                                                               row_ids=rows)
             sel_ix = tok.long()
             sel_lp = lp / self.sampling_temp
             full_lp = sel_lp.new_zeros(B, 1)

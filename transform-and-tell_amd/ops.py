@@ -1744,9 +1744,25 @@ def adaptive_loss(x, target, cutoffs, pad_idx, emb0, class_proj, tails):
     return AdaptiveLossFn.apply(x, target, tuple(cutoffs), pad_idx, emb0, class_proj, *tails)
 
 
-def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0):
+def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
+    """The sampling head's last launch (tell_adaptive_logprob_sample) over the fp32 logits of the head and the tails.
+    sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
+    int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
+    counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None)."""
+    k, inv_temp, seed_dev, row_ids, step = sample
+    step_dev = step if torch.is_tensor(step) else None
+    token = torch.empty(N, dtype=torch.int32, device=head.device)
+    token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
+    call('tell_adaptive_logprob_sample', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
+         ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token,
+         token_lp)
+    return token, token_lp, None
+
+
+def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
-    topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search)."""
+    topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
+    sample = (k, inv_temp, seed_dev, row_ids, step): one top-k draw per row instead of the arg-max (logprob_sample)."""
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
@@ -1756,7 +1772,7 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
-        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk)
+        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
     def logits(a, w):                    # fp32 rows start on 16 bytes (see AdaptiveLossFn): vector stores in the epilogue
@@ -1770,6 +1786,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
         tl[i] = logits(h, weight(emb))
         ld[i], nn_[i] = tl[i].stride(0), tl[i].shape[1]
     vocab = c0 + sum(nn_)
+    if sample is not None and not want_full:
+        return logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample)
     if topk:
         tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
         lps = torch.empty(N, topk, dtype=torch.float32, device=dev)

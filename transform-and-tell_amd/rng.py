@@ -35,3 +35,33 @@ def keep_mask(seed, salt, n_or_idx, p):
     """float32 array of 0/1 keep flags for element indices 0..n-1 (or the given indices)."""
     idx = np.arange(n_or_idx, dtype=np.uint64) if np.isscalar(n_or_idx) else np.asarray(n_or_idx, dtype=np.uint64)
     return (keep_field(seed, salt, idx) >= threshold(p)).astype(np.float32)
+
+
+def _mix(x, y):
+    """tell_quad_mix on uint64 arrays holding 32-bit words."""
+    h = x ^ y
+    h = h ^ (h >> _U(16))
+    h = (h * _U(0x7FEB352D)) & M32
+    return h ^ (h >> _U(15))
+
+
+def sample_uniform(seed, row, step):
+    """u in [0, 1) of one top-k draw (csrc/common.h tell_sample_u): two rounds of the quad mix over (seed, row) and the
+    step, 24 bits as a float32.  Broadcasts over array arguments."""
+    seed, row, step = (np.asarray(v, dtype=np.uint64) & M32 for v in (seed, row, step))
+    x = (((row * _U(0x9E3779B1)) & M32) + ((seed * _U(0x85EBCA6B)) & M32)) & M32     # tell_quad_x(seed, row)
+    y = (((step * _U(0xC2B2AE3D)) & M32) + _U(0x27D4EB2F)) & M32               # tell_quad_y(step, row): row < 2^32
+    h = _mix(_mix(x, y), _U(0x27D4EB2F))
+    return ((h >> _U(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
+
+
+def sample_pick(sorted_lps, inv_temp, u):
+    """The pick of tell_sample_pick over candidates sorted best first, in fp32 with the kernel's order of additions:
+    w_j = exp((lp_j - lp_0) * inv_temp), c_j = w_0 + ... + w_j, the smallest j with u * c_{k-1} < c_j (k - 1 if none)."""
+    lp = np.asarray(sorted_lps, dtype=np.float32)
+    it = np.float32(inv_temp)
+    w = np.exp((lp - lp[0]) * it).astype(np.float32)
+    c = np.add.accumulate(w, dtype=np.float32)                        # sequential, like the kernel's loop
+    t = np.float32(u) * c[-1]
+    hit = np.nonzero(t < c)[0]
+    return int(hit[0]) if hit.size else len(lp) - 1
