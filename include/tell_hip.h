@@ -621,6 +621,75 @@ int tell_roberta_embed(const long* ids, int B, int S, int pad, const void* word,
 
 int tell_mask_rows(void* x, const uint8_t* mask, long rows, int C, int dtype, tell_stream_t stream);
 
+/* ---- copy mechanism of transformer_pointer / transformer_pointer_2 (csrc/copy.hip)
+ * Copy attention (multi_head.py:14-204 multi_head_attention_score_forward): q [T,B,H*D] already scaled, element
+ * (t,b,h,d) at q + t*q_st + b*q_sb + h*D + d; k [S,B,H*D] likewise (k_ss, k_sb); bias_k [H*D] and a zero key are the
+ * virtual columns S, S+1; mask [B,S] uint8 (1 = padding -> -inf); fp32 softmax per head; dropout p on the per-head
+ * weights (counter-based, index ((b*H+h)*T+t)*(S+2)+s); head mean.  w [B,T,S] fp32 drops the virtual columns and is
+ * zero where proper [B,S] int8 < 1 (proper may be NULL).  lse [B,H,T] fp32.  D <= 64, S <= 512. */
+int tell_copy_attn_fwd(const void* q, const void* k, const void* bias_k, const uint8_t* mask, const int8_t* proper,
+                       float* w, float* lse, int B, int H, int T, int S, int D, long q_st, long q_sb, long k_ss,
+                       long k_sb, float p, uint32_t seed, uint32_t salt, int dtype, tell_stream_t stream);
+/* dw [B,T,S] fp32 -> dq (q's strides), dk (k's strides), dbias_k_rows [B*T, H*D] fp32 per-row partials of the bias_k
+ * gradient (the caller sums the rows); delta [B,H,T] fp32 scratch.  The per-head probabilities are recomputed. */
+int tell_copy_attn_bwd(const void* q, const void* k, const void* bias_k, const uint8_t* mask, const int8_t* proper,
+                       const float* lse, const float* dw, void* dq, void* dk, float* dbias_k_rows, float* delta,
+                       int B, int H, int T, int S, int D, long q_st, long q_sb, long k_ss, long k_sb, float p,
+                       uint32_t seed, uint32_t salt, int dtype, tell_stream_t stream);
+/* V = the number of distinct ids of cat(context_ids, targets) (transformer_pointer.py:264), counted with a bitmap
+ * of ceil(vocab/32) words plus one flag word; *count is written on the device, -1 when an id lies outside [0, vocab)
+ * (the reference's index_copy_ fails there; tell_copy_loss_fwd variant 2 then yields NaN). */
+int tell_copy_vocab_count(const long* ctx_ids, long n_ctx, const long* targets, int B, int T, long tgt_sb, int vocab,
+                          uint32_t* bitmap, int* count, tell_stream_t stream);
+/* Fused copy loss (pointer_loss :253-313).  w [B,T,S] from tell_copy_attn_fwd, ctx_ids [B,S], targets / copy_mask
+ * [B,T] (row strides tgt_sb, cm_sb).  Per entity row (copy_mask >= 1): p_t = the summed weight of the target id,
+ * lp = log p_t (0 when p_t = 0); variant 1 (transformer_pointer) term = -lp, variant 2 (transformer_pointer_2)
+ * term = -lp + log(sum_{p>0} p + V - n_pos), V = *vcount.  *loss = sum over entity indices i = 1 .. max of the mean term
+ * of index i (NaN when an index in that range has no row, as in the reference).  term, p_target, z, scale: [B,T] fp32
+ * kept for the backward (scale = 1 / the row index's count). */
+int tell_copy_loss_fwd(const float* w, const long* ctx_ids, const long* targets, long tgt_sb, const long* copy_mask,
+                       long cm_sb, const int* vcount, int variant, int B, int T, int S, float* term, float* p_target,
+                       float* z, float* scale, float* loss, tell_stream_t stream);
+/* dw [B,T,S] fp32 (assigned) from the device scalar *dloss */
+int tell_copy_loss_bwd(const float* dloss, const float* w, const long* ctx_ids, const long* targets, long tgt_sb,
+                       const long* copy_mask, long cm_sb, const float* p_target, const float* z, const float* scale,
+                       int variant, int B, int T, int S, float* dw, tell_stream_t stream);
+/* entity_fc + CrossEntropy(ignore_index=-1) against min(copy_mask, 1) (:211-228).  x: row (t,b) at t*x_st + b*x_sb,
+ * E wide; w [2,E] fp32 (the weight-normed weight), bias [2] fp32.  logits [B,T,2] fp32, *loss, *nvalid fp32. */
+int tell_entity_head_fwd(const void* x, long x_st, long x_sb, const float* w, const float* bias, const long* copy_mask,
+                         long cm_sb, int B, int T, int E, float* logits, float* loss, float* nvalid, int dtype,
+                         tell_stream_t stream);
+/* the logits alone (the generation step): logits [B,T,2] fp32 */
+int tell_entity_logits(const void* x, long x_st, long x_sb, const float* w, const float* bias, int B, int T, int E,
+                       float* logits, int dtype, tell_stream_t stream);
+/* dx (x's layout, assigned), dlogits [B,T,2] fp32 scratch, dw [2,E] fp32 (assigned), dbias [2] fp32 (accumulated). */
+int tell_entity_head_bwd(const float* dloss, const float* nvalid, const float* logits, const long* copy_mask,
+                         long cm_sb, const void* x, long x_st, long x_sb, const float* w, void* dx, long dx_st,
+                         long dx_sb, float* dlogits, float* dw, float* dbias, int B, int T, int E, int dtype,
+                         tell_stream_t stream);
+/* Causal entity attention (self_attention.py, downsampled_single_head.py _mask_future_full + scalar_bias.py): query i
+ * at position pos0 + i sees keys s < pos0 + i, plus a slot of logit 0 and value 0; no dropout; logits are
+ * scale * q.k (q unscaled, dq likewise).  Layout as
+ * tell_attn_fwd; D = 64; lse [B,H,Tq].  pos0 = S - 1, Tq = 1 is the generation step over a K/V history of S rows. */
+int tell_causal_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int H, int Tq,
+                         int S, int D, int pos0, long q_st, long q_sb, long k_ss, long k_sb, long v_ss, long v_sb,
+                         long o_st, long o_sb, float scale, int dtype, tell_stream_t stream);
+/* training backward (Tq = S = T, pos0 = 0): dq (q's strides), dk / dv (k's / v's strides); delta [B,H,T] scratch */
+int tell_causal_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                         const float* lse, void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int D,
+                         long q_st, long q_sb, long k_ss, long k_sb, long v_ss, long v_sb, long o_st, long o_sb,
+                         float scale, int dtype, tell_stream_t stream);
+/* The copy decision of one generation step (_generate :488-590) for Ba alive rows; rows [Ba] int32 = each alive row's
+ * batch row.  q [Ba,H*D] (row stride q_sb, scaled); k [S,B,H*D] the article keys projected once per batch; copy
+ * attention without dropout, proper mask, per-id sums, arg-max (ties to the lower id), top p < 1e-6 -> p = 1e-6 and no
+ * copy, no copy of an id in hist[b, 0 .. n_hist) (hist [B, hist_len] int64), copy only where entity_logits [Ba,2]
+ * has logit 1 > logit 0.  Writes tok [Ba] (the copied id or gen_tok), copied [Ba] uint8, prob [Ba] fp32 and
+ * hist[b, n_hist] (the copied id, else -1). */
+int tell_copy_step(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k,
+                   const uint8_t* mask, const int8_t* proper, const long* ctx_ids, const int* rows,
+                   const float* entity_logits, const long* gen_tok, long* hist, int hist_len, int n_hist, int Ba, int H,
+                   int S, int D, long* tok, uint8_t* copied, float* prob, int dtype, tell_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,3 +5,4 @@ from .transformer import (TransformerFacesObjectModel, TransformerFlattenedModel
                           CaptionModel)
 from .decoder_lstm import LSTMDecoder  # noqa: F401
 from .baseline_glove import BaselineGloveModel, TransformerGloveModel  # noqa: F401
+from .pointer import TransformerPointer2Model, TransformerPointerModel  # noqa: F401

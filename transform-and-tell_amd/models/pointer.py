@@ -1,0 +1,254 @@
+"""tell/models/transformer_pointer.py and transformer_pointer_2.py on the MI355X path: transformer_faces plus the
+copy mechanism (an entity head that decides, per caption token, whether to copy a name from the article, and a copy
+attention over the article that picks which).
+
+Training restates `pointer_loss` (:180-313) with the kernels of csrc/copy.hip: entity self-attention over strictly
+earlier positions, entity_fc + cross entropy, 16-head copy attention with head-mean weights, and the fused copy loss
+(no [B, T, V] tensor, no host loop over entity indices).  Variant 1 (transformer_pointer) takes the mean -log p of
+each entity index, variant 2 (transformer_pointer_2) a cross entropy over the batch's reduced vocabulary.  The loss
+is entity_loss + copy_loss in bits; gen_loss is computed and logged only.
+
+Generation (_generate :427-696) is greedy: per step the decoder's token, the entity decision over the step's output
+and its history, and one copy-decision launch (csrc/copy.hip tell_copy_step) with the article keys projected once
+per batch."""
+import logging
+import math
+from collections import defaultdict
+
+import torch
+import torch.nn as nn
+from torch.nn.init import constant_, xavier_normal_, xavier_uniform_
+
+from .. import ops
+from ..modules.linear import GehringLinear
+from ..modules.self_attention import SelfAttention
+from .transformer import CaptionModel, Model
+
+logger = logging.getLogger(__name__)
+
+
+def load_state_dict_with_prefix(module, state_dict, prefix=''):
+    """tell/modules/mixins.py LoadStateDictWithPrefix: keys missing from / unexpected by the checkpoint are reported
+    as a warning, not an error."""
+    sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+    result = nn.Module.load_state_dict(module, sd, strict=False)
+    if result.missing_keys:
+        logger.warning('missing keys in the checkpoint: %s', result.missing_keys)
+    if result.unexpected_keys:
+        logger.warning('unexpected keys in the checkpoint: %s', result.unexpected_keys)
+    return result
+
+
+class PointerModelBase(CaptionModel):
+    USE_FACES_OBJECTS = True
+    EXTRA_CONTEXTS = ('faces',)
+    COPY_VARIANT = 1
+    STEP_GRAPH = False             # the loss may be None (no copy target in the batch): the trainer stays eager
+    # the trainer's shape buckets would pad the article with pad ids: transformer_pointer_2's reduced vocabulary counts
+    # every id of the context, so padding the graphs need (and these models do not capture) would change its loss
+    SHAPE_BUCKETS = False
+
+    def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
+                 dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
+                 padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
+                 model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25):
+        if sampling_topk != 1:
+            raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
+        super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
+                         model_name, namespace, index, padding_value, use_context, sampling_topk, sampling_temp,
+                         weigh_bert, initializer, resnet, roberta, n_bert_layers)
+        if weigh_bert:
+            self.bert_weight_2 = nn.Parameter(torch.rand(n_bert_layers))      # :61-62
+        self.batch_history = defaultdict(float)        # summed on the device (0-d tensors); floats once get_metrics reads
+        self.copy_dropout = 0.1                      # p of the per-head copy weights (:234, a constant in the reference)
+        self.entity_fc = GehringLinear(1024, 2)
+        self.in_proj_weight = nn.Parameter(torch.empty(2 * 1024, 1024))     # :78-84
+        self.in_proj_bias = nn.Parameter(torch.empty(2 * 1024))
+        self.out_proj = GehringLinear(1024, 1024, bias=True)                 # never used (as in the reference)
+        self.bias_k = nn.Parameter(torch.empty(1, 1, 1024))
+        xavier_uniform_(self.in_proj_weight)
+        constant_(self.in_proj_bias, 0.)
+        xavier_normal_(self.bias_k)
+        self.entity_attn = SelfAttention(out_channels=1024, embed_dim=1024, num_heads=16, gated=True)
+        # never applied (project_input=False; out_proj of the copy attention): in the reference their grad stays None
+        # and BertAdam skips them, here the trainer's flat optimizer leaves out what does not require a gradient
+        am = self.entity_attn.attention.attention_module
+        for m in (self.out_proj, am.in_proj_q, am.in_proj_k, am.in_proj_v):
+            for p in m.parameters():
+                p.requires_grad_(False)
+        self.vocab_size = vocab_size
+        self.copy_heads = 16
+        if model_path is not None:
+            logger.info('Recovering weights from %s.', model_path)
+            load_state_dict_with_prefix(self, torch.load(model_path, map_location='cpu'))
+
+    def lanes_usable(self):
+        return False
+
+    def _check_beam(self, beam_size):
+        if int(beam_size) > 1:
+            raise ValueError('transformer_pointer has no beam search (beam_size %d)' % int(beam_size))
+
+    # ------------------------------------------------------------------ pieces shared by loss and generation
+    def _require_masks(self, context, caption=None):
+        """The masks of the names-matched indexer (`<index>_copy_masks`: entity index of each caption token, padded
+        with -1; `<index>_proper_masks`: 1 for the article tokens a name may be copied from, padded with -1)."""
+        need = [(context, '_proper_masks')] + ([(caption, '_copy_masks')] if caption is not None else [])
+        for field, key in need:
+            if self.index + key not in field:
+                raise ValueError('%s needs %s%s in the batch (a names-matched batch: see DESIGN.md section 13)'
+                                 % (type(self).__name__, self.index, key))
+
+    def _article_2(self, enc):
+        return ops.mix_layers(enc.stack, self.bert_weight_2) if self.weigh_bert else enc.stack[-1]   # :199-213
+
+    def _copy_q(self, X):
+        E = self.in_proj_weight.shape[1]
+        return ops.linear(X, self.in_proj_weight, self.in_proj_bias, rows=(0, E), alpha=(E // self.copy_heads) ** -0.5)
+
+    def _copy_k(self, x_article):
+        E = self.in_proj_weight.shape[1]
+        return ops.linear(x_article, self.in_proj_weight, self.in_proj_bias, rows=(E, 2 * E)).transpose(0, 1)
+
+    # ------------------------------------------------------------------ :103-178
+    def forward(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
+                attn_idx=None, encoded=None):
+        self._require_masks(context, caption)
+        copy_masks = caption[self.index + '_copy_masks'][:, 1:]
+        enc = encoded if encoded is not None else self.encode(context, image)
+        caption_ids, target_ids, contexts = self._forward(context, image, caption, face_embeds, None, enc)
+        decoder_out = self.decoder(caption, contexts)
+        loss_sum, sample_size = self.criterion(self.decoder.adaptive_softmax, decoder_out, target_ids)
+        gen_loss = loss_sum.detach().float() / sample_size / math.log(2)
+        entity_loss, copy_loss = self.pointer_loss(decoder_out[0], context, copy_masks, target_ids, enc)
+        entity_loss = entity_loss / math.log(2)
+        copy_loss = copy_loss / math.log(2)
+        loss = entity_loss + copy_loss
+        # :118-128.  A NaN loss in training is left to the trainer, which skips the update on a device flag (no host
+        # synchronisation here); outside training it is None, as in the reference
+        if (self.training and not loss.requires_grad) or (not self.training and bool(torch.isnan(loss))):
+            loss = None
+        for key, value in (('gen_loss', gen_loss), ('entity_loss', entity_loss), ('copy_loss', copy_loss)):
+            v = value.detach().float()
+            self.batch_history[key] = self.batch_history[key] + torch.where(torch.isnan(v), torch.zeros_like(v), v)
+        output_dict = {'loss': loss, 'sample_size': sample_size.reshape(())}
+        if not self.training and self.evaluate_mode:
+            gen_ids, _, should_copy, _ = self._generate_pointer(caption_ids, contexts, enc, context)
+            self._forward_generated(output_dict, gen_ids, [], metadata)
+            ids = gen_ids.cpu()
+            output_dict['copied_texts'] = [self.detokenize(x[should_copy[i].cpu()]) for i, x in enumerate(ids)]
+        self.n_samples += caption_ids.shape[0]
+        self.n_batches += 1
+        return output_dict
+
+    def pointer_loss(self, X, context, copy_masks, targets, enc):
+        """:180-313 -> (entity_loss, copy_loss), each a scalar (constant zeros when no token is an entity)."""
+        if not bool((copy_masks >= 1).any()):
+            z = torch.zeros((), device=X.device)
+            return z, z.clone()
+        X = X.transpose(0, 1)                                                       # [T, B, E]
+        X_entity = self.entity_attn(X)
+        fc = self.entity_fc
+        entity_loss, _ = ops.entity_head(X_entity, fc.weight_g, fc.weight_v, fc.bias, copy_masks)
+        proper = context[self.index + '_proper_masks'].to(torch.int8)
+        w = ops.copy_attention(self._copy_q(X), self._copy_k(self._article_2(enc)), self.bias_k, enc.article_mask,
+                               proper, self.copy_heads, p=self.copy_dropout, training=self.training)
+        copy_loss = ops.copy_loss(w, context[self.index], targets, copy_masks, self.COPY_VARIANT, self.vocab_size)
+        return entity_loss, copy_loss
+
+    # ------------------------------------------------------------------ :397-426, :427-696
+    def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
+                 attn_idx=None, beam_size=1, encoded=None):
+        self._check_beam(beam_size)
+        self._require_masks(context)
+        enc = encoded if encoded is not None else self.encode(context, image)
+        caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, None, enc)
+        gen_ids, log_probs, should_copy, copy_probs = self._generate_pointer(caption_ids, contexts, enc, context)
+        ids = gen_ids.cpu()
+        return {'gen_ids': gen_ids, 'log_probs': log_probs, 'should_copy': should_copy, 'copy_probs': copy_probs,
+                'generations': [self.detokenize(x[x > 1]) for x in ids],
+                'copied_texts': [self.detokenize(x[should_copy[i].cpu()]) for i, x in enumerate(ids)]}
+
+    @torch.no_grad()
+    def _generate_pointer(self, caption_ids, contexts, enc, context, gen_len=100, eos=2):
+        """-> (gen_ids [B, n+1], log_probs [B, n], should_copy [B, n+1] bool, copy_probs [B, n])."""
+        B = caption_ids.shape[0]
+        dev = caption_ids.device
+        E = self.in_proj_weight.shape[1]
+        k_article = self._copy_k(self._article_2(enc))                # [S, B, E], once per batch
+        proper = context[self.index + '_proper_masks'].to(torch.int8).contiguous()
+        ctx_ids = context[self.index].contiguous()
+        art_mask = enc.article_mask
+        hist = torch.full((B, gen_len + 1), -1, dtype=torch.int64, device=dev)    # copied ids, column 0 = the seed
+        state = {}
+        seed = caption_ids[:, 0:1]
+        alive = seed[:, -1] != eos
+        keep = alive
+        cur = seed
+        k_hist = v_hist = None
+        log_probs, paths, copies, probs = [], [seed], [torch.ones(B, 1, dtype=torch.bool, device=dev)], []
+        names = [k for k in contexts if not k.endswith('_mask') and not k.startswith('_')]
+        ea = self.entity_attn
+        for i in range(gen_len):
+            self.decoder.filter_incremental_state(state, keep)
+            ctx_i = {}
+            for n in names:
+                ctx_i[n] = contexts[n][:, alive]
+                ctx_i[n + '_mask'] = contexts[n + '_mask'][alive]
+            dec_out = self.decoder({self.index: cur[:, -1:]}, ctx_i, incremental_state=state)
+            h = dec_out[0][:, -1:]                                                   # [Ba, 1, E]
+            gen_tok, lp = self.decoder.adaptive_softmax.greedy(h)
+            x = h.transpose(0, 1).contiguous()                                       # [1, Ba, E]
+            k, v = ea.project_kv(x)
+            if k_hist is not None:
+                k_hist, v_hist = k_hist[:, keep], v_hist[:, keep]
+                k_hist, v_hist = torch.cat([k_hist, k], 0), torch.cat([v_hist, v], 0)
+            else:
+                k_hist, v_hist = k, v
+            x_entity = ea.step(x, k_hist, v_hist)
+            fc = self.entity_fc
+            ent = ops.entity_logits(x_entity, fc.weight_g, fc.weight_v, fc.bias)
+            rows = alive.nonzero().squeeze(1).to(torch.int32)
+            tok, copied, prob = ops.copy_step(self._copy_q(x[0]).contiguous(), k_article, self.bias_k, art_mask, proper,
+                                              ctx_ids, rows, ent, gen_tok.reshape(-1).long(), hist, i + 1,
+                                              self.copy_heads)
+            full_lp = lp.new_zeros(B, 1)
+            full_lp[alive] = lp.reshape(-1, 1).float() / self.sampling_temp        # :636-637 topk_lprobs / T
+            full_ix = tok.new_full((B, 1), self.padding_idx)
+            full_ix[alive] = tok.unsqueeze(1)
+            full_cp = copied.new_zeros(B, 1)
+            full_cp[alive] = copied.unsqueeze(1)
+            full_pr = prob.new_zeros(B, 1)
+            full_pr[alive] = prob.unsqueeze(1)
+            log_probs.append(full_lp)
+            paths.append(full_ix)
+            copies.append(full_cp)
+            probs.append(full_pr)
+            keep = tok != eos
+            alive = alive.clone()
+            alive[alive.nonzero().squeeze(1)[~keep]] = False
+            cur = torch.cat([cur, tok.unsqueeze(1)], dim=1)[keep]
+            if int(keep.sum()) == 0:
+                break
+        return torch.cat(paths, -1), torch.cat(log_probs, -1), torch.cat(copies, -1), torch.cat(probs, -1)
+
+    def get_metrics(self, reset=False):
+        metrics = super().get_metrics(reset=False)
+        for key, value in self.batch_history.items():
+            metrics[key] = float(value) / max(self.n_batches, 1)
+        if reset:
+            super().get_metrics(reset=True)
+            self.batch_history = defaultdict(float)
+        return metrics
+
+
+@Model.register('transformer_pointer')
+class TransformerPointerModel(PointerModelBase):
+    """tell/models/transformer_pointer.py: copy_loss = sum_i mean over rows of entity index i of -log p_target."""
+    COPY_VARIANT = 1
+
+
+@Model.register('transformer_pointer_2')
+class TransformerPointer2Model(PointerModelBase):
+    """tell/models/transformer_pointer_2.py: each term is CrossEntropy over the batch's reduced vocabulary."""
+    COPY_VARIANT = 2

@@ -1803,3 +1803,227 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
 
 
 LN2 = math.log(2.0)
+
+
+# --------------------------------------------------------------------------- #
+# copy mechanism of transformer_pointer / transformer_pointer_2 (csrc/copy.hip)
+# --------------------------------------------------------------------------- #
+def _check_rows(what, shape, **tensors):
+    """The copy kernels index the per-position tensors as [B, S] (or [B, T]) with the sizes of the attention: a tensor of
+    another width (e.g. a mask that was not padded with its ids) would be read out of bounds."""
+    for name, t in tensors.items():
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError('%s: %s has shape %s, expected %s' % (what, name, tuple(t.shape), tuple(shape)))
+
+
+class CopyAttnFn(Function):
+    """Head-mean copy attention weights [B,T,S] fp32 (multi_head.py:14-204 with the two virtual columns dropped and
+    proper_mask < 1 zeroed).  q: [T,B,E] already scaled; k: [S,B,E] view; mask [B,S] uint8 (1 = padding);
+    proper [B,S] int8 or None."""
+
+    @staticmethod
+    def forward(ctx, q, k, bias_k, mask, proper, H, p, salt):
+        T, B, E = q.shape
+        S = k.shape[0]
+        _check_rows('copy_attention', (B, S), mask=mask, proper=proper)
+        assert k.shape[1:] == (B, E), ('copy_attention: k', tuple(k.shape), (S, B, E))
+        if q.stride(2) != 1:
+            q = q.contiguous()
+        if k.stride(2) != 1:
+            k = k.contiguous()
+        w = torch.empty(B, T, S, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        bk = _bias_row(bias_k, q.dtype)
+        call('tell_copy_attn_fwd', q, k, bk, mask, proper, w, lse, B, H, T, S, E // H, q.stride(0), q.stride(1),
+             k.stride(0), k.stride(1), float(p), rt.seed(), salt, hip.dt(q))
+        ctx.save_for_backward(q, k, bk, mask, proper, lse)
+        ctx.meta = (bias_k, H, p, salt)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        q, k, bk, mask, proper, lse = ctx.saved_tensors
+        bias_k, H, p, salt = ctx.meta
+        T, B, E = q.shape
+        S = k.shape[0]
+        dq = torch.empty_like(q)
+        if dq.stride() != q.stride():         # the kernel writes dq with q's strides: only a dense q keeps them
+            q = q.contiguous()
+            dq = torch.empty_like(q)
+        kc = k
+        dk = torch.empty_like(kc)
+        if dk.stride() != kc.stride():
+            kc = k.contiguous()
+            dk = torch.empty_like(kc)
+        want_bk = bias_k is not None and bias_k.requires_grad
+        dbk = torch.empty(B * T, E, dtype=torch.float32, device=q.device) if want_bk else None
+        delta = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        call('tell_copy_attn_bwd', q, kc, bk, mask, proper, lse, dw.contiguous(), dq, dk, dbk, delta, B, H, T, S,
+             E // H, q.stride(0), q.stride(1), kc.stride(0), kc.stride(1), float(p), rt.seed(), salt, hip.dt(q))
+        if want_bk:
+            colsum_into(dbk, grad_buffer(bias_k).view(-1))
+        return dq, (dk if S > 0 else None), None, None, None, None, None, None
+
+
+def copy_attention(q, k, bias_k, mask, proper, H, p=0.0, training=False):
+    p = p if training else 0.0
+    return CopyAttnFn.apply(q, k, bias_k, mask, proper, H, p, rt.next_salt() if p > 0 else 0)
+
+
+class CopyLossFn(Function):
+    """The copy loss of transformer_pointer (variant 1) / transformer_pointer_2 (variant 2), pointer_loss :253-313,
+    fused: w [B,T,S] fp32, ctx_ids [B,S], targets [B,T], copy_mask [B,T] (int64) -> scalar (not divided by ln 2)."""
+
+    @staticmethod
+    def forward(ctx, w, ctx_ids, targets, copy_mask, variant, vocab):
+        B, T, S = w.shape
+        dev = w.device
+        _check_rows('copy_loss', (B, S), ctx_ids=ctx_ids)
+        _check_rows('copy_loss', (B, T), targets=targets, copy_mask=copy_mask)
+        ctx_ids, targets, copy_mask = (t.contiguous() for t in (ctx_ids, targets, copy_mask))
+        vcount = None
+        if variant == 2:
+            bitmap = torch.empty((vocab + 31) // 32 + 1, dtype=torch.int32, device=dev)     # + the out-of-range flag
+            vcount = torch.empty(1, dtype=torch.int32, device=dev)
+            call('tell_copy_vocab_count', ctx_ids, ctx_ids.numel(), targets, B, T, targets.stride(0), int(vocab),
+                 bitmap, vcount)
+        rows = torch.empty(4, B, T, dtype=torch.float32, device=dev)        # term, p_target, z, scale
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call('tell_copy_loss_fwd', w, ctx_ids, targets, targets.stride(0), copy_mask, copy_mask.stride(0), vcount,
+             int(variant), B, T, S, rows[0], rows[1], rows[2], rows[3], loss)
+        ctx.save_for_backward(w, ctx_ids, targets, copy_mask, rows)
+        ctx.variant = variant
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        w, ctx_ids, targets, copy_mask, rows = ctx.saved_tensors
+        B, T, S = w.shape
+        dw = torch.empty_like(w)
+        call('tell_copy_loss_bwd', dloss.float().contiguous(), w, ctx_ids, targets, targets.stride(0), copy_mask,
+             copy_mask.stride(0), rows[1], rows[2], rows[3], int(ctx.variant), B, T, S, dw)
+        return dw, None, None, None, None, None
+
+
+def copy_loss(w, ctx_ids, targets, copy_mask, variant, vocab):
+    return CopyLossFn.apply(w, ctx_ids, targets, copy_mask, int(variant), int(vocab))
+
+
+def _wn_weight_f32(g, v):
+    R, C = v.shape
+    norms = torch.empty(R, dtype=torch.float32, device=v.device)
+    w = torch.empty(R, C, dtype=torch.float32, device=v.device)
+    call('tell_wn_weight', g.detach(), v.detach(), R, C, w, hip.F32, norms)
+    return w, norms
+
+
+class EntityHeadFn(Function):
+    """entity_fc (a 2-output GehringLinear) + CrossEntropyLoss(ignore_index=-1) against min(copy_mask, 1)
+    (transformer_pointer.py:211-228).  x: [T,B,E]; copy_mask [B,T] int64 -> (scalar loss, logits [B,T,2] fp32)."""
+
+    @staticmethod
+    def forward(ctx, x, g, v, b, copy_mask):
+        T, B, E = x.shape
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        copy_mask = copy_mask.contiguous()
+        w, norms = _wn_weight_f32(g, v)
+        logits = torch.empty(B, T, 2, dtype=torch.float32, device=x.device)
+        stats = torch.empty(2, dtype=torch.float32, device=x.device)        # loss, number of valid rows
+        call('tell_entity_head_fwd', x, x.stride(0), x.stride(1), w, b.detach().float().contiguous(), copy_mask,
+             copy_mask.stride(0), B, T, E, logits, stats[0:], stats[1:], hip.dt(x))
+        ctx.save_for_backward(x, w, norms, logits, stats, copy_mask)
+        ctx.params = (g, v, b)
+        ctx.mark_non_differentiable(logits)
+        return stats[0], logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        x, w, norms, logits, stats, copy_mask = ctx.saved_tensors
+        g, v, b = ctx.params
+        T, B, E = x.shape
+        dx = torch.empty_like(x)
+        dlogits = torch.empty(B, T, 2, dtype=torch.float32, device=x.device)
+        dW = torch.empty(2, E, dtype=torch.float32, device=x.device)
+        db = grad_buffer(b) if b.requires_grad else None
+        call('tell_entity_head_bwd', dloss.float().contiguous(), stats[1:], logits, copy_mask, copy_mask.stride(0),
+             x, x.stride(0), x.stride(1), w, dx, dx.stride(0), dx.stride(1), dlogits, dW, db, B, T, E, hip.dt(x))
+        if v.requires_grad:
+            _wn_backward([(dW, g, v, norms)])
+        return dx, None, None, None, None
+
+
+def entity_head(x, g, v, b, copy_mask):
+    return EntityHeadFn.apply(x, g, v, b, copy_mask)
+
+
+class CausalAttnFn(Function):
+    """softmax over keys s < t plus a zero slot (logit 0, value 0), then PV: the entity self-attention of
+    transformer_pointer (self_attention.py with _mask_future_full and scalar_bias).  q, k, v: [T,B,E]; logits scale * q.k."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, H, scale):
+        T, B, E = q.shape
+        q, k, v = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k, v))
+        out = torch.empty(T, B, E, dtype=q.dtype, device=q.device)
+        lse = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        call('tell_causal_attn_fwd', q, k, v, out, lse, B, H, T, T, E // H, 0, q.stride(0), q.stride(1),
+             k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(scale), hip.dt(q))
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.H, ctx.scale = H, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        H = ctx.H
+        T, B, E = q.shape
+        dout = dout.contiguous()
+        q, k, v = (t.contiguous() for t in (q, k, v))
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        delta = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+        call('tell_causal_attn_bwd', q, k, v, out, dout, lse, dq, dk, dv, delta, B, H, T, E // H, q.stride(0),
+             q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(ctx.scale),
+             hip.dt(q))
+        return dq, dk, dv, None, None
+
+
+def causal_attention(q, k, v, H, scale):
+    return CausalAttnFn.apply(q, k, v, H, scale)
+
+
+def causal_attention_step(q, k, v, H, scale):
+    """The last row of causal_attention over a K/V history: q [1,B,E] at position S - 1, k, v [S,B,E]; no autograd."""
+    _, B, E = q.shape
+    S = k.shape[0]
+    out = torch.empty(1, B, E, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, 1, dtype=torch.float32, device=q.device)
+    call('tell_causal_attn_fwd', q, k, v, out, lse, B, H, 1, S, E // H, S - 1, q.stride(0), q.stride(1),
+         k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(scale), hip.dt(q))
+    return out
+
+
+def copy_step(q, k, bias_k, mask, proper, ctx_ids, rows, entity_logits, gen_tok, hist, n_hist, H):
+    """One generation step's copy decision (include/tell_hip.h tell_copy_step) -> (tok [Ba] int64, copied [Ba] bool,
+    prob [Ba] fp32); hist[:, n_hist] is written."""
+    Ba, E = q.shape
+    S, B = k.shape[0], k.shape[1]
+    _check_rows('copy_step', (B, S), mask=mask, proper=proper, ctx_ids=ctx_ids)
+    assert hist.shape[0] == B and rows.shape == (Ba,) and entity_logits.shape == (Ba, 2), 'copy_step: shapes'
+    tok = torch.empty(Ba, dtype=torch.int64, device=q.device)
+    copied = torch.empty(Ba, dtype=torch.uint8, device=q.device)
+    prob = torch.empty(Ba, dtype=torch.float32, device=q.device)
+    call('tell_copy_step', q, q.stride(0), k, k.stride(0), k.stride(1), _bias_row(bias_k, q.dtype), mask, proper,
+         ctx_ids, rows, entity_logits.contiguous(), gen_tok.contiguous(), hist, hist.shape[1], int(n_hist), Ba, H, S,
+         E // H, tok, copied, prob, hip.dt(q))
+    return tok, copied.bool(), prob
+
+
+def entity_logits(x, g, v, b):
+    """entity_fc of the generation step: x [1,Ba,E] -> logits [Ba,2] fp32 (tell_entity_logits)."""
+    _, Ba, E = x.shape
+    w, _ = _wn_weight_f32(g, v)
+    logits = torch.empty(Ba, 2, dtype=torch.float32, device=x.device)
+    call('tell_entity_logits', x, x.stride(0), x.stride(1), w, b.detach().float().contiguous(), Ba, 1, E, logits,
+         hip.dt(x))
+    return logits

@@ -64,6 +64,8 @@ class StepGraph:
         idx = model.index
         if not (ENABLED and graphs.ENABLED) or not hasattr(model, 'encode') or not model.training:
             return None
+        if not getattr(model, 'STEP_GRAPH', True):        # a model whose loss may be None (models/pointer.py)
+            return None
         if tr.async_update:                                # the opt-in update stream belongs to the eager schedule
             return None
         cap = batch['caption'][idx]

@@ -197,6 +197,8 @@ class Trainer:
         from .. import graphs
         if self.shape_buckets is None or not (_sg.ENABLED and graphs.ENABLED) or self.nan_check:
             return batch
+        if not getattr(self.model, 'SHAPE_BUCKETS', True):     # a model whose loss sees the padding (models/pointer.py)
+            return batch
         idx = getattr(self.model, 'index', 'roberta')
         pad = int(getattr(self.model, 'padding_idx', 1))
         out = None
@@ -216,9 +218,10 @@ class Trainer:
                 out = dict(batch) if out is None else out
                 f = dict(field)
                 f[idx] = grow(ids, 1, n, pad)
-                m = f.get(idx + '_copy_masks')
-                if torch.is_tensor(m) and m.dim() == 2 and m.shape[1] == ids.shape[1]:
-                    f[idx + '_copy_masks'] = grow(m, 1, n, -1)
+                for mk in (idx + '_copy_masks', idx + '_proper_masks'):      # masks are padded with -1
+                    m = f.get(mk)
+                    if torch.is_tensor(m) and m.dim() == 2 and m.shape[1] == ids.shape[1]:
+                        f[mk] = grow(m, 1, n, -1)
                 out[key] = f
         for key, rows in (('face_embeds', 4), ('obj_embeds', 64)):
             t = batch.get(key)
@@ -340,6 +343,8 @@ class Trainer:
         extra = {'encoded': enc} if enc is not None else {}
         out = self.model(**batch, **extra)                               # :220 / :194
         loss = out['loss']
+        if loss is None:             # the pointer models' batches without a copy target: no backward, no update
+            return None
         self._flag_loss(loss)
         n_local = None
         if self.dp and self._ranges:
