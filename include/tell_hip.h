@@ -515,6 +515,32 @@ int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_
 int tell_sample_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp,
                            const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,
                            float* lps, tell_stream_t stream);
+/* nucleus (top-p) sampling with a temperature over the full adaptive softmax.  Per row, with the
+ * log-probs lp_t of tell_adaptive_logprob_argmax, inv_temp = 1 / T, 0 < p <= 1 and k = 0 (no top-k cut) or 2..64:
+ *   1. weights w_t = exp((lp_t - lp_max) * inv_temp); with k > 0 only the k best tokens (value descending, lower id first on
+ *      ties: the candidates of tell_adaptive_logprob_sample) keep a weight;
+ *   2. the nucleus: the shortest prefix of that order whose weight sum reaches p * (total weight); tokens that tie at the
+ *      boundary enter in id order until the sum is reached; the best token is always a member;
+ *   3. the draw: u(seed, row, step) as above, scaled by the nucleus' weight sum; the pick is the first member IN TOKEN-ID
+ *      ORDER whose running weight sum exceeds it (the last member if rounding leaves none).  Id order, not value order, so
+ *      that the nucleus - thousands of tokens for a flat distribution - is never sorted.  Consequence: a (k, p = 1) call and
+ *      tell_adaptive_logprob_sample(k) draw from the same distribution but map the same u to different ids;
+ *   4. out: tokens[r] and lps[r] = lp of the pick WITHOUT the temperature (tell_greedy_update multiplies by inv_temp).
+ * p = 1, k = 0 is multinomial sampling from the tempered softmax; p -> 0 is the arg-max (bit for bit).  Weight sums that
+ * decide the boundary are exact 64-bit fixed-point sums of the fp32 weights (2^-44 of the largest weight is the unit: a
+ * token lighter than that counts as zero), so a row's nucleus does not depend on the batch or on the launch mode.
+ * nuc_size / nuc_key (optional, NULL in the product path): per row the number of members and the order-preserving key
+ * (u = bits of lp; lp < 0: ~u, else u | 2^31) of the smallest member log-prob.  row_ids, step, step_dev, seed_dev and the
+ * register / streaming forms as for tell_adaptive_logprob_sample; vocab < 2^19. */
+int tell_adaptive_logprob_nucleus(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                  int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                  int rows, int k, float inv_temp, float p, const uint32_t* seed_dev, const int* row_ids,
+                                  int step, const int* step_dev, int* tokens, float* lps, int* nuc_size,
+                                  uint32_t* nuc_key, tell_stream_t stream);
+/* steps 2-4 above on given candidates (cand_tokens int32 / cand_lps fp32 [rows, k], each row sorted best first, k 1..64) */
+int tell_nucleus_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp, float p,
+                            const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,
+                            float* lps, tell_stream_t stream);
 
 /* per-token bookkeeping of the greedy decode loop (transformer_faces_objects.py:443-494) for all B rows in one launch:
    unfinished rows record tok / lp * inv_temp at step i, rows emitting eos are marked finished (done_step = i + 1),

@@ -5,7 +5,10 @@
      N = 32 / 128 rows;
   2. the full-size faces_objects decode loop (bf16, captured steps), greedy vs sampling_topk = 50, B = 32: microseconds per
      decode step (HIP events around `_generate`, divided by the steps taken; random weights decode all 100 steps).
-usage (GPU box): python tools/bench_sampling.py [--skip-model]"""
+  3. --topp P: nucleus sampling (tell_adaptive_logprob_nucleus, k = 0) - its launch beside the legs of 1., on the rows of 1.
+     (flat: nuclei of thousands of tokens) and on rows scaled x4 (peaked); and the decode step at 32 and 128 captions with
+     sampling_topk = 0, sampling_topp = P against sampling_topk = 64, legs interleaved, medians.
+usage (GPU box): python tools/bench_sampling.py [--skip-model] [--topp P]"""
 import sys
 
 import torch
@@ -38,7 +41,7 @@ def timeit(fn, n=400):
     return 1e3 * e0.elapsed_time(e1) / (n // 20 * 20)
 
 
-def head_launches():
+def head_launches(topp=None):
     c0, tails = 5000, (15000, 30265)
     for N in (32, 128):
         g = torch.Generator().manual_seed(N)
@@ -55,6 +58,18 @@ def head_launches():
         for k in (1, 8, 50, 64):
             t = timeit(lambda: call('tell_adaptive_logprob_sample', *args, N, k, 1.0 / 0.8, seed, None, 0, cnt, tok, lp))
             print('head last launch  N=%3d  sample k=%-2d          %7.2f us   (%.2fx the arg-max)' % (N, k, t, t / t_arg))
+        if topp is not None:
+            t64 = t
+            for name, mul in (('flat rows', 1.0), ('rows x4  ', 4.0)):
+                sc = [a.mul(mul) if torch.is_tensor(a) else a for a in args]
+                sc = [sc[0], sc[0].stride(0)] + sc[2:]
+                nuc = lambda: call('tell_adaptive_logprob_nucleus', *sc, N, 0, 1.0 / 0.8, topp, seed, None, 0, cnt,  # noqa: E731
+                                   tok, lp, None, None)
+                t = timeit(nuc)
+                size = torch.empty(N, dtype=torch.int32, device=dev)
+                call('tell_adaptive_logprob_nucleus', *sc, N, 0, 1.0 / 0.8, topp, seed, None, 0, cnt, tok, lp, size, None)
+                print('head last launch  N=%3d  nucleus p=%.2f %s %7.2f us   (%.2fx sample k=64; median nucleus %d tokens)'
+                      % (N, topp, name, t, t / t64, int(size.median())))
         sys.stdout.flush()
 
 
@@ -88,7 +103,44 @@ def decode_steps(B=32):
     print('decode step  sampling / greedy: %.3f' % (res['sampling_topk=50'] / res['greedy']))
 
 
+def decode_steps_topp(topp, sizes=(32, 128), loops=7):
+    """Decode step with sampling_topk = 0, sampling_topp = topp against sampling_topk = 64: the legs alternate loop by loop
+    on the same model and batch, warm (captures recorded first), medians."""
+    from tell_amd.build import build_model
+    from tell_amd.data import synthetic_batch
+    tell_amd.set_compute_dtype(torch.bfloat16)
+    torch.manual_seed(0)
+    model = build_model('faces_objects').to(dev).eval()
+    legs = (('sampling_topk=64', 64, None), ('topk=0 topp=%.2f' % topp, 0, topp))
+    for B in sizes:
+        batch = synthetic_batch(B, 512, 33, True, seed=3, device=dev)
+        with torch.no_grad():
+            caption_ids, _, contexts = model._forward(batch['context'], batch['image'], batch['caption'],
+                                                      batch['face_embeds'], batch['obj_embeds'])
+        per = {name: [] for name, _, _ in legs}
+        for it in range(2 + loops):
+            for name, k, p in legs:
+                model.sampling_topk, model.sampling_temp, model.sampling_topp = k, 1.0, p
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _, ids, _ = model._generate(caption_ids, contexts)
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= 2:                                                    # (the first two loops record the graphs)
+                    per[name].append(1e3 * e0.elapsed_time(e1) / (ids.shape[1] - 1))
+        med = {name: sorted(v)[len(v) // 2] for name, v in per.items()}
+        for name, _, _ in legs:
+            print('decode step  B=%3d  %-18s %7.1f us per step (median of %d loops; min %.1f max %.1f)'
+                  % (B, name, med[name], loops, min(per[name]), max(per[name])))
+        print('decode step  B=%3d  nucleus / top-k 64: %.3f' % (B, med[legs[1][0]] / med[legs[0][0]]))
+        sys.stdout.flush()
+
+
 if __name__ == '__main__':
-    head_launches()
+    topp = float(sys.argv[sys.argv.index('--topp') + 1]) if '--topp' in sys.argv else None
+    head_launches(topp)
     if '--skip-model' not in sys.argv:
-        decode_steps()
+        if topp is None:
+            decode_steps()
+        else:
+            decode_steps_topp(topp)

@@ -694,6 +694,7 @@ struct SampleArgs {
   int k; float inv_temp;
   const uint32_t* seed_dev; const int* row_ids; int step; const int* step_dev;
   int* tokens; float* lps;
+  float topp; int* nuc_size; uint32_t* nuc_key;       // the nucleus entry point only (tell_adaptive_logprob_nucleus)
 };
 struct SampleSmem {
   int hist[256];
@@ -708,6 +709,60 @@ __device__ __forceinline__ uint32_t lp_key(float v) {          // order-preservi
 }
 __device__ __forceinline__ float key_lp(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// ---- nucleus (top-p) over k candidates sorted best first (tell_adaptive_logprob_nucleus with k > 0, tell_nucleus_candidates)
+// steps 1-2: w_j = exp((lp_j - lp_0) * inv_temp) summed in candidate order; -> n, the shortest prefix with c_n >= p * total
+__device__ __forceinline__ int nucleus_prefix(const float* lp, int k, float inv_temp, float p) {
+  const float l0 = lp[0];
+  float tot = 0.f;
+  for (int j = 0; j < k; ++j) tot += expf((lp[j] - l0) * inv_temp);
+  const float target = p * tot;
+  float c = 0.f;
+  for (int j = 0; j < k; ++j) {
+    c += expf((lp[j] - l0) * inv_temp);
+    if (c >= target) return j + 1;
+  }
+  return k;
+}
+// step 3: order[0..n) lists the members by ascending token id; the first whose running weight exceeds u * sum (the last if none)
+__device__ __forceinline__ int nucleus_draw(const float* lp, const int* order, int n, float inv_temp, float u) {
+  const float l0 = lp[0];
+  float sum = 0.f;
+  for (int r = 0; r < n; ++r) sum += expf((lp[order[r]] - l0) * inv_temp);
+  const float t = u * sum;
+  float c = 0.f;
+  for (int r = 0; r < n; ++r) {
+    c += expf((lp[order[r]] - l0) * inv_temp);
+    if (t < c) return order[r];
+  }
+  return order[n - 1];
+}
+__device__ __forceinline__ float sample_args_u(const SampleArgs& a, int row) {
+  const uint32_t r = a.row_ids ? (uint32_t)a.row_ids[row] : (uint32_t)row;
+  const uint32_t step = a.step_dev ? (uint32_t)(*a.step_dev + 1) : (uint32_t)a.step;     // (captured: the counter holds i - 1)
+  return tell_sample_u(*a.seed_dev, r, step);
+}
+// the workgroup's form over candidates ranked in LDS: thread 0 cuts the prefix, n threads rank the members by id, thread 0 draws
+__device__ __forceinline__ void nucleus_candidates_block(const float* sort_v, const int* sort_i, int* order, int* n_s, int row,
+                                                         const SampleArgs& a) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *n_s = nucleus_prefix(sort_v, a.k, a.inv_temp, a.topp);
+  __syncthreads();
+  const int n = *n_s;
+  if (tid < n) {
+    const int mi = sort_i[tid];
+    int r = 0;
+    for (int j = 0; j < n; ++j) r += sort_i[j] < mi ? 1 : 0;
+    order[r] = tid;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int j = nucleus_draw(sort_v, order, n, a.inv_temp, sample_args_u(a, row));
+    a.tokens[row] = sort_i[j];
+    a.lps[row] = sort_v[j];
+    if (a.nuc_size) a.nuc_size[row] = n;
+    if (a.nuc_key) a.nuc_key[row] = lp_key(sort_v[n - 1]);
+  }
 }
 // one radix pass's decision (hist complete after the first barrier): the digit whose bin holds the need-th largest of the
 // counted values, how many lie in the bins above it and how many in the bin itself.  Wave 0 decides, everyone reads.
@@ -760,7 +815,7 @@ __device__ __forceinline__ uint32_t sample_radix_select(const Each& each, const 
 }
 // each_ties: the same elements with the same keys, for the tie pass (3) only - the register form hands in a walk over memory
 // there, because ids kept live through the pass loop spill half of its registers
-template <class Each, class EachTies>
+template <bool NUC, class Each, class EachTies>
 __device__ __forceinline__ void sample_row(const Each& each, const EachTies& each_ties, uint32_t thread_max, int row,
                                            const SampleArgs& a, SampleSmem& sm) {
   const int tid = threadIdx.x, k = a.k;
@@ -810,6 +865,10 @@ __device__ __forceinline__ void sample_row(const Each& each, const EachTies& eac
     sm.sort_i[rank] = mi;
   }
   __syncthreads();
+  if (NUC) {                                                  // top-k cut, then the nucleus over the k candidates (below)
+    nucleus_candidates_block(sm.sort_v, sm.sort_i, sm.cand_idx, &sm.n_cand, row, a);
+    return;
+  }
   if (tid == 0) {
     const uint32_t r = a.row_ids ? (uint32_t)a.row_ids[row] : (uint32_t)row;
     const uint32_t step = a.step_dev ? (uint32_t)(*a.step_dev + 1) : (uint32_t)a.step;   // (captured: the counter holds i - 1)
@@ -822,6 +881,7 @@ __device__ __forceinline__ void sample_row(const Each& each, const EachTies& eac
 // The register-resident form: loads, maxima, sums and log-probs exactly as logprob_regs_kernel (so k = 1 is its arg-max bit
 // for bit), then the log-probs become keys in place and every pass of the select runs over registers.  Same capacity and
 // alignment rules.
+template <bool NUC>
 __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p, SampleArgs a) {
   __shared__ float red[4][16];
   __shared__ SampleSmem sm;
@@ -933,10 +993,11 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
     for (int s = 1; s < nseg; ++s)
       for (int j = tid; j < n[s]; j += 1024) f(lp_key(rowp[s][j] + off[s]), base[s] + j);
   };
-  sample_row(each, each_mem, tmax, i, a, sm);
+  sample_row<NUC>(each, each_mem, tmax, i, a, sm);
 }
 // Any row: the log-probs with the arithmetic of logprob_argmax_kernel (the three-pass form; its full-row output is what the
 // tests take top-k of), read from memory in every pass of the select.
+template <bool NUC>
 __global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs p, SampleArgs a) {
   __shared__ float red[16];
   __shared__ SampleSmem sm;
@@ -976,7 +1037,7 @@ __global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs
   };
   uint32_t tmax = 0;
   each([&](uint32_t key, int) { tmax = max(tmax, key); });
-  sample_row(each, each, tmax, i, a, sm);
+  sample_row<NUC>(each, each, tmax, i, a, sm);
 }
 extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
@@ -997,7 +1058,7 @@ extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int
   p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
   SampleArgs a;
   a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps;
+  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr;
   const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
                        (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
                        (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
@@ -1005,10 +1066,10 @@ extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int
   const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
   if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
       (n_tails < 3 || n2 <= 2 * 4096)) {
-    hipLaunchKernelGGL(logprob_sample_regs_kernel, dim3(rows), dim3(1024), 0, stream, p, a);
+    hipLaunchKernelGGL(logprob_sample_regs_kernel<false>, dim3(rows), dim3(1024), 0, stream, p, a);
     return tell_check_launch("logprob_sample (registers)");
   }
-  hipLaunchKernelGGL(logprob_sample_stream_kernel, dim3(rows), dim3(1024), 0, stream, p, a);
+  hipLaunchKernelGGL(logprob_sample_stream_kernel<false>, dim3(rows), dim3(1024), 0, stream, p, a);
   return tell_check_launch("logprob_sample");
 }
 
@@ -1033,9 +1094,487 @@ extern "C" int tell_sample_candidates(const int* cand_tokens, const float* cand_
   if (rows <= 0) return TELL_OK;
   SampleArgs a;
   a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps;
+  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr;
   hipLaunchKernelGGL(sample_candidates_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, cand_tokens, cand_lps, rows, a);
   return tell_check_launch("sample_candidates");
+}
+
+// ------------------------------------------------------------------ nucleus (top-p) sampling with a temperature
+// include/tell_hip.h tell_adaptive_logprob_nucleus, DESIGN.md section 14.  Per row, with the log-probs and keys of the top-k
+// sampler above: weights w = exp((lp - lp_max) * inv_temp); the nucleus is the shortest prefix, by (value descending, id
+// ascending), whose weight reaches p * total; the pick is the first member IN TOKEN-ID ORDER whose running weight exceeds
+// u * (nucleus weight).  No sort: the boundary is the key tau with mass(key > tau) < p * total <= mass(key >= tau), found by
+// a threshold search over weight-mass histograms -
+//  1. one pass over a coarse, well spread digit (quarter nats below the maximum after the temperature, nuc_coarse: monotone
+//     in the key).  The raw key's top byte would put the whole vocabulary into two or three exponent bins, i.e. 50 000 LDS
+//     atomics on three addresses;
+//  2. the crossing coarse bin is a key range klo .. khi (one pass of min / max); then passes of 8 key bits over the elements
+//     of that range (typically a few hundred), skipping every byte that klo and khi share;
+//  3. one pass in id order: `m`, the number of keys equal to tau that the prefix takes, go to the lowest ids (block-wide
+//     prefix count, only when not all of them enter), and the running weight is a block-wide fp32 prefix sum in a fixed
+//     order (thread, wave, workgroup, chunk), from which every thread tests its own elements.
+// The histogram masses are 64-bit FIXED-POINT sums (weight * 2^44, truncated) added with integer LDS atomics: integer
+// addition is associative, so a bin's mass does not depend on the order in which lanes arrive - no atomics on floats, and
+// the same row gives the same tau in any batch, eager or captured.  A weight below 2^-44 of the maximum counts as zero
+// (5.7e-14: below what fp32 sums of the other weights resolve); 2^19 tokens of weight 1 still fit 63 bits.
+// Every pass walks the row through `each` (registers or memory); `sweep` hands out the id-ordered chunks of pass 3.
+#define NUC_FX 17592186044416.f                                 // 2^44
+struct NucleusSmem {
+  unsigned long long hist[256];
+  unsigned long long need, above, bucket;                       // a pass's decision: target left, mass above the bin, the bin's mass
+  float wtot[2][16];
+  int ttot[2][16];
+  int sel;
+  uint32_t klo, khi;                                            // the keys of the crossing coarse bin span klo .. khi
+  float ref_max;                                                // the row's maximum log-prob, re-read in every pass (see nucleus_row)
+  int best, last, cnt;
+};
+__device__ __forceinline__ float nuc_weight(uint32_t key, float lmax, float inv_temp) {
+  return __expf((key_lp(key) - lmax) * inv_temp);
+}
+__device__ __forceinline__ unsigned long long nuc_fx(float w) { return (unsigned long long)(w * NUC_FX); }
+// 255 - quarter nats below the maximum (after the temperature), clamped: larger key -> larger or equal digit
+__device__ __forceinline__ int nuc_coarse(uint32_t key, float lmax, float inv_temp) {
+  return 255 - (int)fminf((lmax - key_lp(key)) * inv_temp * 4.f, 255.f);
+}
+// hist complete after the first barrier; bins taken from 255 down: the bin in which the running mass reaches the target.
+// topp > 0 (the first pass): the target is set here, ceil(topp * total mass), at least 1.  Wave 0 decides, everyone reads.
+__device__ __forceinline__ void nucleus_decide(NucleusSmem& sm, float topp) {
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const unsigned long long h[4] = {sm.hist[4 * lane], sm.hist[4 * lane + 1], sm.hist[4 * lane + 2], sm.hist[4 * lane + 3]};
+    const unsigned long long tot = h[0] + h[1] + h[2] + h[3];
+    unsigned long long suf = tot;                              // sum over lanes >= lane (higher digits)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long v = __shfl_down(suf, o, 64);
+      if (lane + o < 64) suf += v;
+    }
+    unsigned long long need = sm.need;
+    if (topp > 0.f) {
+      const unsigned long long all = __shfl(suf, 0, 64);
+      need = (unsigned long long)ceil((double)topp * (double)all);
+      need = need < 1 ? 1 : (need > all ? all : need);
+    }
+    unsigned long long cum = suf - tot;
+#pragma unroll
+    for (int b = 3; b >= 0; --b) {
+      if (cum < need && cum + h[b] >= need) { sm.sel = 4 * lane + b; sm.above = cum; sm.bucket = h[b]; sm.need = need - cum; }
+      cum += h[b];
+    }
+  }
+  __syncthreads();
+}
+template <class Each, class Sweep>
+__device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep, uint32_t thread_max, int row,
+                                            const SampleArgs& a, NucleusSmem& sm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float inv_temp = a.inv_temp;
+  // the maximum key
+  uint32_t kmax = thread_max;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
+  if (lane == 0) sm.ttot[0][wave] = (int)kmax;
+  if (tid < 256) sm.hist[tid] = 0;
+  if (tid == 0) { sm.best = 0x7fffffff; sm.last = -1; sm.cnt = 0; sm.klo = 0xFFFFFFFFu; sm.khi = 0u; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) kmax = max(kmax, (uint32_t)sm.ttot[0][w]);
+  // 1. the coarse digit over the whole row
+  {
+    const float lmax = key_lp(kmax);
+    if (tid == 0) sm.ref_max = lmax;
+    each([&](uint32_t key, int) {
+      const unsigned long long fx = key ? nuc_fx(nuc_weight(key, lmax, inv_temp)) : 0ull;
+      if (fx) atomicAdd(&sm.hist[nuc_coarse(key, lmax, inv_temp)], fx);          // (a peaked row: most of the vocabulary is 0)
+    });
+  }
+  nucleus_decide(sm, a.topp);
+  unsigned long long above = sm.above;
+  // the crossing coarse bin is a key range (the digit is monotone in the key): klo .. khi, the bin's smallest and largest key
+  {
+    const int g = sm.sel;
+    const float lmax = sm.ref_max;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    each([&](uint32_t key, int) {
+      if (key && nuc_coarse(key, lmax, inv_temp) == g) { lo = min(lo, key); hi = max(hi, key); }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
+      hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
+    }
+    if (lane == 0) { atomicMin(&sm.klo, lo); atomicMax(&sm.khi, hi); }
+    __syncthreads();
+  }
+  // 2. the key's bytes inside that range.  A byte that klo and khi share (with all bytes above it) is the same in every
+  //    participant: its pass is skipped - typically the top byte (a quarter nat rarely spans two exponents), often
+  //    the next.  klo / khi / ref_max are re-read from LDS in every pass: filters and weights computed from register values
+  //    are loop-invariant, and the compiler would keep 64 of each per thread of the register form live across the passes
+  //    (293 VGPRs spilled).
+  uint32_t pre = 0, msk = 0;
+  for (int sh = 24; sh >= 0; sh -= 8) {
+    if (((sm.klo ^ sm.khi) >> sh) == 0) {                        // (uniform)
+      pre |= sm.klo & (0xFFu << sh);
+      msk |= 0xFFu << sh;
+      continue;
+    }
+    if (tid < 256) sm.hist[tid] = 0;
+    __syncthreads();
+    const uint32_t klo = sm.klo, khi = sm.khi;
+    const float lmax = sm.ref_max;
+    each([&](uint32_t key, int) {
+      if (key >= klo && key <= khi && (key & msk) == pre) {
+        const unsigned long long fx = nuc_fx(nuc_weight(key, lmax, inv_temp));
+        if (fx) atomicAdd(&sm.hist[(key >> sh) & 255], fx);
+      }
+    });
+    nucleus_decide(sm, 0.f);
+    pre |= (uint32_t)sm.sel << sh;
+    msk |= 0xFFu << sh;
+    above += sm.above;
+  }
+  // tau = pre: `ties` keys equal it, the prefix takes the m lowest ids of them
+  const uint32_t tau = pre;
+  const float lmax = sm.ref_max;
+  const unsigned long long fx_tau = nuc_fx(nuc_weight(tau, lmax, inv_temp));     // (> 0: its bin reached a target >= 1)
+  const int ties = (int)(sm.bucket / fx_tau);
+  int m = (int)((sm.need + fx_tau - 1) / fx_tau);
+  m = m > ties ? ties : m;
+  const bool cut = m < ties;                                   // (uniform)
+  const float t = sample_args_u(a, row) * ((float)(above + (unsigned long long)m * fx_tau) * (1.f / NUC_FX));
+  // 3. id order
+  float carry = 0.f;
+  int tie_carry = 0, par = 0;
+  int best = 0x7fffffff, last = -1, cnt = 0;
+  uint32_t best_key = 0, last_key = 0;
+  sweep([&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, int id0) {
+    const uint32_t k[4] = {k0, k1, k2, k3};
+    bool mem[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) mem[e] = k[e] > tau || (!cut && k[e] == tau);
+    if (cut) {
+      int tc = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tc += k[e] == tau ? 1 : 0;
+      int incl = tc;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) sm.ttot[par][wave] = incl;
+      __syncthreads();
+      int rank = tie_carry + incl - tc;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) {
+        const int v = sm.ttot[par][w];
+        if (w < wave) rank += v;
+        tie_carry += v;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (k[e] == tau) { mem[e] = rank < m; ++rank; }
+    }
+    float s[4];
+    float run = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      run += mem[e] ? nuc_weight(k[e], lmax, inv_temp) : 0.f;
+      s[e] = run;
+    }
+    float incl = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    if (lane == 63) sm.wtot[par][wave] = incl;
+    __syncthreads();
+    float off = carry, c = carry;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      if (w == wave) off = c;
+      c += sm.wtot[par][w];
+    }
+    carry = c;
+    const float base = off + excl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (mem[e]) {
+        if (best == 0x7fffffff && base + s[e] > t) { best = id0 + e; best_key = k[e]; }
+        last = id0 + e; last_key = k[e];
+        ++cnt;
+      }
+    par ^= 1;
+  });
+  int wb = best, wl = last, wc = cnt;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    wb = min(wb, __shfl_xor(wb, o, 64));
+    wl = max(wl, __shfl_xor(wl, o, 64));
+    wc += __shfl_xor(wc, o, 64);
+  }
+  if (lane == 0) { atomicMin(&sm.best, wb); atomicMax(&sm.last, wl); atomicAdd(&sm.cnt, wc); }
+  __syncthreads();
+  const int pick = sm.best != 0x7fffffff ? sm.best : sm.last;   // (no running sum above t: rounding at the top end - the last member)
+  if (best == pick) { a.tokens[row] = pick; a.lps[row] = key_lp(best_key); }
+  else if (sm.best == 0x7fffffff && last == pick) { a.tokens[row] = pick; a.lps[row] = key_lp(last_key); }
+  if (tid == 0) {
+    if (a.nuc_size) a.nuc_size[row] = sm.cnt;
+    if (a.nuc_key) a.nuc_key[row] = tau;
+  }
+}
+// The register-resident form: loads, maxima, sums and log-probs exactly as logprob_regs_kernel / logprob_sample_regs_kernel
+// (a tiny p is the register arg-max bit for bit); every pass runs over registers, the logits cross HBM once.
+__global__ __launch_bounds__(1024) void logprob_nucleus_regs_kernel(LogProbArgs p, SampleArgs a) {
+  __shared__ float red[4][16];
+  __shared__ NucleusSmem sm;
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nseg = 1 + p.n_tails;
+  const float* rowp[4]; int n[4];
+  rowp[0] = p.head + (long)i * p.ld_head; n[0] = p.head_n;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    rowp[c + 1] = c < p.n_tails ? p.tail[c] + (long)i * p.ld_tail[c] : rowp[0];
+    n[c + 1] = c < p.n_tails ? p.tail_n[c] : 0;
+  }
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  f4 x[16];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const int j = (q * 1024 + tid) * 4;
+      f4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      if (j + 3 < n[s]) v = *reinterpret_cast<const f4*>(rowp[s] + j);
+      else if (j < n[s]) {
+        v.x = rowp[s][j];
+        if (j + 1 < n[s]) v.y = rowp[s][j + 1];
+        if (j + 2 < n[s]) v.z = rowp[s][j + 2];
+      }
+      x[LPF_OFF[s] + q] = v;
+    }
+  float mx[4], sm_[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const f4 v = x[LPF_OFF[s] + q];
+      m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+    m = wave_max(m);
+    if (lane == 0) red[s][wave] = m;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float m = red[s][0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) m = fmaxf(m, red[s][w]);
+    mx[s] = m;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float t = 0.f;
+    if (s < nseg) {
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q) {
+        const f4 v = x[LPF_OFF[s] + q];
+        t += (__expf(v.x - mx[s]) + __expf(v.y - mx[s])) + (__expf(v.z - mx[s]) + __expf(v.w - mx[s]));
+      }
+    }
+    t = wave_sum(t);
+    if (lane == 0) red[s][wave] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) t += red[s][w];
+    sm_[s] = t;
+  }
+  const float lse_h = mx[0] + __logf(sm_[0]);
+  float off[4];
+  int base[4];
+  off[0] = -lse_h; base[0] = 0;
+  base[1] = p.c0;
+#pragma unroll
+  for (int s = 1; s < 4; ++s) {
+    off[s] = s < nseg ? (rowp[0][p.c0 + s - 1] - lse_h) - (mx[s] + __logf(sm_[s])) : 0.f;
+    if (s < 3) base[s + 1] = base[s] + n[s];
+  }
+  const int lim[4] = {p.c0, n[1], n[2], n[3]};               // (segments past n_tails have n = 0)
+  uint32_t key[64];
+  uint32_t tmax = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int q = 0; q < LPF_CAP[s]; ++q) {
+      const int j = (q * 1024 + tid) * 4, e0 = (LPF_OFF[s] + q) * 4;
+      const f4 v = x[LPF_OFF[s] + q];
+      const float l0 = s == 0 ? v.x - lse_h : v.x + off[s], l1 = s == 0 ? v.y - lse_h : v.y + off[s];
+      const float l2 = s == 0 ? v.z - lse_h : v.z + off[s], l3 = s == 0 ? v.w - lse_h : v.w + off[s];
+      key[e0] = j < lim[s] ? lp_key(l0) : 0u;
+      key[e0 + 1] = j + 1 < lim[s] ? lp_key(l1) : 0u;
+      key[e0 + 2] = j + 2 < lim[s] ? lp_key(l2) : 0u;
+      key[e0 + 3] = j + 3 < lim[s] ? lp_key(l3) : 0u;
+      tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
+    }
+  auto each = [&](auto f) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f(key[(LPF_OFF[s] + q) * 4 + e], 0);
+  };
+  auto sweep = [&](auto chunk) {                              // chunk (s, q): ids base[s] + q * 4096 .. + 4095, four per thread
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q)
+        if (q * 4096 < lim[s]) {                              // (uniform)
+          const int e0 = (LPF_OFF[s] + q) * 4;
+          chunk(key[e0], key[e0 + 1], key[e0 + 2], key[e0 + 3], base[s] + (q * 1024 + tid) * 4);
+        }
+  };
+  nucleus_row(each, sweep, tmax, i, a, sm);
+}
+// Any row: the log-probs with the arithmetic of logprob_argmax_kernel, read from memory in every pass (a chunk of pass 3 is
+// 1024 consecutive ids, one per thread).
+__global__ __launch_bounds__(1024) void logprob_nucleus_stream_kernel(LogProbArgs p, SampleArgs a) {
+  __shared__ float red[16];
+  __shared__ NucleusSmem sm;
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const float* hrow = p.head + (long)i * p.ld_head;
+  float mx = -INFINITY;
+#pragma unroll 4
+  for (int j = tid; j < p.head_n; j += 1024) mx = fmaxf(mx, hrow[j]);
+  mx = block_max(mx, red);
+  float s = 0.f;
+#pragma unroll 4
+  for (int j = tid; j < p.head_n; j += 1024) s += __expf(hrow[j] - mx);
+  s = block_sum(s, red);
+  const float lse_h = mx + __logf(s);
+  float off[3] = {0.f, 0.f, 0.f};
+  for (int c = 0; c < p.n_tails; ++c) {
+    const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+    const int n = p.tail_n[c];
+    float m2 = -INFINITY;
+#pragma unroll 4
+    for (int j = tid; j < n; j += 1024) m2 = fmaxf(m2, trow[j]);
+    m2 = block_max(m2, red);
+    float s2 = 0.f;
+#pragma unroll 4
+    for (int j = tid; j < n; j += 1024) s2 += __expf(trow[j] - m2);
+    s2 = block_sum(s2, red);
+    off[c] = (hrow[p.c0 + c] - lse_h) - (m2 + __logf(s2));
+  }
+  auto each = [&](auto f) {
+    for (int j = tid; j < p.c0; j += 1024) f(lp_key(hrow[j] - lse_h), j);
+    int base = p.c0;
+    for (int c = 0; c < p.n_tails; ++c) {
+      const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+      for (int j = tid; j < p.tail_n[c]; j += 1024) f(lp_key(trow[j] + off[c]), base + j);
+      base += p.tail_n[c];
+    }
+  };
+  auto sweep = [&](auto chunk) {
+    for (int j0 = 0; j0 < p.c0; j0 += 1024) {
+      const int j = j0 + tid;
+      chunk(j < p.c0 ? lp_key(hrow[j] - lse_h) : 0u, 0u, 0u, 0u, j);
+    }
+    int base = p.c0;
+    for (int c = 0; c < p.n_tails; ++c) {
+      const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+      const int n = p.tail_n[c];
+      for (int j0 = 0; j0 < n; j0 += 1024) {
+        const int j = j0 + tid;
+        chunk(j < n ? lp_key(trow[j] + off[c]) : 0u, 0u, 0u, 0u, base + j);
+      }
+      base += n;
+    }
+  };
+  uint32_t tmax = 0;
+  each([&](uint32_t key, int) { tmax = max(tmax, key); });
+  nucleus_row(each, sweep, tmax, i, a, sm);
+}
+extern "C" int tell_adaptive_logprob_nucleus(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                             int rows, int k, float inv_temp, float p, const uint32_t* seed_dev,
+                                             const int* row_ids, int step, const int* step_dev, int* tokens, float* lps,
+                                             int* nuc_size, uint32_t* nuc_key, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_nucleus: up to 3 tails");
+  TELL_REQUIRE(k == 0 || (k >= 2 && k <= 64), "logprob_nucleus: k = 0 (no top-k cut) or 2 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_nucleus: inv_temp > 0");
+  TELL_REQUIRE(p > 0.f && p <= 1.f, "logprob_nucleus: 0 < p <= 1");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_nucleus: seed_dev, tokens and lps are required");
+  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(vocab >= 1 && vocab >= k && vocab < (1L << 19), "logprob_nucleus: k <= vocab < 2^19");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs q;
+  q.head = head; q.ld_head = ld_head; q.head_n = c0 + n_tails; q.c0 = c0; q.n_tails = n_tails; q.rows = rows;
+  q.tail[0] = tail0; q.ld_tail[0] = ld0; q.tail_n[0] = n0;
+  q.tail[1] = tail1; q.ld_tail[1] = ld1; q.tail_n[1] = n1;
+  q.tail[2] = tail2; q.ld_tail[2] = ld2; q.tail_n[2] = n2;
+  q.log_probs = nullptr; q.ld_lp = 0; q.token = nullptr; q.token_lp = nullptr;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = p; a.nuc_size = nuc_size; a.nuc_key = nuc_key;
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs = tell_opt(OPT_ARGMAX_REGS) != 0 && aligned && q.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
+                    (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096);
+  if (k > 0) {                                                // the top-k sampler's selection, then the nucleus of the k
+    if (regs) hipLaunchKernelGGL(logprob_sample_regs_kernel<true>, dim3(rows), dim3(1024), 0, stream, q, a);
+    else hipLaunchKernelGGL(logprob_sample_stream_kernel<true>, dim3(rows), dim3(1024), 0, stream, q, a);
+    return tell_check_launch("logprob_nucleus (top-k)");
+  }
+  if (regs) hipLaunchKernelGGL(logprob_nucleus_regs_kernel, dim3(rows), dim3(1024), 0, stream, q, a);
+  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel, dim3(rows), dim3(1024), 0, stream, q, a);
+  return tell_check_launch("logprob_nucleus");
+}
+
+// the nucleus of given candidates (sorted best first, as tell_sample_candidates takes them): one thread per row
+__global__ __launch_bounds__(256) void nucleus_candidates_kernel(const int* __restrict__ cand_tokens,
+                                                                 const float* __restrict__ cand_lps, int rows, SampleArgs a) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const float* lp = cand_lps + (long)r * a.k;
+  const int* id = cand_tokens + (long)r * a.k;
+  const int n = nucleus_prefix(lp, a.k, a.inv_temp, a.topp);
+  int order[64];                                              // the members by ascending id (insertion sort, n <= 64)
+  for (int j = 0; j < n; ++j) {
+    int q = j;
+    while (q > 0 && id[order[q - 1]] > id[j]) { order[q] = order[q - 1]; --q; }
+    order[q] = j;
+  }
+  const int j = nucleus_draw(lp, order, n, a.inv_temp, sample_args_u(a, r));
+  a.tokens[r] = id[j];
+  a.lps[r] = lp[j];
+}
+extern "C" int tell_nucleus_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp, float p,
+                                       const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev,
+                                       int* tokens, float* lps, hipStream_t stream) {
+  TELL_REQUIRE(k >= 1 && k <= 64, "nucleus_candidates: 1 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "nucleus_candidates: inv_temp > 0");
+  TELL_REQUIRE(p > 0.f && p <= 1.f, "nucleus_candidates: 0 < p <= 1");
+  TELL_REQUIRE(seed_dev && cand_tokens && cand_lps && tokens && lps, "nucleus_candidates: null pointer");
+  if (rows <= 0) return TELL_OK;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = p; a.nuc_size = nullptr; a.nuc_key = nullptr;
+  hipLaunchKernelGGL(nucleus_candidates_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, cand_tokens, cand_lps, rows, a);
+  return tell_check_launch("nucleus_candidates");
 }
 
 // ------------------------------------------------------------------ greedy generation: one step's bookkeeping

@@ -16,7 +16,7 @@ from .transformer import CaptionModel, Model, check_sampling, draw_seed
 class BaselineGloveModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
-                 weigh_bert=False, initializer=None, resnet=None):
+                 weigh_bert=False, initializer=None, resnet=None, sampling_topp=None):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -25,7 +25,8 @@ class BaselineGloveModel(Model):
             resnet = resnet152()
         self.resnet = resnet
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
-        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
+        self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
         self.max_caption_len = max_caption_len
         self.n_batches = self.n_samples = 0
 
@@ -89,10 +90,13 @@ class BaselineGloveModel(Model):
         batch at its full size (finished rows masked) gives the same token ids: pad after <eos>, length = 1 + steps
         until the last row has finished.  sampling_topk = k > 1 (:247-320 with topk + multinomial): the k best of the full
         log-prob row, sorted, and the draw of tell_sample_candidates keyed on (seed, row, step) - one seed per call from
-        torch's default CPU generator."""
+        torch's default CPU generator.  sampling_topp = p: the nucleus draw - of those k candidates
+        (tell_nucleus_candidates), or with k = 0 of the whole row (tell_adaptive_logprob_nucleus over the log-prob row as a
+        head without tails: a log-softmax of log-probs leaves them as they are)."""
         B, dev = caption_ids.shape[0], caption_ids.device
         k = int(self.sampling_topk)
-        if k > 1:
+        topp = self.sampling_topp
+        if k > 1 or topp is not None:
             seed_word = torch.full((1,), draw_seed(), dtype=torch.int32, device=dev)
             inv_temp = 1.0 / float(self.sampling_temp)
         cur = caption_ids[:, 0:1].contiguous()
@@ -104,7 +108,19 @@ class BaselineGloveModel(Model):
         for i in range(gen_len):
             out = self.decoder({self.index: cur}, contexts, incremental_state=state)
             lp_all = self.decoder.get_normalized_probs((out[0][:, -1:], None), log_probs=True).squeeze(1).float()
-            if k == 1:
+            if topp is not None:
+                tok32 = torch.empty(B, dtype=torch.int32, device=dev)
+                lp = torch.empty(B, dtype=torch.float32, device=dev)
+                if k == 0:
+                    lp_all = lp_all.contiguous()
+                    ops.call('tell_adaptive_logprob_nucleus', lp_all, lp_all.stride(0), lp_all.shape[1], 0, None, 0, 0, None, 0,
+                             0, None, 0, 0, B, 0, inv_temp, topp, seed_word, None, i, None, tok32, lp, None, None)
+                else:
+                    top_lp, top_ix = lp_all.topk(k, dim=-1)                        # sorted, best first
+                    ops.call('tell_nucleus_candidates', top_ix.to(torch.int32).contiguous(), top_lp.contiguous(), B, k,
+                             inv_temp, topp, seed_word, None, i, None, tok32, lp)
+                tok = tok32.long()
+            elif k == 1:
                 lp, tok = lp_all.max(dim=-1)
             else:
                 top_lp, top_ix = lp_all.topk(k, dim=-1)                            # sorted, best first
@@ -131,7 +147,7 @@ class TransformerGloveModel(CaptionModel):
 
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024, dropout=0.1,
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
-                 use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None):
+                 use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -140,7 +156,8 @@ class TransformerGloveModel(CaptionModel):
             resnet = resnet152()
         self.resnet = resnet
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
-        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
+        self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0

@@ -22,7 +22,7 @@ from torch.nn.init import constant_, xavier_normal_, xavier_uniform_
 from .. import ops
 from ..modules.linear import GehringLinear
 from ..modules.self_attention import SelfAttention
-from .transformer import CaptionModel, Model
+from .transformer import CaptionModel, Model, draw_seed
 
 logger = logging.getLogger(__name__)
 
@@ -51,12 +51,12 @@ class PointerModelBase(CaptionModel):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
-                 model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25):
-        if sampling_topk != 1:
+                 model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None):
+        if sampling_topk != 1 and sampling_topp is None:       # (with sampling_topp: the generated token is a nucleus draw)
             raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
         super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
                          model_name, namespace, index, padding_value, use_context, sampling_topk, sampling_temp,
-                         weigh_bert, initializer, resnet, roberta, n_bert_layers)
+                         weigh_bert, initializer, resnet, roberta, n_bert_layers, sampling_topp)
         if weigh_bert:
             self.bert_weight_2 = nn.Parameter(torch.rand(n_bert_layers))      # :61-62
         self.batch_history = defaultdict(float)        # summed on the device (0-d tensors); floats once get_metrics reads
@@ -189,6 +189,9 @@ class PointerModelBase(CaptionModel):
         log_probs, paths, copies, probs = [], [seed], [torch.ones(B, 1, dtype=torch.bool, device=dev)], []
         names = [k for k in contexts if not k.endswith('_mask') and not k.startswith('_')]
         ea = self.entity_attn
+        sampling = self._sampling()                                   # (k, T, p) with sampling_topp, else None
+        if sampling is not None:
+            seed_word = torch.full((1,), draw_seed(), dtype=torch.int32, device=dev)
         for i in range(gen_len):
             self.decoder.filter_incremental_state(state, keep)
             ctx_i = {}
@@ -197,7 +200,12 @@ class PointerModelBase(CaptionModel):
                 ctx_i[n + '_mask'] = contexts[n + '_mask'][alive]
             dec_out = self.decoder({self.index: cur[:, -1:]}, ctx_i, incremental_state=state)
             h = dec_out[0][:, -1:]                                                   # [Ba, 1, E]
-            gen_tok, lp = self.decoder.adaptive_softmax.greedy(h)
+            rows = alive.nonzero().squeeze(1).to(torch.int32)
+            if sampling is None:
+                gen_tok, lp = self.decoder.adaptive_softmax.greedy(h)
+            else:                                                                    # keyed on the ORIGINAL batch rows
+                gen_tok, lp = self.decoder.adaptive_softmax.sample(h, sampling[0], sampling[1], seed_word, i, row_ids=rows,
+                                                                   topp=sampling[2])
             x = h.transpose(0, 1).contiguous()                                       # [1, Ba, E]
             k, v = ea.project_kv(x)
             if k_hist is not None:
@@ -208,7 +216,6 @@ class PointerModelBase(CaptionModel):
             x_entity = ea.step(x, k_hist, v_hist)
             fc = self.entity_fc
             ent = ops.entity_logits(x_entity, fc.weight_g, fc.weight_v, fc.bias)
-            rows = alive.nonzero().squeeze(1).to(torch.int32)
             tok, copied, prob = ops.copy_step(self._copy_q(x[0]).contiguous(), k_article, self.bias_k, art_mask, proper,
                                               ctx_ids, rows, ent, gen_tok.reshape(-1).long(), hist, i + 1,
                                               self.copy_heads)

@@ -67,9 +67,24 @@ class Model(nn.Module, Registrable):
 MAX_SAMPLING_TOPK = 64          # tell_adaptive_logprob_sample's exact top-k
 
 
-def check_sampling(sampling_topk, sampling_temp):
+def check_sampling(sampling_topk, sampling_temp, sampling_topp=None):
     """The caption models' `sampling_topk` / `sampling_temp` (transformer_faces_objects.py:38-55): top-k sampling with a
-    temperature, 1 <= k <= 64 (k = 1: the arg-max token) and T > 0.  -> (k, T); ValueError otherwise."""
+    temperature, 1 <= k <= 64 (k = 1: the arg-max token) and T > 0.  -> (k, T); ValueError otherwise.
+    With `sampling_topp` = p (nucleus sampling, 0 < p <= 1): k is 0 (no top-k cut) or 2..64 -> (k, T, p)."""
+    if sampling_topp is not None:
+        p = sampling_topp
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
+            raise ValueError('sampling_topp must be a number with 0 < p <= 1, or None (got %r)' % (p,))
+        k = sampling_topk
+        if not isinstance(k, bool) and isinstance(k, (int, float)) and k == 1:
+            raise ValueError('sampling_topk=1 (the arg-max token) and sampling_topp=%r do not combine: pass sampling_topk=0 '
+                             'for a nucleus without a top-k cut' % (p,))
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or \
+                not (int(k) == 0 or 2 <= int(k) <= MAX_SAMPLING_TOPK):
+            raise ValueError('with sampling_topp, sampling_topk must be 0 (no top-k cut) or an integer in 2..%d (got %r)'
+                             % (MAX_SAMPLING_TOPK, k))
+        _, temp = check_sampling(2, sampling_temp)
+        return int(k), temp, float(p)
     if isinstance(sampling_topk, bool) or not isinstance(sampling_topk, (int, float)) or int(sampling_topk) != sampling_topk \
             or not 1 <= int(sampling_topk) <= MAX_SAMPLING_TOPK:
         raise ValueError('sampling_topk must be an integer in 1..%d (got %r)' % (MAX_SAMPLING_TOPK, sampling_topk))
@@ -77,6 +92,36 @@ def check_sampling(sampling_topk, sampling_temp):
             or float(sampling_temp) == float('inf'):
         raise ValueError('sampling_temp must be a finite number > 0 (got %r)' % (sampling_temp,))
     return int(sampling_topk), float(sampling_temp)
+
+
+def nucleus_definition(lp, temp, topp, topk=0, u=None):
+    """The definition of nucleus sampling (include/tell_hip.h tell_adaptive_logprob_nucleus, steps 1-4) on one row of
+    log-probs, in fp64 on the CPU - what the kernel is tested against.  lp: [V] log-probs; temp = T; topp = p; topk = 0 or
+    the size of the top-k cut; u in [0, 1) or None.
+    -> dict: members (token ids of the nucleus, ascending), boundary (the smallest member log-prob), margin
+    (|cum - p * total| / total at the boundary: the smaller of the distances by which the prefix reaches p * total and by
+    which the prefix without its last member misses it), cdf (running weight of the members in id order, normalised),
+    token (the pick for u, or None)."""
+    import numpy as np
+    lp = np.asarray(lp, dtype=np.float64).reshape(-1)
+    p = float(topp)
+    order = np.lexsort((np.arange(lp.size), -lp))             # value descending, lower id first on ties
+    if topk:
+        order = order[:int(topk)]
+    w = np.exp((lp[order] - lp[order[0]]) / float(temp))
+    cum = np.cumsum(w)
+    total = cum[-1]
+    n = min(int(np.searchsorted(cum, p * total, side='left')) + 1, order.size)
+    members = np.sort(order[:n])
+    margin = min(cum[n - 1] - p * total, p * total - (cum[n - 2] if n > 1 else 0.0)) / total
+    wm = np.exp((lp[members] - lp[order[0]]) / float(temp))
+    run = np.cumsum(wm)
+    out = {'members': members, 'boundary': float(lp[order[n - 1]]), 'margin': float(abs(margin)), 'cdf': run / run[-1],
+           'token': None}
+    if u is not None:
+        hit = np.nonzero(run > float(u) * run[-1])[0]
+        out['token'] = int(members[hit[0]] if hit.size else members[-1])
+    return out
 
 
 def draw_seed():
@@ -92,7 +137,7 @@ class CaptionModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
-                 initializer=None, resnet=None, roberta=None, n_bert_layers=25):
+                 initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -106,7 +151,8 @@ class CaptionModel(Model):
         self.use_context = use_context
         self.padding_idx = padding_value
         self.evaluate_mode = evaluate_mode
-        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp)
+        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
+        self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -118,11 +164,18 @@ class CaptionModel(Model):
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.reset_graphs())
 
     def _sampling(self):
-        """-> (k, T) when generation samples (sampling_topk > 1), None for the arg-max decode (sampling_topk = 1)."""
+        """-> (k, T) when generation samples (sampling_topk > 1), None for the arg-max decode (sampling_topk = 1);
+        (k, T, p) with nucleus sampling (sampling_topp = p; k = 0: no top-k cut)."""
         k = int(self.sampling_topk)
+        p = getattr(self, 'sampling_topp', None)
+        if p is not None:
+            return (k, float(self.sampling_temp), float(p))
         return (k, float(self.sampling_temp)) if k > 1 else None
 
     def _check_beam(self, beam_size):
+        if int(beam_size) > 1 and getattr(self, 'sampling_topp', None) is not None:
+            raise ValueError('beam search (beam_size %d) and nucleus sampling (sampling_topp %r) do not combine'
+                             % (int(beam_size), self.sampling_topp))
         if int(beam_size) > 1 and self._sampling() is not None:
             raise ValueError('beam search (beam_size %d) and top-k sampling (sampling_topk %d) do not combine: the reference '
                              'samples without a beam' % (int(beam_size), int(self.sampling_topk)))
@@ -602,6 +655,9 @@ class CaptionModel(Model):
 
         def make_head(seed_dev):
             if sample is not None:
+                topp = sample[2] if len(sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
+                if topp is not None:
+                    return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, topp=topp)
                 return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx)
             if topk:
                 return lambda x, sidx: dec.adaptive_softmax.topk(x, topk)
@@ -623,7 +679,8 @@ class CaptionModel(Model):
         sig = (B, dtype, topk, int(gen_len), tuple((n, tuple(kv[0][n][0].shape), tuple(kv[0][n][1].shape)) for n in names),
                dec.embedder.token_embedder_position.weights.data_ptr(), int(lane))
         if sample is not None:                                    # (greedy and beam signatures are unchanged)
-            sig = sig + (('sample', int(sample[0]), float(sample[1])),)
+            sig = sig + ((('sample', int(sample[0]), float(sample[1])) if len(sample) == 2 else
+                          ('nucleus', int(sample[0]), float(sample[1]), float(sample[2]))),)
         cache = self.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -966,7 +1023,7 @@ class CaptionModel(Model):
             else:                                                                   # :443-470, topk + multinomial
                 rows = alive.nonzero().squeeze(1).to(torch.int32)
                 tok, lp = self.decoder.adaptive_softmax.sample(dec_out[0][:, -1:], sampling[0], sampling[1], seed_word, i,
-                                                               row_ids=rows)
+                                                               row_ids=rows, **({'topp': sampling[2]} if len(sampling) > 2 else {}))
             sel_ix = tok.long()
             sel_lp = lp / self.sampling_temp
             full_lp = sel_lp.new_zeros(B, 1)

@@ -1748,11 +1748,17 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
     """The sampling head's last launch (tell_adaptive_logprob_sample) over the fp32 logits of the head and the tails.
     sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
     int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
-    counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None)."""
-    k, inv_temp, seed_dev, row_ids, step = sample
+    counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None).
+    A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut)."""
+    k, inv_temp, seed_dev, row_ids, step = sample[:5]
     step_dev = step if torch.is_tensor(step) else None
     token = torch.empty(N, dtype=torch.int32, device=head.device)
     token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
+    if len(sample) > 5:
+        call('tell_adaptive_logprob_nucleus', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
+             lds[2], ns[2], N, int(k), float(inv_temp), float(sample[5]), seed_dev, row_ids,
+             0 if step_dev is not None else int(step), step_dev, token, token_lp, None, None)
+        return token, token_lp, None
     call('tell_adaptive_logprob_sample', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
          ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token,
          token_lp)
@@ -1762,7 +1768,8 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
 def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
-    sample = (k, inv_temp, seed_dev, row_ids, step): one top-k draw per row instead of the arg-max (logprob_sample)."""
+    sample = (k, inv_temp, seed_dev, row_ids, step[, p]): one top-k (with p: nucleus) draw per row instead of the arg-max
+    (logprob_sample)."""
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
