@@ -387,6 +387,30 @@ int tell_attn_decode(int n_ctx, const void* const* q, const long* q_sb, const vo
                      const long* v_sh, const void* const* mask, const void* const* bias_k, const void* const* bias_v,
                      int has_zero, const int* S, void* const* out, const long* o_sb, int B, int H, int beams,
                      tell_stream_t stream);
+/* tell_attn_decode + the HEAD-AVERAGED ATTENTION WEIGHTS of the step (multi_head.py:478-482; what the reference's generate()
+ * returns per generated word, transformer_faces_objects.py:142-309).  Everything up to `beams` is tell_attn_decode's.  Contract:
+ *   - out[c] is bit-identical to what tell_attn_decode writes for the same arguments (the same kernel; its exporting form only
+ *     ADDS one store per (context, row, head): the base-2 log-sum-exp, into lse_ws - a workspace of n_ctx * B * H floats);
+ *   - row b of context c receives S[c] + 2 floats at w[c] + slot * w_st[c] + b * w_sb[c] (strides in floats, w_sb[c] >=
+ *     S[c] + 2): w[s] = (1/H) * sum_h softmax_h(s); columns 0 .. S-1 are the cached keys, column S the learned bias_k key,
+ *     column S + 1 the zero key.  A masked key - and the bias / zero column when bias_k[c] is NULL / has_zero is 0 - is exactly
+ *     0.0f.  S = 0 writes the two virtual columns only;
+ *   - slot = slot_host + *step_dev (step_dev NULL: slot_host - the convention of tell_dynconv_step's t): an eager step passes
+ *     its index, a captured step the index it was captured at minus the counter's value then, plus the device word that the
+ *     step's bookkeeping launch moves along, so one captured step and a graph of several steps write a fresh slot per replay.
+ *     0 <= slot < n_slots is checked on the host (step_dev NULL) and on the device (outside: nothing is written);
+ *   - beams == 1 (an error otherwise: beam search would need the ancestor walk of tell_beam_update applied to the slots);
+ *   - no atomic on a float: the sum over the heads runs in a register, head 0 first, so a row's weights are the same bits
+ *     whatever the batch size, the launch mode (eager, captured) and the run.
+ * Two launches: the one-pass attention in its exporting form, then one workgroup per (row, context, 128 columns) that
+ * recomputes q_h . k_h[s] head by head from the K cache (never V) and accumulates exp2(score * log2 e - lse2_h).
+ * bf16, head width 64, n_ctx <= 4, S <= 2048, row-major [S, B, E] and head-major (k_sh) caches. */
+int tell_attn_decode_weights(int n_ctx, const void* const* q, const long* q_sb, const void* const* k, const long* k_ss,
+                             const long* k_sb, const long* k_sh, const void* const* v, const long* v_ss, const long* v_sb,
+                             const long* v_sh, const void* const* mask, const void* const* bias_k,
+                             const void* const* bias_v, int has_zero, const int* S, void* const* out, const long* o_sb,
+                             int B, int H, int beams, float* lse_ws, float* const* w, const long* w_st, const long* w_sb,
+                             int slot, int n_slots, const int* step_dev, tell_stream_t stream);
 /* n LayerNorms over ONE residual in one launch each way - the end of a decoder layer's context block
    (decoder_faces_objects.py:283-352): y[:, i*C:(i+1)*C] = LayerNorm_i(res + dropout_p(x_i)), mean / rstd [n, rows].
    Backward: dx_i (entries may be NULL), dres = sum_i dz_i (may be NULL), dgamma_i / dbeta_i ACCUMULATED; partial is a

@@ -34,7 +34,9 @@ def _ttr(text):
 
 
 def write_to_json(output_dict, serialization_dir, eval_suffix='', annotate=None):
-    """evaluate.py:179-223.  annotate(record, metadata) may add the NLP-derived keys (caption_names, ...)."""
+    """evaluate.py:179-223.  annotate(record, metadata) may add the NLP-derived keys (caption_names, ...).  With
+    `attn_words` in the output (evaluate(attention_maps=True)) every record also carries `attns`: the per-word attention
+    view of its generation (models/attention_maps.py)."""
     if 'captions' not in output_dict:
         return
     captions, generations, metadatas = output_dict['captions'], output_dict['generations'], output_dict['metadata']
@@ -47,14 +49,19 @@ def write_to_json(output_dict, serialization_dir, eval_suffix='', annotate=None)
                    'copied_texts': copied[i], 'web_url': m.get('web_url'), 'image_path': m.get('image_path'),
                    'context': m.get('context'), 'caption_np': _ttr(m.get('caption') or ''),
                    'gen_np': _ttr(generations[i])}
+            if 'attn_words' in output_dict:
+                obj['attns'] = output_dict['attn_words'][i]
             if annotate is not None:
                 annotate(obj, m)
             f.write(json.dumps(obj) + '\n')
 
 
 def evaluate(model, instances, data_iterator, cuda_device, serialization_dir, eval_suffix='', batch_weight_key='',
-             annotate=None, beam_size=1):
-    """evaluate.py:89-176: -> final metrics dict (model metrics + the weighted average loss)."""
+             annotate=None, beam_size=1, attention_maps=False, bpe=None):
+    """evaluate.py:89-176: -> final metrics dict (model metrics + the weighted average loss).
+    attention_maps=True (opt-in; greedy / top-k / nucleus only): the captions are generated with their attention maps and
+    every record of generations.jsonl gets an `attns` key, the reference's per-word view (model.caption_attention; `bpe`:
+    an injected tokenizer, default the installed RoBERTa files).  Off: the file is what it always was."""
     os.makedirs(serialization_dir, exist_ok=True)
     assert not os.path.exists(os.path.join(serialization_dir, 'generations%s.jsonl' % eval_suffix))
     device = torch.device(cuda_device) if not isinstance(cuda_device, int) else \
@@ -63,24 +70,39 @@ def evaluate(model, instances, data_iterator, cuda_device, serialization_dir, ev
         model.eval()
         model.evaluate_mode = True
         model.eval_beam_size = beam_size
+        if attention_maps:
+            # (only models whose evaluate-mode forward generates WITH maps: a model that ignored the switch would write a
+            #  file without them and say nothing)
+            if not getattr(model, 'EVAL_ATTENTION', False) or not hasattr(model, 'caption_attention'):
+                raise ValueError('attention_maps=True: %s exports no attention maps in evaluate mode' % type(model).__name__)
+            model._check_attention(beam_size)
         loss_count, total_loss, total_weight = 0, 0.0, 0.0
         batches = data_iterator(instances, num_epochs=1, shuffle=False, device=device)
         lanes = int(os.environ.get('TELL_EVAL_LANES', '2'))
-        if hasattr(model, 'generate_lanes') and lanes > 1:
-            # two batches' decode loops in flight together on two streams (CaptionModel.generate_lanes): +17-27 % captions/s
-            outputs = (out for _, out in model.generate_lanes(batches, lanes=lanes, forward=True))
-        elif hasattr(model, 'generate_stream'):       # encoders of batch N+1 underneath the decode loop of batch N
-            outputs = (out for _, out in model.generate_stream(batches, forward=True))
-        else:
-            outputs = (model(**batch) for batch in batches)
-        for output_dict in outputs:
-            loss = output_dict.get('loss')
-            write_to_json(output_dict, serialization_dir, eval_suffix, annotate)
-            if loss is not None:
-                loss_count += 1
-                weight = float(output_dict[batch_weight_key]) if batch_weight_key else 1.0
-                total_weight += weight
-                total_loss += float(loss) * weight
+        model.eval_attention = bool(attention_maps)
+        try:
+            if hasattr(model, 'generate_lanes') and lanes > 1:
+                # two batches' decode loops in flight together on two streams (CaptionModel.generate_lanes): +17-27 % captions/s
+                outputs = model.generate_lanes(batches, lanes=lanes, forward=True)
+            elif hasattr(model, 'generate_stream'):       # encoders of batch N+1 underneath the decode loop of batch N
+                outputs = model.generate_stream(batches, forward=True)
+            else:
+                outputs = ((batch, model(**batch)) for batch in batches)
+            for batch, output_dict in outputs:
+                loss = output_dict.get('loss')
+                if attention_maps and 'captions' in output_dict:
+                    if not isinstance(output_dict.get('attns'), dict):
+                        raise ValueError('attention_maps=True: %s generated captions without attention maps'
+                                         % type(model).__name__)
+                    output_dict['attn_words'] = model.caption_attention(batch, output_dict, bpe=bpe)
+                write_to_json(output_dict, serialization_dir, eval_suffix, annotate)
+                if loss is not None:
+                    loss_count += 1
+                    weight = float(output_dict[batch_weight_key]) if batch_weight_key else 1.0
+                    total_weight += weight
+                    total_loss += float(loss) * weight
+        finally:
+            model.eval_attention = False              # (also when the loop raises: the switch never outlives the call)
         final_metrics = model.get_metrics(reset=True)
         if loss_count > 0:
             final_metrics['loss'] = total_loss / total_weight

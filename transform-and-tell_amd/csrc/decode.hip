@@ -1068,8 +1068,14 @@ struct AttnDecArgs { AttnDecCtx c[SK_MAXP]; int B, H, beams; };
 // in flight per lane), no score ever leaves the registers, nothing synchronises until the end, where the 8 key slots of a wave
 // merge through shuffles and the 4 waves through LDS.  The learned bias_k / bias_v key and the zero key are two more keys of
 // wave 0's first slot.
-template <int NQ>
-__global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecArgs g) {
+// LSE (tell_attn_decode_weights): the same kernel, same arithmetic, that additionally leaves every (context, row, head)'s
+// base-2 log-sum-exp m + log2(l) in lse2 [n_ctx, B, H] fp32 for the weight export below; the plain instantiation takes the
+// plain argument block and carries no trace of it.
+struct AttnDecArgsLse : AttnDecArgs { float* lse2; };
+template <bool LSE> struct AttnDecArgsOf { typedef AttnDecArgs type; };
+template <> struct AttnDecArgsOf<true> { typedef AttnDecArgsLse type; };
+template <int NQ, bool LSE = false>
+__global__ __launch_bounds__(256) void attn_decode_kernel(typename AttnDecArgsOf<LSE>::type g) {
   const AttnDecCtx& p = g.c[blockIdx.y];
   __shared__ float part_o[NQ][NQ <= 2 ? 4 : 32][64];           // per wave (NQ <= 2) / per (wave, key slot): output, (max, sum)
   __shared__ float part_ml[NQ][NQ <= 2 ? 4 : 32][2];
@@ -1248,6 +1254,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecArgs g) {
       v = fmaf(part_o[i][sl][d], a, v);
     }
     p.out[(long)(b0 + i) * p.o_sb + h * 64 + d] = f2bf(lt > 0.f ? v / lt : 0.f);
+    if constexpr (LSE) {
+      if (d == 0) g.lse2[((long)blockIdx.y * g.B + b0 + i) * g.H + h] = lt > 0.f ? mn + __log2f(lt) : -INFINITY;
+    }
   }
 }
 
@@ -1256,13 +1265,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecArgs g) {
 // (k_sh / v_sh NULL: 64 - heads side by side in a row of E; the generation loop keeps its cache HEAD-MAJOR, [B, H, S, 64]:
 // the S keys a workgroup walks are then one contiguous 64 KB block instead of 128-byte pieces a whole [B, 2E] row apart),
 // mask[c] [B / beams, S[c]] uint8 or null, bias_k[c] / bias_v[c] [H*64] or null, out[c] [B, H*64] (row stride o_sb[c]).
-extern "C" int tell_attn_decode(int n_ctx, const void* const* q, const long* q_sb, const void* const* k, const long* k_ss,
-                                const long* k_sb, const long* k_sh, const void* const* v, const long* v_ss, const long* v_sb,
-                                const long* v_sh, const void* const* mask, const void* const* bias_k,
-                                const void* const* bias_v, int has_zero, const int* S, void* const* out, const long* o_sb,
-                                int B, int H, int beams, hipStream_t stream) {
+static int attn_decode_fill(AttnDecArgs& g, int n_ctx, const void* const* q, const long* q_sb, const void* const* k, const long* k_ss,
+                            const long* k_sb, const long* k_sh, const void* const* v, const long* v_ss, const long* v_sb,
+                            const long* v_sh, const void* const* mask, const void* const* bias_k,
+                            const void* const* bias_v, int has_zero, const int* S, void* const* out, const long* o_sb,
+                            int B, int H, int beams) {
   TELL_REQUIRE(n_ctx >= 1 && n_ctx <= SK_MAXP && B > 0 && H > 0 && beams >= 1 && B % beams == 0, "attn_decode: 1-4 contexts");
-  AttnDecArgs g;
   g.B = B; g.H = H; g.beams = beams;
   for (int c = 0; c < SK_MAXP; ++c) {
     const int j = c < n_ctx ? c : 0;
@@ -1280,11 +1288,123 @@ extern "C" int tell_attn_decode(int n_ctx, const void* const* q, const long* q_s
     g.c[c].o_sb = o_sb[j]; g.c[c].S = S[j]; g.c[c].has_zero = has_zero ? 1 : 0;
     g.c[c].bias_k = bias_k ? (const uint16_t*)bias_k[j] : nullptr; g.c[c].bias_v = bias_v ? (const uint16_t*)bias_v[j] : nullptr;
   }
+  return TELL_OK;
+}
+extern "C" int tell_attn_decode(int n_ctx, const void* const* q, const long* q_sb, const void* const* k, const long* k_ss,
+                                const long* k_sb, const long* k_sh, const void* const* v, const long* v_ss, const long* v_sb,
+                                const long* v_sh, const void* const* mask, const void* const* bias_k,
+                                const void* const* bias_v, int has_zero, const int* S, void* const* out, const long* o_sb,
+                                int B, int H, int beams, hipStream_t stream) {
+  AttnDecArgs g;
+  const int rc = attn_decode_fill(g, n_ctx, q, q_sb, k, k_ss, k_sb, k_sh, v, v_ss, v_sb, v_sh, mask, bias_k, bias_v, has_zero, S,
+                                  out, o_sb, B, H, beams);
+  if (rc != TELL_OK) return rc;
   const int samples = B / beams;
   if (beams == 1) hipLaunchKernelGGL((attn_decode_kernel<1>), dim3(B * H, n_ctx), dim3(256), 0, stream, g);
   else if (beams == 2) hipLaunchKernelGGL((attn_decode_kernel<2>), dim3(samples * H, n_ctx), dim3(256), 0, stream, g);
   else hipLaunchKernelGGL((attn_decode_kernel<4>), dim3(samples * ((beams + 3) / 4) * H, n_ctx), dim3(256), 0, stream, g);
   return tell_check_launch("attn_decode");
+}
+
+// ------------------------------------------------------------------ head-averaged attention weights of a decode step
+// w[s] = (1/H) sum_h softmax_h(s) (multi_head.py:478-482) for the demo output of the reference's generate().  The one-pass
+// kernel above keeps no score, so the weights are a SECOND launch behind its LSE form: one workgroup per (row, context,
+// chunk of AW_CHUNK columns); 8 lanes share a key exactly as above (same loads, same dot product, same DPP reduction: the
+// score of (head, key) is bit for bit the one the attention saw), and every group of 8 lanes walks the heads h = 0 .. H-1 IN
+// ORDER for its four columns, adding exp2(score * log2 e - lse2_h) into a register.  No atomic, no cross-lane sum of weights:
+// a column's value depends on nothing but its row's q, K, mask and lse2 - not on the batch, the grid or the launch mode.  It
+// re-reads K (L2-warm from the launch before) and never V.  Columns S and S + 1 are the learned bias_k key and the zero key;
+// a masked key, an absent bias_k and an absent zero key give exactly 0.  The destination row is slot_host + *step_dev of a
+// [n_slots, B, S + 2]-shaped buffer: one captured launch writes a fresh slot per replay; a slot outside the buffer is skipped.
+#define AW_CHUNK 128
+struct AttnWArgs {
+  float* w[SK_MAXP]; long w_st[SK_MAXP], w_sb[SK_MAXP];
+  const float* lse2; const uint32_t* step_dev; int slot, n_slots;
+};
+__global__ __launch_bounds__(256) void attn_decode_weights_kernel(AttnDecArgs g, AttnWArgs a) {
+  const AttnDecCtx& p = g.c[blockIdx.y];
+  const int S = p.S, c0 = blockIdx.z * AW_CHUNK;
+  if (c0 >= S + 2) return;
+  const long slot = (long)a.slot + (a.step_dev ? (long)(int)*a.step_dev : 0L);
+  if (slot < 0 || slot >= a.n_slots) return;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ks = lane >> 3, dc = lane & 7;
+  const uint16_t* qb = p.q + (long)b * p.q_sb + dc * 8;
+  const uint16_t* kb = p.k + (long)b * p.k_sb + dc * 8;
+  const uint8_t* mk = p.mask ? p.mask + (long)b * S : nullptr;
+  const float* lse = a.lse2 + ((long)blockIdx.y * g.B + b) * g.H;
+  const int kss = (int)p.k_ss;
+  constexpr float LOG2E = 1.4426950408889634f;
+  constexpr int NU = AW_CHUNK / 32;
+  int col[NU], kind[NU];                    // kind: 0 = nothing to add (past the end, masked, absent), 1 = cached key, 2 = bias_k, 3 = zero key
+  float acc[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    col[u] = c0 + u * 32 + wave * 8 + ks;
+    acc[u] = 0.f;
+    if (col[u] < S) kind[u] = (mk && mk[col[u]] != 0) ? 0 : 1;
+    else if (col[u] == S) kind[u] = p.bias_k ? 2 : 0;
+    else if (col[u] == S + 1) kind[u] = p.has_zero ? 3 : 0;
+    else kind[u] = 0;
+  }
+  for (int h = 0; h < g.H; ++h) {           // heads in order, head 0 first
+    const uint4 q = *reinterpret_cast<const uint4*>(qb + h * 64);
+    const float l2 = lse[h];
+    uint4 kr[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      kr[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (kind[u] == 1) kr[u] = *reinterpret_cast<const uint4*>(kb + (long)h * p.k_sh + col[u] * kss);
+      else if (kind[u] == 2) kr[u] = *reinterpret_cast<const uint4*>(p.bias_k + h * 64 + dc * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      float d = sk_dot8(q, kr[u], 0.f);
+      d += sk_dpp<0xB1>(d); d += sk_dpp<0x4E>(d); d += sk_dpp<0x141>(d);
+      const float pr = (kind[u] != 0 && l2 != -INFINITY) ? __builtin_amdgcn_exp2f(d * LOG2E - l2) : 0.f;
+      acc[u] += pr;
+    }
+  }
+  if (dc == 0) {
+    float* wr = a.w[blockIdx.y] + slot * a.w_st[blockIdx.y] + (long)b * a.w_sb[blockIdx.y];
+    const float inv_h = 1.f / (float)g.H;
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (col[u] < S + 2) wr[col[u]] = acc[u] * inv_h;
+  }
+}
+
+// tell_attn_decode + the head-averaged weights of the step.  out[c] is what tell_attn_decode writes (same kernel, LSE form);
+// lse_ws: workspace of n_ctx * B * H floats; w[c] + slot * w_st[c] + b * w_sb[c]: S[c] + 2 floats per row, slot = slot_host +
+// *step_dev (step_dev NULL: slot_host), 0 <= slot < n_slots or nothing is written.  beams == 1.
+extern "C" int tell_attn_decode_weights(int n_ctx, const void* const* q, const long* q_sb, const void* const* k, const long* k_ss,
+                                        const long* k_sb, const long* k_sh, const void* const* v, const long* v_ss, const long* v_sb,
+                                        const long* v_sh, const void* const* mask, const void* const* bias_k,
+                                        const void* const* bias_v, int has_zero, const int* S, void* const* out, const long* o_sb,
+                                        int B, int H, int beams, float* lse_ws, float* const* w, const long* w_st, const long* w_sb,
+                                        int slot, int n_slots, const int* step_dev, hipStream_t stream) {
+  TELL_REQUIRE(beams == 1, "attn_decode_weights: one hypothesis per sample (beam search is not covered)");
+  TELL_REQUIRE(lse_ws && w && w_st && w_sb && n_slots >= 1, "attn_decode_weights: workspace and destinations");
+  AttnDecArgsLse g;
+  const int rc = attn_decode_fill(g, n_ctx, q, q_sb, k, k_ss, k_sb, k_sh, v, v_ss, v_sb, v_sh, mask, bias_k, bias_v, has_zero, S,
+                                  out, o_sb, B, H, beams);
+  if (rc != TELL_OK) return rc;
+  TELL_REQUIRE(step_dev || (slot >= 0 && slot < n_slots), "attn_decode_weights: slot outside the buffer");
+  g.lse2 = lse_ws;
+  AttnWArgs a;
+  int s_max = 0;
+  for (int c = 0; c < SK_MAXP; ++c) {
+    const int j = c < n_ctx ? c : 0;
+    TELL_REQUIRE(w[j] && w_sb[j] >= S[j] + 2 && w_st[j] >= 0, "attn_decode_weights: rows of S + 2 floats");
+    a.w[c] = w[j]; a.w_st[c] = w_st[j]; a.w_sb[c] = w_sb[j];
+    if (S[j] > s_max) s_max = S[j];
+  }
+  a.lse2 = lse_ws; a.step_dev = reinterpret_cast<const uint32_t*>(step_dev); a.slot = slot; a.n_slots = n_slots;
+  hipLaunchKernelGGL((attn_decode_kernel<1, true>), dim3(B * H, n_ctx), dim3(256), 0, stream, g);
+  const int rc2 = tell_check_launch("attn_decode (lse)");
+  if (rc2 != TELL_OK) return rc2;
+  hipLaunchKernelGGL(attn_decode_weights_kernel, dim3(B, n_ctx, (s_max + 2 + AW_CHUNK - 1) / AW_CHUNK), dim3(256), 0, stream,
+                     static_cast<const AttnDecArgs&>(g), a);
+  return tell_check_launch("attn_decode_weights");
 }
 
 // ------------------------------------------------------------------ one-query attention over a PACKED cache, matrix cores

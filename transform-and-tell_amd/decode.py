@@ -387,14 +387,43 @@ def attn_decode_usable(mods, kv_layer, names, q):
     return True
 
 
-def attn_decode_all(mods, names, qs, kv_layer, contexts, M, E):
+class AttnSink:
+    """Where a generation step leaves its head-averaged attention weights (model.generate(attention=True)): bufs[layer][name]
+    static fp32 [n_slots, B, S_name + 2] - one slot per decode step, columns: the S cached keys, the learned bias_k key, the
+    zero key.  The slot of a step is `slot + *step_dev`: `slot` a host integer (the step index of an eager step; in a
+    captured step the constant that, with the device counter, gives the step index), `step_dev` the counter word of a
+    captured step or None - the convention of tell_attn_decode_weights."""
+
+    def __init__(self, bufs, n_slots):
+        self.bufs, self.n_slots, self.slot, self.step_dev = bufs, int(n_slots), 0, None
+
+    def at(self, slot, step_dev=None):
+        self.slot, self.step_dev = int(slot), step_dev
+        return self
+
+    def index(self, device):
+        """The slot as a device tensor [1] (the per-context path writes with index_copy_: no host integer baked into a capture)."""
+        if self.step_dev is None:
+            return torch.full((1,), self.slot, dtype=torch.long, device=device)
+        return self.step_dev.reshape(1).long() + self.slot
+
+    def put(self, layer, name, w, idx):
+        """w [B, 1, S + 2] fp32 of tell_attn_avg_weights -> slot idx of the layer's buffer, on the device."""
+        self.bufs[layer][name].index_copy_(0, idx, w.transpose(0, 1).to(torch.float32))
+
+
+def attn_decode_all(mods, names, qs, kv_layer, contexts, M, E, sink=None):
     """The n one-query context attentions of a layer against the projected K / V cache as ONE launch (multi_head.py:376-475
     at Tq = 1): qs[i] [M, E] bf16 (projected, scaled) -> [n, M, E] bf16.  The `beams` hypotheses of a sample (rows
-    b * beams + j) share its cache: beams = M // (cached batch)."""
+    b * beams + j) share its cache: beams = M // (cached batch).
+    sink = (AttnSink, layer index): the exporting entry point instead (tell_attn_decode_weights: same output, + the
+    head-averaged weights of this step in the sink's slot); without one the launch is exactly what it was."""
     n = len(mods)
     dev = qs[0].device
     a_all = torch.empty(n, M, E, dtype=torch.bfloat16, device=dev)
     if isinstance(kv_layer[names[0]], PackedKV):
+        if sink is not None:
+            raise RuntimeError('attention maps: the packed K / V cache has no exporting kernel (one hypothesis per sample only)')
         pk = [kv_layer[nm] for nm in names]
         call('tell_attn_decode_packed', n, _ptrs(qs), _longs([int(q.stride(-2)) for q in qs]), _ptrs([c.kc for c in pk]),
              _ptrs([c.vt for c in pk]), _ptrs([c.mask for c in pk]), _ints([c.Sp for c in pk]),
@@ -424,15 +453,29 @@ def attn_decode_all(mods, names, qs, kv_layer, contexts, M, E):
         bk.append(ops._bias_row(m.bias_k, torch.bfloat16))
         bv.append(ops._bias_row(m.bias_v, torch.bfloat16))
     q_sb = [int(q.stride(-2)) for q in qs]
+    if sink is not None:
+        snk, li = sink
+        if beams != 1:
+            raise RuntimeError('attention maps: one hypothesis per sample only')
+        ws = [snk.bufs[li][nm] for nm in names]
+        for w_, s_ in zip(ws, S):
+            assert w_.dtype == torch.float32 and w_.shape == (snk.n_slots, M, s_ + 2) and w_.is_contiguous()
+        lse = torch.empty(n, M, mods[0].num_heads, dtype=torch.float32, device=dev)
+        call('tell_attn_decode_weights', n, _ptrs(qs), _longs(q_sb), _ptrs(ks), _longs(k_ss), _longs(k_sb), _longs(k_sh),
+             _ptrs(vs), _longs(v_ss), _longs(v_sb), _longs(v_sh), _ptrs(masks), _ptrs(bk), _ptrs(bv), 1, _ints(S),
+             _ptrs([a_all[i] for i in range(n)]), _longs([E] * n), M, mods[0].num_heads, beams, lse, _ptrs(ws),
+             _longs([w_.stride(0) for w_ in ws]), _longs([w_.stride(1) for w_ in ws]), snk.slot, snk.n_slots, snk.step_dev)
+        return a_all
     call('tell_attn_decode', n, _ptrs(qs), _longs(q_sb), _ptrs(ks), _longs(k_ss), _longs(k_sb), _longs(k_sh), _ptrs(vs),
          _longs(v_ss), _longs(v_sb), _longs(v_sh), _ptrs(masks), _ptrs(bk), _ptrs(bv), 1, _ints(S),
          _ptrs([a_all[i] for i in range(n)]), _longs([E] * n), M, mods[0].num_heads, beams)
     return a_all
 
 
-def decoder_step(dec, X, contexts, state, kv_cache):
+def decoder_step(dec, X, contexts, state, kv_cache, sink=None):
     """X [1, M, E] bf16 (embedded tokens of this step) -> [1, M, E] bf16 after all layers; the DynamicConv input
-    buffers in `state` are shifted in place."""
+    buffers in `state` are shifted in place.  sink: an AttnSink - every layer's attention launch also exports its
+    head-averaged weights (attn_decode_all); None: the launches of the plain step."""
     M, E = X.shape[1], X.shape[2]
     dev = X.device
     x_bf = X.reshape(M, E)
@@ -491,7 +534,8 @@ def decoder_step(dec, X, contexts, state, kv_cache):
         else:
             _skinny([raw3] * n, E, wq, bq, [q_all[i] for i in range(n)], E, M, E, E, pro=1, gammas=[ln3.weight],
                     betas=[ln3.bias], eps=ln3.eps, stats_out=st3, scale=mods[0].scaling)
-        a_all = attn_decode_all(mods, names, [q_all[i] for i in range(n)], kv_cache[li], contexts, M, E)
+        a_all = attn_decode_all(mods, names, [q_all[i] for i in range(n)], kv_cache[li], contexts, M, E,
+                                sink=None if sink is None else (sink, li))
         raw6 = torch.empty(M, n * E, **f32)
         raw6_bf = torch.empty(M, n * E, **bf) if fold else None     # (problem i's copy lands at columns i E ..: out2_prob)
         _skinny([a_all[i] for i in range(n)], E, [ops.weight(m.out_proj.weight) for m in mods],

@@ -78,7 +78,10 @@ class BaselineGloveModel(Model):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None):
+    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False):
+        if attention:
+            raise ValueError('attention=True: %s decodes with an LSTM decoder; attention maps are exported for the DynamicConv '
+                             'decoders only (its dot attention is not covered)' % type(self).__name__)
         caption_ids, _, contexts = self._forward(self._vectors(context_vectors, metadata), image, caption)
         log_probs, gen_ids = self._generate(caption_ids, contexts)
         return {'gen_ids': gen_ids, 'log_probs': log_probs}
@@ -162,6 +165,7 @@ class TransformerGloveModel(CaptionModel):
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0
 
+    EVAL_ATTENTION = False       # its own forward(): evaluate mode generates without maps (no article pieces to merge either)
     _vectors = staticmethod(BaselineGloveModel._vectors)
     _glove_forward = BaselineGloveModel._forward
 
@@ -181,8 +185,10 @@ class TransformerGloveModel(CaptionModel):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1):
+    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False):
+        if attention:
+            self._check_attention(beam_size)
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size)
-        return {'gen_ids': gen_ids, 'log_probs': log_probs, 'attns': attns}
+        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention)
+        return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)

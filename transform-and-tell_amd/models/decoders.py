@@ -85,7 +85,10 @@ class DynamicConvDecoderLayer(DecoderLayer):
             return res + ops.dropout(h, self.dropout, self.training)
         return self._ln(ln, h, res, self.dropout, self.training)
 
-    def forward(self, X, contexts, incremental_state, contexts_t=None, kv=None, kv_packed=None):
+    def forward(self, X, contexts, incremental_state, contexts_t=None, kv=None, kv_packed=None, attn_sink=None):
+        """attn_sink = (decode.AttnSink, layer index, slot tensor): generation with attention maps on the per-context path -
+        every context's head-averaged weights (tell_attn_avg_weights) go into the sink's device buffer, nothing is copied
+        to the host and nothing is returned in `attns` (that is the legacy need_attn switch, untouched)."""
         tr = self.training
         use_blocks = _BLOCKS and incremental_state is None and blocks.usable(self, X) and X.requires_grad
         if use_blocks:                                                     # :256-266 as one autograd node
@@ -109,7 +112,7 @@ class DynamicConvDecoderLayer(DecoderLayer):
         else:
             handles = (X,) * (nctx + 1)
         grouped = (fused and nctx > 1 and ops.rt.compute_dtype() == torch.bfloat16 and X.dtype == torch.bfloat16 and
-                   not (not tr and self.need_attn))        # (attention-weight export takes the per-context path)
+                   not (not tr and self.need_attn) and attn_sink is None)   # (attention-weight export: the per-context path)
         if grouped:
             # the n attentions only meet at the LayerNorms: their query projections and their output projections each
             # travel as ONE grouped launch (forward, input gradients; the weight gradients join the trainer's queue).
@@ -135,11 +138,13 @@ class DynamicConvDecoderLayer(DecoderLayer):
         for i, name in enumerate(() if grouped else self.context_names):  # :271-352
             a, w = self.context_attns[name](
                 self._pre(self.context_attn_lns[name], handles[i]), contexts[name], contexts[name],
-                key_padding_mask=contexts[name + '_mask'], need_weights=(not tr and self.need_attn),
+                key_padding_mask=contexts[name + '_mask'], need_weights=(not tr and (self.need_attn or attn_sink is not None)),
                 key_t=None if contexts_t is None else contexts_t.get(name),
                 kv=None if kv is None else kv[name])
             outs.append(a if fused else self._post(self.context_attn_lns[name], a, X))
-            if w is not None:
+            if w is not None and attn_sink is not None:
+                attn_sink[0].put(attn_sink[1], name, w, attn_sink[2])
+            if w is not None and not tr and self.need_attn:
                 attns[name] = w.cpu().numpy()
         if fused:
             cat = ops.layer_norm_cat(outs, handles[nctx], [self.context_attn_lns[n] for n in self.context_names],
@@ -207,7 +212,8 @@ class _DynamicConvDecoderBase(Decoder):
             object.__setattr__(self, '_wn_pair_list', pairs)
         return pairs
 
-    def forward(self, prev_target, contexts, incremental_state=None, use_layers=None, kv_cache=None, **kwargs):
+    def forward(self, prev_target, contexts, incremental_state=None, use_layers=None, kv_cache=None, attn_sink=None,
+                **kwargs):
         if self.training and torch.is_grad_enabled():
             ops.wn_prepare(self._wn_pairs())          # every weight-normalised working weight of the step in one launch
         X = self.embedder(prev_target, incremental_state=incremental_state)      # :98  [B,T,E] view
@@ -250,13 +256,15 @@ class _DynamicConvDecoderBase(Decoder):
                     contexts[name + '_mask'] = m.to(torch.uint8).contiguous()
         if not use_layers and decode.usable(self, X, incremental_state, kv_cache):
             # generation: the whole layer stack of this step as weight-streaming launches (decode.py)
-            X = decode.decoder_step(self, X, contexts, incremental_state, kv_cache)
+            X = decode.decoder_step(self, X, contexts, incremental_state, kv_cache, sink=attn_sink)
             return X.transpose(0, 1), {'attn': [], 'inner_states': []}
+        sink_idx = attn_sink.index(X.device) if attn_sink is not None else None
         for i, layer in enumerate(self.layers):
             if not use_layers or i in use_layers:
                 X = ops.grad_ready_marker(X, 'decoder.layers.%d.' % i)    # DP: layer i's gradients are final here
                 X, attn = layer(X, contexts, incremental_state, contexts_t,
-                                None if kv_cache is None else kv_cache[i], None if kv_packed is None else kv_packed[i])
+                                None if kv_cache is None else kv_cache[i], None if kv_packed is None else kv_packed[i],
+                                **({} if attn_sink is None else {'attn_sink': (attn_sink, i, sink_idx)}))
                 inner_states.append(X)
             attns.append(attn)
         if self.normalize:                                                         # :125-126

@@ -85,6 +85,12 @@ class PointerModelBase(CaptionModel):
     def lanes_usable(self):
         return False
 
+    EVAL_ATTENTION = False       # forward() generates through _generate_pointer: no attention maps
+
+    def _check_attention(self, beam_size=1):
+        raise ValueError('attention=True: %s is a pointer model; attention maps are exported for the plain caption models only '
+                         '(the copy attention is not covered)' % type(self).__name__)
+
     def _check_beam(self, beam_size):
         if int(beam_size) > 1:
             raise ValueError('transformer_pointer has no beam search (beam_size %d)' % int(beam_size))
@@ -158,7 +164,9 @@ class PointerModelBase(CaptionModel):
 
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False):
+        if attention:
+            self._check_attention(beam_size)
         self._check_beam(beam_size)
         self._require_masks(context)
         enc = encoded if encoded is not None else self.encode(context, image)

@@ -2,7 +2,7 @@
 on the MI355X path (training forward + loss, greedy generation)."""
 import math
 import os
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import torch
 import torch.nn as nn
@@ -130,8 +130,16 @@ def draw_seed():
     return int(torch.randint(0, 1 << 31, (1,)).item())
 
 
+class AttnMaps(namedtuple('AttnMaps', 'maps steps')):
+    """Third result of the cached generator with attention=True (without: the empty list it always was).
+    maps: {context name: fp32 [B, steps, n_layers, S + 2]} on the device; steps: [B] long, the row's `done_step` - the
+    number of decode steps it took part in, the one that produced its </s> included."""
+    __slots__ = ()
+
+
 class CaptionModel(Model):
     USE_FACES_OBJECTS = False
+    EVAL_ATTENTION = True        # forward() in evaluate mode honours `eval_attention` (commands/evaluate.py attention_maps=True)
     EXTRA_CONTEXTS = ()          # which of ('faces', 'obj') the model feeds to its decoder
 
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
@@ -179,6 +187,26 @@ class CaptionModel(Model):
         if int(beam_size) > 1 and self._sampling() is not None:
             raise ValueError('beam search (beam_size %d) and top-k sampling (sampling_topk %d) do not combine: the reference '
                              'samples without a beam' % (int(beam_size), int(self.sampling_topk)))
+
+    def _check_attention(self, beam_size=1):
+        """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
+        sample (greedy, top-k, nucleus)."""
+        if int(beam_size) > 1:
+            raise ValueError('attention=True: attention maps are exported for greedy / top-k / nucleus generation only, not '
+                             'for beam search (beam_size %d): the slots would have to follow the surviving hypotheses'
+                             % int(beam_size))
+        if not hasattr(self.decoder, 'project_contexts'):
+            raise ValueError('attention=True: %s is an LSTM decoder; attention maps are exported for the DynamicConv '
+                             'decoders only (its dot attention is not covered)' % type(self.decoder).__name__)
+
+    @staticmethod
+    def _attn_output(out, attns):
+        """'attns' (+ 'attn_steps') of an output dict from a generator's third result: an AttnMaps, or the plain list."""
+        if isinstance(attns, AttnMaps):
+            out['attns'], out['attn_steps'] = attns.maps, attns.steps
+        else:
+            out['attns'] = attns
+        return out
 
     def reset_graphs(self):
         """Forget every captured hipGraph of this model (encoders, decode steps); they are re-recorded on next use."""
@@ -351,7 +379,9 @@ class CaptionModel(Model):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`."""
         output_dict, caption_ids, contexts = self._forward_loss(context, image, caption, face_embeds, obj_embeds, encoded)
         if not self.training and self.evaluate_mode:                       # :92-116
-            _, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=getattr(self, 'eval_beam_size', 1))
+            # (eval_attention: commands/evaluate.py's opt-in - the captions come with their attention maps)
+            _, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=getattr(self, 'eval_beam_size', 1),
+                                               **({'attention': True} if getattr(self, 'eval_attention', False) else {}))
             self._forward_generated(output_dict, gen_ids, attns, metadata)
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
@@ -369,7 +399,7 @@ class CaptionModel(Model):
         """:92-116 - what evaluate mode adds to the output once the captions are decoded: ids, text, per-sample BLEU."""
         ids_cpu = gen_ids.cpu()
         output_dict['gen_ids'] = ids_cpu.numpy()
-        output_dict['attns'] = attns
+        self._attn_output(output_dict, attns)
         gen_texts = [self.detokenize(x[x > 1]) for x in ids_cpu]        # :96 "we ignore <s> and <pad>"
         output_dict['generations'] = gen_texts
         if metadata is not None:
@@ -411,11 +441,25 @@ class CaptionModel(Model):
         return ' '.join(str(int(i)) for i in ids if int(i) != 2)
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None):
-        """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`."""
+                 attn_idx=None, beam_size=1, encoded=None, attention=False):
+        """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        attention=True (greedy / top-k / nucleus, DynamicConv decoders): 'attns' is a dict name -> fp32 device tensor
+        [B, steps, n_layers, S_name + 2] of head-averaged attention weights, one row per generated token and decoder layer
+        (steps = gen_ids.shape[1] - 1; columns: the S context positions, the learned bias_k key, the zero key), and
+        'attn_steps' [B] is the number of steps a row took part in, THE STEP THAT PRODUCED ITS </s> INCLUDED (= the column of
+        </s> in gen_ids; `steps` for a row that never ended): maps[b, :attn_steps[b] - 1] are the steps of the words of an ended
+        row, maps[b, attn_steps[b]:] what the static batch computed after it.  The tokens and log-probs are bit for bit those of attention=False.  `caption_attention` turns the maps into the
+        reference's per-word view.  Default: 'attns' is [] on the cached generators."""
+        if attention:
+            self._check_attention(beam_size)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size)
-        return {'gen_ids': gen_ids, 'log_probs': log_probs, 'attns': attns}
+        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention)
+        return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
+
+    def caption_attention(self, batch, gen, bpe=None):
+        """The reference's per-word attention view of `gen = generate(**batch, attention=True)` (attention_maps.py)."""
+        from .attention_maps import caption_attention
+        return caption_attention(self, batch, gen, bpe=bpe)
 
     def lanes_usable(self):
         """Whether `generate_lanes` has a decode loop to interleave: the K/V-cached static-batch generator on a GPU."""
@@ -423,7 +467,7 @@ class CaptionModel(Model):
                 and next(self.parameters()).is_cuda)
 
     @torch.no_grad()
-    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False):
+    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
@@ -431,8 +475,15 @@ class CaptionModel(Model):
         encoders of a group of batches run first (eval mode: no randomness, results identical to `generate`).
         Yields (batch, output) in order.  forward=True: the outputs of `forward` in evaluate mode (loss + captions + per-sample
         BLEU bookkeeping: what commands/evaluate.py consumes) instead of `generate`'s; beam_size then is `eval_beam_size`."""
+        if attention:
+            if forward:
+                raise ValueError('attention=True goes with generate, not with forward=True')
+            self._check_attention(beam_size)
         if forward:
             beam_size = getattr(self, 'eval_beam_size', 1)
+            if getattr(self, 'eval_attention', False) and not self.training and self.evaluate_mode:
+                self._check_attention(beam_size)
+                attention = True
             if self.training or not self.evaluate_mode or not self.lanes_usable():
                 yield from self.generate_stream(batches, forward=True)  # nothing to decode / no static-batch decode loop
                 return
@@ -448,7 +499,7 @@ class CaptionModel(Model):
                     group.append(b)
             if not group:
                 return
-            gens, outs, heads = [], [None] * len(group), []
+            gens, outs, heads, thirds = [], [None] * len(group), [], [None] * len(group)
             for ln, b in enumerate(group):
                 f = {k: v for k, v in b.items() if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds')}
                 if forward:
@@ -463,7 +514,7 @@ class CaptionModel(Model):
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
                     g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln) if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed))
+                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -473,7 +524,8 @@ class CaptionModel(Model):
                             next(gens[ln])
                         except StopIteration as done:
                             lp, ids, attns = done.value
-                            outs[ln] = {'gen_ids': ids, 'log_probs': lp, 'attns': attns}
+                            outs[ln] = self._attn_output({'gen_ids': ids, 'log_probs': lp}, attns)
+                            thirds[ln] = attns
                             live.remove(ln)
             for ln in range(len(group)):
                 ev = torch.cuda.Event()
@@ -482,13 +534,13 @@ class CaptionModel(Model):
             for ln, (b, o) in enumerate(zip(group, outs)):
                 if forward:
                     od, metadata, n = heads[ln]
-                    self._forward_generated(od, o['gen_ids'], o['attns'], metadata)
+                    self._forward_generated(od, o['gen_ids'], thirds[ln], metadata)
                     self.n_samples += n
                     self.n_batches += 1
                     o = od
                 yield b, o
 
-    def generate_stream(self, batches, beam_size=1, forward=False):
+    def generate_stream(self, batches, beam_size=1, forward=False, attention=False):
         """Captions for a sequence of batches (the test-set loop of tell/commands/evaluate.py:118-160) with the frozen
         encoders of batch N+1 launched on their own streams BEFORE the decode loop of batch N is issued - the trainer's
         schedule applied to generation.  Numerics are those of `generate` / `forward` batch by batch: the encoders read
@@ -506,6 +558,11 @@ class CaptionModel(Model):
 
         batches: any iterable of batch dicts (keys of `forward`); forward=True yields `self(**batch)` (evaluate mode:
         loss + generation + metrics) instead of `generate(**batch)`.  Yields (batch, output_dict) in order."""
+        if attention:
+            if forward:
+                raise ValueError('attention=True goes with generate, not with forward=True')
+            self._check_attention(beam_size)
+        gen_kw = {'attention': True} if attention else {}
         it = iter(batches)
         cur = next(it, None)
         enc = None
@@ -520,14 +577,19 @@ class CaptionModel(Model):
             if enc is not None and enc.stale():
                 enc = self.encode(cur['context'], cur['image'])
             extra = {'encoded': enc} if enc is not None else {}
-            out = self(**cur, **extra) if forward else self.generate(**cur, beam_size=beam_size, **extra)
+            out = self(**cur, **extra) if forward else self.generate(**cur, beam_size=beam_size, **extra, **gen_kw)
             yield cur, out
             cur, enc = nxt, ahead
 
     # ---- :399-494 -----------------------------------------------------------------
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
-    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1):
+    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False):
+        if attention:
+            # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
+            # flow with the legacy need_attn export, which stays what it is)
+            self._check_attention(beam_size)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True)
         if not hasattr(self.decoder, 'project_contexts'):
             # a recurrent decoder behind this model class (expt/*/3_lstm_roberta: `lstm_decoder_flattened`): greedy
             # decode that carries the LSTM state.  (The reference's loop feeds such a decoder only the last token with
@@ -553,10 +615,10 @@ class CaptionModel(Model):
             return done.value
 
     @torch.no_grad()
-    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0):
-        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane))
+    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False):
+        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention))
 
-    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None):
+    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -565,13 +627,15 @@ class CaptionModel(Model):
         independent, so every row sees exactly the arithmetic of the reference flow: token ids are
         identical, pad=1 after EOS, output length = 1 + steps until the last row finished.
         sampling_topk > 1: the head's last launch draws from the top k instead (tell_adaptive_logprob_sample), keyed on
-        (seed, row, step) - `seed` (default: drawn now, draw_seed) goes into the stepper's device word before the first step."""
+        (seed, row, step) - `seed` (default: drawn now, draw_seed) goes into the stepper's device word before the first step.
+        attention=True: every step also leaves its head-averaged attention weights in the stepper's sink (step.attn, one slot
+        per step); the third result is then an AttnMaps (maps {name: [B, steps, n_layers, S + 2] fp32}, steps [B]) instead of []."""
         dec = self.decoder
         B = caption_ids.shape[0]
         dev = caption_ids.device
         kv = dec.project_contexts(contexts)
         sampling = self._sampling()
-        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling)
+        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention)
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous()
@@ -632,11 +696,17 @@ class CaptionModel(Model):
                 break
         steps = int(done_step.max())                                          # one sync at the end
         steps = max(steps, 1)
+        attns = []
+        if attention:
+            # slot i of a layer's buffer = step i (the token at ids[:, i + 1]); copied out: the buffers belong to the stepper
+            bufs = step.attn.bufs
+            attns = AttnMaps({n: torch.stack([lb[n][:steps] for lb in bufs], 0).permute(2, 1, 0, 3).contiguous()
+                              for n in bufs[0]}, done_step.clamp(max=steps).clone())
         if fused:                                                             # (the static buffers belong to the stepper)
-            return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), []
-        return lps[:, :steps], ids[:, :steps + 1], []
+            return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
+        return lps[:, :steps], ids[:, :steps + 1], attns
 
-    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None):
+    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False):
         """-> step(i, cur [B,1]) -> (token [B,1], log-prob [B,1]) - or, with topk=k, the k best (tokens [B,1,k],
         log-probs [B,1,k]) of every row - for the cached greedy / beam generators; step.reorder(rows) permutes the
         rows of the incremental state (beam search).
@@ -649,9 +719,19 @@ class CaptionModel(Model):
 
         sample = (k, T): every step draws from the top k at temperature T (AdaptiveSoftmax.sample) with the seed in the
         device word step.seed and the step index from the host (eager) or from the device counter (captured: every replay of
-        the single-step and the multi-step graphs draws fresh numbers); (k, T) is part of the capture's signature."""
+        the single-step and the multi-step graphs draws fresh numbers); (k, T) is part of the capture's signature.
+
+        attention=True: the step also exports the head-averaged attention weights of every (layer, context) into static
+        fp32 buffers [gen_len, B, S + 2] (decode.AttnSink, handed out as step.attn), slot = step index: from the host in an
+        eager step, from the device counter in a captured one (single-step and multi-step graphs alike).  ('attn',) joins
+        the signature only then: the captures without maps are keyed and recorded exactly as before."""
         dec = self.decoder
         names = [n for layer_kv in kv[:1] for n in layer_kv]
+
+        def make_sink(device):
+            from ..decode import AttnSink
+            return AttnSink([{n: torch.zeros(int(gen_len), B, int(pair[0].shape[0]) + 2, dtype=torch.float32, device=device)
+                              for n, pair in lk.items()} for lk in kv], gen_len)
 
         def make_head(seed_dev):
             if sample is not None:
@@ -668,8 +748,12 @@ class CaptionModel(Model):
             seed_word = torch.zeros(1, dtype=torch.int32, device=next(dec.parameters()).device)
             head = make_head(seed_word)
 
+            sink = make_sink(seed_word.device) if attention else None
+
             def eager_step(i, cur):
-                return head(dec({self.index: cur}, contexts, incremental_state=state, kv_cache=kv)[0][:, -1:], int(i))
+                kw = {'attn_sink': sink.at(int(i))} if sink is not None else {}
+                return head(dec({self.index: cur}, contexts, incremental_state=state, kv_cache=kv, **kw)[0][:, -1:], int(i))
+            eager_step.attn = sink
             eager_step.reorder = lambda rows: dec.reorder_incremental_state(state, rows)
             eager_step.seed = seed_word
             return eager_step
@@ -681,6 +765,8 @@ class CaptionModel(Model):
         if sample is not None:                                    # (greedy and beam signatures are unchanged)
             sig = sig + ((('sample', int(sample[0]), float(sample[1])) if len(sample) == 2 else
                           ('nucleus', int(sample[0]), float(sample[1]), float(sample[2]))),)
+        if attention:                                             # (... and so are the sampling ones)
+            sig = sig + (('attn',),)
         cache = self.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -736,6 +822,10 @@ class CaptionModel(Model):
                 h['kv'] = [{n: tuple(static_like(t, layer.context_attns[n]) for t in pair) for n, pair in lk.items()}
                            for lk, layer in zip(kv, dec.layers)]
             # in-graph bookkeeping needs the step's first kernel to be tell_embed_gather_step (it publishes the counter)
+            if attention:
+                if topk:
+                    raise ValueError('attention maps: one hypothesis per sample only (no beam search)')
+                h['attn'] = make_sink(dev)
             h['ig'] = bool(_dec.IN_GRAPH_BOOK and dtype == torch.bfloat16 and _dec.usable(dec, probe, h['state'], kv) and
                            _dec.embed_usable(dec.embedder, h['cur'], h['state']))
         for lk, ls in zip(kv, h['kv']):
@@ -765,7 +855,11 @@ class CaptionModel(Model):
             prev_lane = _dec2.CUR_LANE[0]
             _dec2.CUR_LANE[0] = int(lane)
             try:
-                out = dec({self.index: h['cur']}, h['ctx'], incremental_state=h['state'], kv_cache=h['kv'])
+                kw = {}
+                if attention:
+                    # slot = step index: the host's in an eager step; captured, the counter holds i - 1 (base 1)
+                    kw['attn_sink'] = h['attn'].at(1, sidx) if torch.is_tensor(sidx) else h['attn'].at(int(sidx))
+                out = dec({self.index: h['cur']}, h['ctx'], incremental_state=h['state'], kv_cache=h['kv'], **kw)
                 return head(out[0][:, -1:], sidx)
             finally:
                 _dec2.CUR_LANE[0] = prev_lane
@@ -882,6 +976,7 @@ class CaptionModel(Model):
         step.cur = h['cur']
         step.book = book
         step.seed = h['seed']
+        step.attn = h.get('attn')
         step.counter_out = c_out                                  # (base 1: the offset of step i is i - 1)
         step.back = h['state'].get('_back')                       # ancestor table of the DynamicConv rings, or None
         return step
