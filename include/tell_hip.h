@@ -269,6 +269,26 @@ int tell_loss_bits(const float* x, const int* n_valid, float* out, tell_stream_t
 int tell_beam_update(const int* tk, const float* lp, float* cum, uint8_t* finished, long* seqs, float* lps, long* cur,
                      long* rows, int B, int K, int L, int step, int pad, int eos, float inv_temp, int* back, int n_back,
                      int* counter, const int* step_dev, tell_stream_t stream);
+/* tell_beam_update with a length penalty.  len int32 [B,K], in place: the number of generated tokens
+ * of every hypothesis, eos included (a live candidate of step i has i + 1, a finished one keeps its own); inv_norm fp32
+ * [L + 1], built by the host: inv_norm[0] = 1, inv_norm[l] = float32(float64(l) ** -alpha).  Per sample the K survivors are
+ * the K best of score = (cum[parent] + lp * inv_temp) * inv_norm[len] - ONE fp32 multiply on the raw sum - among the K x K
+ * candidates, lowest candidate index first on ties; cum stays the RAW sum, len is written for the survivors; everything else
+ * (finished, seqs, lps, cur, rows, the ancestor table, counter / step_dev) as tell_beam_update.  The all-ones table gives
+ * tell_beam_update's results bit for bit. */
+int tell_beam_update_norm(const int* tk, const float* lp, float* cum, uint8_t* finished, long* seqs, float* lps, long* cur,
+                          long* rows, int* len, const float* inv_norm, int B, int K, int L, int step, int pad, int eos,
+                          float inv_temp, int* back, int n_back, int* counter, const int* step_dev, tell_stream_t stream);
+/* The ban set of every decode row (no_repeat_ngram_size / min_len).  Step i of a row has the history
+ * h[0 .. i], h[0] = <s>.  With n = ngram >= 1 and i + 1 >= n: for every p in 0 .. i + 1 - n with
+ * h[p .. p + n - 2] == h[i - n + 2 .. i], h[p + n - 1] is banned (n = 1: every token of the history).  i < min_len bans eos.
+ * A finished row (finished[r] != 0) bans nothing.  hist int64 [rows, ld_hist] with L <= 256 columns (beam: seqs as
+ * [B*K, L]; greedy: ids), finished uint8 [rows] or NULL; i = `step`, or *step_dev + 1 when step_dev is given (the device
+ * counter of a captured decode step, as tell_greedy_update / tell_beam_update read it).  out: ban int32 [rows, ld_ban],
+ * ld_ban >= L + 1 (duplicates allowed, no order promised), n_ban int32 [rows]. */
+int tell_decode_ban_list(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
+                         const int* step_dev, int ngram, int min_len, int eos, int* ban, long ld_ban, int* n_ban,
+                         tell_stream_t stream);
 /* buf[i][p][r][:] <- buf[i][p][rows[r]][:] in place for n <= 8 bf16 buffers [planes[i], M, 1024] (HOST arrays); rows[r]
  * must lie inside r's group of K consecutive rows (dynamic.py:338-342 reorder_incremental_state, all layers at once) - for
  * input buffers kept in time order (the layer-by-layer fp32 step); the rings of tell_dynconv_step are never moved. */
@@ -511,6 +531,16 @@ int tell_ce_bwd(const float* logits, long ld, int M, int V, const int* targets, 
 int tell_adaptive_logprob_topk(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
                                int rows, int k, int* tokens, float* lps, tell_stream_t stream);
+/* tell_adaptive_logprob_topk under a ban list per row: ban int32 [rows, ld_ban], n_ban int32 [rows] (tell_decode_ban_list).
+ * The tokens ban[r][0 .. n_ban[r]) have log-prob -inf: they never enter the list.  Every other log-prob is exactly the one
+ * tell_adaptive_logprob_topk returns - the log-sum-exps run over the whole row, nothing is renormalised - under the same
+ * tie rule (lower id first); n_ban[r] = 0 gives its row bit for bit.  If fewer than k tokens remain, the tail of the list is
+ * (-inf, 0x7fffffff).  k = 1..8 (k = 1: the greedy decode under bans); vocab <= 2^18; register and streaming forms as
+ * tell_adaptive_logprob_topk (option argmax_regs). */
+int tell_adaptive_logprob_topk_banned(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                      int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                      int rows, int k, const int* ban, long ld_ban, const int* n_ban, int* tokens,
+                                      float* lps, tell_stream_t stream);
 int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,

@@ -44,7 +44,8 @@ def build_decoder(kind='faces_objects', vocab_size=50265, dim=1024, heads=16, ff
 
 
 def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=25, sampling_topk=1, sampling_temp=1.0,
-                sampling_topp=None, **decoder_kw):
+                sampling_topp=None, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, **decoder_kw):
+    search = dict(beam_len_penalty=beam_len_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_len=min_len)
     if kind in ('pointer', 'pointer_2'):                     # expt/*/a1-a3: transformer_pointer(_2) on the faces decoder
         from .models.pointer import TransformerPointer2Model, TransformerPointerModel
         dec = build_decoder('faces_parallel', **decoder_kw)
@@ -52,10 +53,10 @@ def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=
         return cls(None, dec, AdaptiveLoss(padding_idx=1), weigh_bert=weigh_bert,
                    vocab_size=decoder_kw.get('vocab_size', 50265), resnet=resnet, roberta=roberta,
                    n_bert_layers=n_bert_layers, sampling_topk=sampling_topk, sampling_temp=sampling_temp,
-                   sampling_topp=sampling_topp)
+                   sampling_topp=sampling_topp, **search)
     dec = build_decoder(kind, **decoder_kw)
     cls = {'faces_objects': TransformerFacesObjectModel, 'faces': TransformerFacesModel,
            'faces_parallel': TransformerFacesModel}.get(kind, TransformerFlattenedModel)
     return cls(None, dec, AdaptiveLoss(padding_idx=1), weigh_bert=weigh_bert, vocab_size=decoder_kw.get('vocab_size', 50265),
                resnet=resnet, roberta=roberta, n_bert_layers=n_bert_layers, sampling_topk=sampling_topk,
-               sampling_temp=sampling_temp, sampling_topp=sampling_topp)
+               sampling_temp=sampling_temp, sampling_topp=sampling_topp, **search)

@@ -399,9 +399,28 @@ __device__ constexpr int LPF_CAP[4] = {2, 4, 8, 2};
 __device__ constexpr int LPF_OFF[4] = {0, 2, 6, 14};
 // K = 1: arg-max (token, token_lp); K = 4 / 8: every thread keeps its K best while scanning its registers, the block pops
 // the global best k times (beam search: tokens / lps [rows, k], best first).
-template <int K>
+// BAN (tell_adaptive_logprob_topk_banned): the row's ban list (ban[i][0 .. n_ban[i])) becomes a bitmap over the vocabulary
+// in LDS; a banned token never enters a thread's candidate list.  The test sits behind consider()'s "beats my K-th best"
+// return, which few elements pass, and a row without bans skips the bitmap altogether; maxima, sums and log-probs are
+// those of the whole row either way.  BAN = false is the kernel as it was.
+struct BanArgs { const int* ban; long ld_ban; const int* n_ban; int vocab; };
+extern __shared__ unsigned ban_bits[];
+template <int THREADS>
+__device__ __forceinline__ void ban_stage(const BanArgs& ba, int row, int nb) {
+  const int words = (ba.vocab + 31) >> 5;
+  for (int w = threadIdx.x; w < words; w += THREADS) ban_bits[w] = 0u;
+  __syncthreads();
+  for (int e = threadIdx.x; e < nb; e += THREADS) {
+    const int t = ba.ban[(long)row * ba.ld_ban + e];
+    if (t >= 0 && t < ba.vocab) atomicOr(&ban_bits[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+}
+// (the register-resident kernel takes `ba` as a trailing argument that BAN = false never reads: its code stays the kernel's
+//  own, not an inlined body - this is the launch every greedy and beam step ends with)
+template <int K, bool BAN>
 __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
-                                                            float* __restrict__ lps) {
+                                                            float* __restrict__ lps, BanArgs ba) {
   __shared__ float red[4][16];
   __shared__ float best_v[16];
   __shared__ int best_i[16];
@@ -415,6 +434,8 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
     rowp[c + 1] = c < p.n_tails ? p.tail[c] + (long)i * p.ld_tail[c] : rowp[0];
     n[c + 1] = c < p.n_tails ? p.tail_n[c] : 0;
   }
+  int nb = 0;                                          // (requested before the row: its wait does not cover the row's loads)
+  if (BAN) { nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb); }
   typedef float f4 __attribute__((ext_vector_type(4)));
   f4 x[16];
 #pragma unroll
@@ -431,6 +452,7 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
       }
       x[LPF_OFF[s] + q] = v;
     }
+  if (BAN && nb > 0) ban_stage<1024>(ba, i, nb);       // (nb is uniform over the workgroup)
   float mx[4], sm[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -480,6 +502,7 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
   auto better = [](float v, int j, float w, int m) { return v > w || (v == w && j < m); };
   auto consider = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
+    if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
     tv[K - 1] = v; ti[K - 1] = j;
 #pragma unroll
     for (int q = K - 1; q > 0; --q)
@@ -548,9 +571,9 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
 // Top-k variant for beam search: per row the k best (log-prob, token) pairs of the adaptive softmax, sorted best
 // first, without materialising [rows, vocab] (a beam of k only ever needs each hypothesis' own k best tokens).
 // Every thread keeps its k best in registers while streaming the row; the block then pops the global best k times.
-template <int K>
-__global__ __launch_bounds__(256) void logprob_topk_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
-                                                           float* __restrict__ lps) {
+template <int K, bool BAN>
+__device__ __forceinline__ void logprob_topk_body(const LogProbArgs& p, int k, int* __restrict__ tokens,
+                                                  float* __restrict__ lps, const BanArgs& ba) {
   __shared__ float red[4];
   __shared__ float best_v[4];
   __shared__ int best_i[4];
@@ -561,8 +584,14 @@ __global__ __launch_bounds__(256) void logprob_topk_kernel(LogProbArgs p, int k,
 #pragma unroll
   for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
   auto better = [](float v, int j, float w, int m) { return v > w || (v == w && j < m); };
+  int nb = 0;
+  if (BAN) {
+    nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb);
+    if (nb > 0) ban_stage<256>(ba, i, nb);             // (nb is uniform over the workgroup)
+  }
   auto push = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
+    if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
     tv[K - 1] = v; ti[K - 1] = j;
 #pragma unroll
     for (int q = K - 1; q > 0; --q)
@@ -618,6 +647,16 @@ __global__ __launch_bounds__(256) void logprob_topk_kernel(LogProbArgs p, int k,
     }
   }
 }
+template <int K>
+__global__ __launch_bounds__(256) void logprob_topk_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
+                                                           float* __restrict__ lps) {
+  logprob_topk_body<K, false>(p, k, tokens, lps, BanArgs{nullptr, 0, nullptr, 0});
+}
+template <int K>
+__global__ __launch_bounds__(256) void logprob_topk_banned_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
+                                                                  float* __restrict__ lps, BanArgs ba) {
+  logprob_topk_body<K, true>(p, k, tokens, lps, ba);
+}
 extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c0, int n_tails,
                                           const float* tail0, long ld0, int n0, const float* tail1, long ld1,
                                           int n1, const float* tail2, long ld2, int n2, int rows, int k,
@@ -638,13 +677,50 @@ extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c
   const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
   if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
       (n_tails < 3 || n2 <= 2 * 4096)) {
-    if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps);
-    else hipLaunchKernelGGL((logprob_regs_kernel<8>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps);
+    if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps, BanArgs{});
+    else hipLaunchKernelGGL((logprob_regs_kernel<8, false>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps, BanArgs{});
     return tell_check_launch("logprob_topk (registers)");
   }
   if (k <= 4) hipLaunchKernelGGL((logprob_topk_kernel<4>), dim3(rows), dim3(256), 0, stream, p, k, tokens, lps);
   else hipLaunchKernelGGL((logprob_topk_kernel<8>), dim3(rows), dim3(256), 0, stream, p, k, tokens, lps);
   return tell_check_launch("logprob_topk");
+}
+
+// tell_adaptive_logprob_topk with a ban list per row (include/tell_hip.h): ban int32 [rows, ld_ban], n_ban int32 [rows].
+extern "C" int tell_adaptive_logprob_topk_banned(const float* head, long ld_head, int c0, int n_tails,
+                                                 const float* tail0, long ld0, int n0, const float* tail1, long ld1,
+                                                 int n1, const float* tail2, long ld2, int n2, int rows, int k,
+                                                 const int* ban, long ld_ban, const int* n_ban, int* tokens, float* lps,
+                                                 hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk_banned: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_banned: 1 <= k <= 8");
+  TELL_REQUIRE(ban && n_ban && ld_ban >= 1, "logprob_topk_banned: ban [rows, ld_ban] and n_ban [rows]");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  BanArgs ba;
+  ba.ban = ban; ba.ld_ban = ld_ban; ba.n_ban = n_ban;
+  ba.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(ba.vocab > 0 && ba.vocab <= (1 << 18), "logprob_topk_banned: vocab <= 2^18 (the ban bitmap: 32 KB of LDS)");
+  const size_t lds = (size_t)((ba.vocab + 31) >> 5) * sizeof(unsigned);
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ba);
+    else hipLaunchKernelGGL((logprob_regs_kernel<8, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ba);
+    return tell_check_launch("logprob_topk_banned (registers)");
+  }
+  if (k <= 4) hipLaunchKernelGGL((logprob_topk_banned_kernel<4>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ba);
+  else hipLaunchKernelGGL((logprob_topk_banned_kernel<8>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ba);
+  return tell_check_launch("logprob_topk_banned");
 }
 
 extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails,
@@ -667,7 +743,8 @@ extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int
   const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
   if (!log_probs && regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
       (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096)) {
-    hipLaunchKernelGGL((logprob_regs_kernel<1>), dim3(rows), dim3(1024), 0, stream, p, 1, (int*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL((logprob_regs_kernel<1, false>), dim3(rows), dim3(1024), 0, stream, p, 1, (int*)nullptr, (float*)nullptr,
+                       BanArgs{});
     return tell_check_launch("logprob_argmax (registers)");
   }
   hipLaunchKernelGGL(logprob_argmax_kernel, dim3(rows), dim3(1024), 0, stream, p);

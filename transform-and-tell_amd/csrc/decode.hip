@@ -1670,13 +1670,18 @@ extern "C" int tell_embed_lookup_step(const long* ids, int M, const float* table
 // cum[parent] + lp[parent][m] (lowest flat index wins a tie), the surviving sequences / per-token log-probs gathered
 // by parent and extended, the parent ROW of every surviving hypothesis for the state reorder, the next input tokens.
 // One 64-thread workgroup per sample; K <= 8.  Thirty-five elementwise / gather / top-k launches per token before.
-__global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__ tk, const float* __restrict__ lp,
-                                                         float* __restrict__ cum, uint8_t* __restrict__ finished,
-                                                         long* __restrict__ seqs, float* __restrict__ lps,
-                                                         long* __restrict__ cur, long* __restrict__ rows, int K, int L,
-                                                         int step_host, int pad, int eos, float inv_temp, int* back, int n_back,
-                                                         int M, int* counter, const int* step_dev) {
+// NORM (tell_beam_update_norm): the candidates are ranked by cum * inv_norm[len] - len = step + 1 for a live candidate, the
+// frozen length of a finished one - while cum stays the raw sum; the survivors' lengths are written back.
+template <bool NORM>
+__device__ __forceinline__ void beam_update_body(const int* __restrict__ tk, const float* __restrict__ lp,
+                                                 float* __restrict__ cum, uint8_t* __restrict__ finished,
+                                                 long* __restrict__ seqs, float* __restrict__ lps,
+                                                 long* __restrict__ cur, long* __restrict__ rows, int K, int L,
+                                                 int step_host, int pad, int eos, float inv_temp, int* back, int n_back,
+                                                 int M, int* counter, const int* step_dev, int* __restrict__ len,
+                                                 const float* __restrict__ inv_norm) {
   const int step = step_dev ? *step_dev + 1 : step_host;      // (in a captured step: the registered counter holds step - 1)
+  __shared__ int s_len[8];
   __shared__ long s_seq[8 * 256];
   __shared__ float s_lp[8 * 256];
   __shared__ int s_parent[8], s_tok[8];
@@ -1705,9 +1710,16 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__
     token = was_fin ? pad : tk[((long)b * K + j) * K + m];
     score = cum[b * K + j] + l;
   }
+  float rank = score;
+  int ln = 0;
+  if (NORM && t < K * K) {
+    ln = was_fin ? len[b * K + j] : step + 1;
+    ln = ln < 0 ? 0 : (ln > L ? L : ln);
+    rank = score * inv_norm[ln];
+  }
   bool taken = false;
   for (int r = 0; r < K; ++r) {
-    float bv = taken ? -INFINITY : score;
+    float bv = taken ? -INFINITY : rank;
     int bi = taken || t >= K * K ? 0x7fffffff : t;
     if (bv != bv) { bv = -INFINITY; }                       // (a NaN score never wins)
     for (int o = 32; o > 0; o >>= 1) {
@@ -1721,6 +1733,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__
       s_tok[r] = token;
       s_fin[r] = (was_fin || token == eos) ? 1 : 0;
       s_dlp[r] = was_fin ? 0.f : score - cum[b * K + j];
+      if (NORM) s_len[r] = ln;
     }
   }
   __syncthreads();
@@ -1744,6 +1757,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__
     finished[b * K + t] = s_fin[t];
     cur[b * K + t] = s_tok[t];
     rows[b * K + t] = (long)b * K + s_parent[t];
+    if (NORM) len[b * K + t] = s_len[t];
   }
   // slot r now holds a child of slot parent[r]: one step ago it sat there, j steps ago where the parent sat j - 1 steps ago
   if (back)
@@ -1752,6 +1766,25 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__
       back[(long)j * M + b * K + r] = j == 0 ? b * K + s_parent[r] : s_back[(j - 1) * K + s_parent[r]];
     }
   if (counter && b == 0 && t == 0) *counter = step;            // position offset of the NEXT replay of a captured step: (step + 1) - 1
+}
+__global__ __launch_bounds__(64) void beam_update_kernel(const int* __restrict__ tk, const float* __restrict__ lp,
+                                                         float* __restrict__ cum, uint8_t* __restrict__ finished,
+                                                         long* __restrict__ seqs, float* __restrict__ lps,
+                                                         long* __restrict__ cur, long* __restrict__ rows, int K, int L,
+                                                         int step_host, int pad, int eos, float inv_temp, int* back, int n_back,
+                                                         int M, int* counter, const int* step_dev) {
+  beam_update_body<false>(tk, lp, cum, finished, seqs, lps, cur, rows, K, L, step_host, pad, eos, inv_temp, back, n_back, M,
+                          counter, step_dev, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void beam_update_norm_kernel(const int* __restrict__ tk, const float* __restrict__ lp,
+                                                              float* __restrict__ cum, uint8_t* __restrict__ finished,
+                                                              long* __restrict__ seqs, float* __restrict__ lps,
+                                                              long* __restrict__ cur, long* __restrict__ rows, int K, int L,
+                                                              int step_host, int pad, int eos, float inv_temp, int* back,
+                                                              int n_back, int M, int* counter, const int* step_dev,
+                                                              int* __restrict__ len, const float* __restrict__ inv_norm) {
+  beam_update_body<true>(tk, lp, cum, finished, seqs, lps, cur, rows, K, L, step_host, pad, eos, inv_temp, back, n_back, M,
+                         counter, step_dev, len, inv_norm);
 }
 // tk int32 / lp fp32 [B,K,K] (the K best continuations of every hypothesis, best first), cum fp32 [B,K], finished uint8
 // [B,K], seqs int64 [B,K,L], lps fp32 [B,K,L-1] - all updated in place -, cur int64 [B*K] (next input tokens), rows
@@ -1768,6 +1801,74 @@ extern "C" int tell_beam_update(const int* tk, const float* lp, float* cum, uint
   hipLaunchKernelGGL(beam_update_kernel, dim3(B), dim3(64), 0, stream, tk, lp, cum, finished, seqs, lps, cur, rows, K, L,
                      step, pad, eos, inv_temp, back, back ? n_back : 0, B * K, counter, step_dev);
   return tell_check_launch("beam_update");
+}
+
+// tell_beam_update with a length penalty: len int32 [B,K] (in place: generated tokens of every hypothesis, eos included),
+// inv_norm fp32 [L + 1] (inv_norm[l] = l^-alpha, inv_norm[0] = 1); everything else as tell_beam_update.
+extern "C" int tell_beam_update_norm(const int* tk, const float* lp, float* cum, uint8_t* finished, long* seqs, float* lps,
+                                     long* cur, long* rows, int* len, const float* inv_norm, int B, int K, int L, int step,
+                                     int pad, int eos, float inv_temp, int* back, int n_back, int* counter,
+                                     const int* step_dev, hipStream_t stream) {
+  TELL_REQUIRE(B > 0 && K >= 1 && K <= 8 && L >= 2 && L <= 256 && (step_dev || (step >= 0 && step + 1 < L)), "beam_update_norm: K <= 8, L <= 256");
+  TELL_REQUIRE(!back || (n_back >= 1 && n_back <= 31), "beam_update_norm: ancestor table of 1 .. 31 steps");
+  TELL_REQUIRE(len && inv_norm, "beam_update_norm: len [B,K] and inv_norm [L + 1]");
+  hipLaunchKernelGGL(beam_update_norm_kernel, dim3(B), dim3(64), 0, stream, tk, lp, cum, finished, seqs, lps, cur, rows, K, L,
+                     step, pad, eos, inv_temp, back, back ? n_back : 0, B * K, counter, step_dev, len, inv_norm);
+  return tell_check_launch("beam_update_norm");
+}
+
+// ------------------------------------------------------------------ decoding constraints: the ban set of every row
+// Step i of a row with history h[0 .. i] (h[0] = <s>): with n = ngram > 0 and i + 1 >= n, every p in 0 .. i + 1 - n whose
+// n - 1 tokens h[p .. p + n - 2] equal the last n - 1 tokens h[i - n + 2 .. i] bans h[p + n - 1] (n = 1: every token of the
+// history); i < min_len bans eos; a finished row bans nothing.  One wave per row: lane l tests p = l, l + 64, ..; the hits
+// of a round are appended in lane order (duplicates stay).
+__global__ __launch_bounds__(64) void decode_ban_list_kernel(const long* __restrict__ hist, long ld_hist, int L,
+                                                             const uint8_t* __restrict__ finished, int step_host,
+                                                             const int* step_dev, int ngram, int min_len, int eos,
+                                                             int* __restrict__ ban, long ld_ban, int* __restrict__ n_ban) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  int step = step_dev ? *step_dev + 1 : step_host;
+  step = step < 0 ? 0 : (step > L - 1 ? L - 1 : step);
+  if (finished && finished[row]) {
+    if (lane == 0) n_ban[row] = 0;
+    return;
+  }
+  const long* h = hist + (long)row * ld_hist;
+  int* out = ban + (long)row * ld_ban;
+  int count = 0;
+  if (ngram >= 1 && step + 1 >= ngram) {
+    const int np = step + 2 - ngram;
+    long suf[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) suf[q] = q < ngram - 1 ? h[step - ngram + 2 + q] : 0;
+    for (int p0 = 0; p0 < np; p0 += 64) {
+      const int p = p0 + lane;
+      bool match = p < np;
+#pragma unroll
+      for (int q = 0; q < 7; ++q)
+        if (q < ngram - 1 && match) match = h[p + q] == suf[q];
+      const unsigned long long hits = __ballot(match);
+      if (match) out[count + __popcll(hits & ((1ull << lane) - 1ull))] = (int)h[p + ngram - 1];
+      count += __popcll(hits);
+    }
+  }
+  if (lane == 0) {
+    if (step < min_len) out[count++] = eos;
+    n_ban[row] = count;
+  }
+}
+// hist int64 [rows, ld_hist] (L valid columns: beam `seqs` as [B*K, L], the greedy `ids`), finished uint8 [rows] or NULL,
+// step = `step`, or *step_dev + 1 inside a captured step; ban int32 [rows, ld_ban >= L + 1], n_ban int32 [rows].
+extern "C" int tell_decode_ban_list(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
+                                    const int* step_dev, int ngram, int min_len, int eos, int* ban, long ld_ban, int* n_ban,
+                                    hipStream_t stream) {
+  TELL_REQUIRE(rows > 0 && L >= 1 && L <= 256 && ld_hist >= L, "decode_ban_list: history [rows, L <= 256]");
+  TELL_REQUIRE(step_dev || (step >= 0 && step < L), "decode_ban_list: 0 <= step < L");
+  TELL_REQUIRE(ngram >= 0 && ngram <= 8 && min_len >= 0, "decode_ban_list: no_repeat_ngram_size 0 .. 8, min_len >= 0");
+  TELL_REQUIRE(ld_ban >= L + 1, "decode_ban_list: ld_ban >= L + 1");
+  hipLaunchKernelGGL(decode_ban_list_kernel, dim3(rows), dim3(64), 0, stream, hist, ld_hist, L, finished, step, step_dev, ngram,
+                     min_len, eos, ban, ld_ban, n_ban);
+  return tell_check_launch("decode_ban_list");
 }
 
 // Rows of the DynamicConv input buffers follow their hypotheses (dynamic.py:338-342 reorder_incremental_state):

@@ -208,13 +208,16 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
     -> (token int32 [N], log-prob fp32 [N], None); topk = k > 0 (beam search): the k best of every row, best first,
     (tokens int32 [N,k], log-probs fp32 [N,k], None); sample = (k, inv_temp, seed_dev, row_ids, step): the last launch is
-    the top-k draw instead of the arg-max (ops.logprob_sample)."""
+    the top-k draw instead of the arg-max (ops.logprob_sample); ban = (ban, n_ban) with topk: the last launch is
+    tell_adaptive_logprob_topk_banned (ops.logprob_topk)."""
+    if ban is not None and (not topk or sample is not None):
+        raise ValueError('head_step: a ban list goes with topk = k >= 1')
     N, E = x2.shape
     dev = x2.device
     c0, n_tails = cutoffs[0], len(tails) // 2
@@ -258,11 +261,7 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None):
         if sample is not None:
             return ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample)
         if topk:
-            tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
-            lps = torch.empty(N, topk, dtype=torch.float32, device=dev)
-            call('tell_adaptive_logprob_topk', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-                 ns[2], N, int(topk), tokens, lps)
-            return tokens, lps, None
+            return ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban)
         token = torch.empty(N, dtype=torch.int32, device=dev)
         token_lp = torch.empty(N, dtype=torch.float32, device=dev)
         call('tell_adaptive_logprob_argmax', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
@@ -301,11 +300,7 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None):
     if sample is not None:
         return ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample)
     if topk:
-        tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
-        lps = torch.empty(N, topk, dtype=torch.float32, device=dev)
-        call('tell_adaptive_logprob_topk', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-             ns[2], N, int(topk), tokens, lps)
-        return tokens, lps, None
+        return ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban)
     token = torch.empty(N, dtype=torch.int32, device=dev)
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
     call('tell_adaptive_logprob_argmax', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],

@@ -9,15 +9,31 @@ import math
 import torch
 
 from .. import ops
-from .transformer import CaptionModel, Model, check_sampling, draw_seed
+from .transformer import CaptionModel, Model, check_beam_options, check_sampling, draw_seed
+
+
+def _refuse_search_options(model, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, n_best=1):
+    """The LSTM decoders' step has its own decision launch: the search options of the cached DynamicConv generator
+     are refused here unless they are at their defaults."""
+    opts = check_beam_options(beam_len_penalty, no_repeat_ngram_size, min_len)
+    used = ['%s=%r' % (k, v) for k, v in zip(('beam_len_penalty', 'no_repeat_ngram_size', 'min_len'), opts) if v]
+    if isinstance(n_best, bool) or not isinstance(n_best, int) or n_best < 1:
+        raise ValueError('n_best must be an integer >= 1 (got %r)' % (n_best,))
+    if n_best != 1:
+        used.append('n_best=%r' % (n_best,))
+    if used:
+        raise ValueError('%s: %s decodes with an LSTM decoder; the search options cover the cached DynamicConv generator '
+                         'only' % (' / '.join(used), type(model).__name__))
 
 
 @Model.register('baseline_glove')
 class BaselineGloveModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
-                 weigh_bert=False, initializer=None, resnet=None, sampling_topp=None):
+                 weigh_bert=False, initializer=None, resnet=None, sampling_topp=None, beam_len_penalty=0.0,
+                 no_repeat_ngram_size=0, min_len=0):
         super().__init__(vocab)
+        _refuse_search_options(self, beam_len_penalty, no_repeat_ngram_size, min_len)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
         if resnet is None:
@@ -78,7 +94,8 @@ class BaselineGloveModel(Model):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False):
+    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1):
+        _refuse_search_options(self, n_best=n_best)
         if attention:
             raise ValueError('attention=True: %s decodes with an LSTM decoder; attention maps are exported for the DynamicConv '
                              'decoders only (its dot attention is not covered)' % type(self).__name__)
@@ -150,7 +167,8 @@ class TransformerGloveModel(CaptionModel):
 
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024, dropout=0.1,
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
-                 use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None):
+                 use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None,
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -161,6 +179,9 @@ class TransformerGloveModel(CaptionModel):
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
         self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
         self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
+        self.beam_len_penalty, self.no_repeat_ngram_size, self.min_len = check_beam_options(
+            beam_len_penalty, no_repeat_ngram_size, min_len)
+        self._check_options()
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0
@@ -185,10 +206,12 @@ class TransformerGloveModel(CaptionModel):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False):
+    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1):
         if attention:
             self._check_attention(beam_size)
+        self._check_options(beam_size, attention, n_best)
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention)
+        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention,
+                                                   **({'n_best': n_best} if n_best != 1 else {}))
         return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)

@@ -43,6 +43,7 @@ class PointerModelBase(CaptionModel):
     USE_FACES_OBJECTS = True
     EXTRA_CONTEXTS = ('faces',)
     COPY_VARIANT = 1
+    SEARCH_OPTIONS = False         # the decode step ends in the copy decision: the search options are out of scope
     STEP_GRAPH = False             # the loss may be None (no copy target in the batch): the trainer stays eager
     # the trainer's shape buckets would pad the article with pad ids: transformer_pointer_2's reduced vocabulary counts
     # every id of the context, so padding the graphs need (and these models do not capture) would change its loss
@@ -51,12 +52,14 @@ class PointerModelBase(CaptionModel):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
-                 model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None):
+                 model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
         if sampling_topk != 1 and sampling_topp is None:       # (with sampling_topp: the generated token is a nucleus draw)
             raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
         super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
                          model_name, namespace, index, padding_value, use_context, sampling_topk, sampling_temp,
-                         weigh_bert, initializer, resnet, roberta, n_bert_layers, sampling_topp)
+                         weigh_bert, initializer, resnet, roberta, n_bert_layers, sampling_topp,
+                         beam_len_penalty, no_repeat_ngram_size, min_len)   # (refused unless at their defaults: SEARCH_OPTIONS)
         if weigh_bert:
             self.bert_weight_2 = nn.Parameter(torch.rand(n_bert_layers))      # :61-62
         self.batch_history = defaultdict(float)        # summed on the device (0-d tensors); floats once get_metrics reads
@@ -164,10 +167,11 @@ class PointerModelBase(CaptionModel):
 
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1):
         if attention:
             self._check_attention(beam_size)
         self._check_beam(beam_size)
+        self._check_options(beam_size, attention, n_best)
         self._require_masks(context)
         enc = encoded if encoded is not None else self.encode(context, image)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, None, enc)

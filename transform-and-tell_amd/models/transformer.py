@@ -94,6 +94,42 @@ def check_sampling(sampling_topk, sampling_temp, sampling_topp=None):
     return int(sampling_topk), float(sampling_temp)
 
 
+MAX_NO_REPEAT_NGRAM = 8         # tell_decode_ban_list's longest n-gram
+DEFAULT_GEN_LEN = 100           # `_generate`'s gen_len: what the constructor checks min_len against
+
+
+def check_beam_options(beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, gen_len=DEFAULT_GEN_LEN):
+    """The search options of the cached generators: `beam_len_penalty` alpha >= 0 (score =
+    sum of log-probs * len ** -alpha; beam search), `no_repeat_ngram_size` 0 (off) or 1..8, `min_len` 0..gen_len - 1 (no
+    </s> before that step) - the last two for greedy and beam search.  -> (alpha, n, min_len); ValueError otherwise."""
+    a = beam_len_penalty
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) < float('inf'):
+        raise ValueError('beam_len_penalty must be a finite number >= 0 (got %r)' % (a,))
+    n = no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or not 0 <= int(n) <= MAX_NO_REPEAT_NGRAM:
+        raise ValueError('no_repeat_ngram_size must be 0 (off) or an integer in 1..%d (got %r)' % (MAX_NO_REPEAT_NGRAM, n))
+    m = min_len
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or int(m) != m or not 0 <= int(m) <= int(gen_len) - 1:
+        raise ValueError('min_len must be an integer in 0..%d (gen_len - 1; got %r)' % (int(gen_len) - 1, m))
+    return float(a), int(n), int(m)
+
+
+def inv_norm_table(alpha, L):
+    """The length-penalty table of tell_beam_update_norm: fp32 [L + 1], [0] = 1, [l] = float32(float64(l) ** -alpha)."""
+    import numpy as np
+    t = np.ones(int(L) + 1, dtype=np.float32)
+    t[1:] = (np.arange(1, int(L) + 1, dtype=np.float64) ** -float(alpha)).astype(np.float32)
+    return torch.from_numpy(t)
+
+
+class DecodeInfo(list):
+    """Third result of the cached generators without attention maps: the empty list it always was, carrying what
+    `generate` reports beside the best hypothesis - scores [B] (beam: the normalised score of hypothesis 0) and, with
+    n_best > 1, nbest = (ids [B, n, L], log_probs [B, n, L - 1], scores [B, n]), best first."""
+    scores = None
+    nbest = None
+
+
 def nucleus_definition(lp, temp, topp, topk=0, u=None):
     """The definition of nucleus sampling (include/tell_hip.h tell_adaptive_logprob_nucleus, steps 1-4) on one row of
     log-probs, in fp64 on the CPU - what the kernel is tested against.  lp: [V] log-probs; temp = T; topp = p; topk = 0 or
@@ -145,7 +181,8 @@ class CaptionModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024,
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
-                 initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None):
+                 initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -161,6 +198,9 @@ class CaptionModel(Model):
         self.evaluate_mode = evaluate_mode
         self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
         self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
+        self.beam_len_penalty, self.no_repeat_ngram_size, self.min_len = check_beam_options(
+            beam_len_penalty, no_repeat_ngram_size, min_len)
+        self._check_options()
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -188,6 +228,38 @@ class CaptionModel(Model):
             raise ValueError('beam search (beam_size %d) and top-k sampling (sampling_topk %d) do not combine: the reference '
                              'samples without a beam' % (int(beam_size), int(self.sampling_topk)))
 
+    SEARCH_OPTIONS = True        # the class decodes through the cached generator below (False: the options are refused)
+
+    def _search_options(self, gen_len=DEFAULT_GEN_LEN):
+        """-> (alpha, n, min_len) of the model's attributes, checked; None when all three are at their defaults."""
+        opts = check_beam_options(getattr(self, 'beam_len_penalty', 0.0), getattr(self, 'no_repeat_ngram_size', 0),
+                                  getattr(self, 'min_len', 0), gen_len)
+        return None if opts == (0.0, 0, 0) else opts
+
+    def _check_options(self, beam_size=1, attention=False, n_best=1, gen_len=DEFAULT_GEN_LEN):
+        """What the search options and n_best combine with: the arg-max / beam decode of the cached DynamicConv generator -
+        no sampling, no attention maps, not the LSTM decoders nor the copy models."""
+        if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= max(int(beam_size), 1):
+            raise ValueError('n_best must be an integer in 1..beam_size (got n_best=%r with beam_size=%d)'
+                             % (n_best, int(beam_size)))
+        opts = self._search_options(gen_len)
+        used = [name for name, v in zip(('beam_len_penalty', 'no_repeat_ngram_size', 'min_len'), opts or ()) if v]
+        if n_best > 1:
+            used.append('n_best')
+        if not used:
+            return None
+        what = ' / '.join('%s=%r' % (u, n_best if u == 'n_best' else getattr(self, u)) for u in used)
+        if getattr(self, 'sampling_topp', None) is not None or int(getattr(self, 'sampling_topk', 1)) > 1:
+            raise ValueError('%s and sampling (sampling_topk %r, sampling_topp %r) do not combine: the search options '
+                             'apply to the arg-max and beam decodes' % (what, self.sampling_topk, self.sampling_topp))
+        if attention:
+            raise ValueError('%s and attention=True do not combine: attention maps are exported without search options'
+                             % what)
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
+                             'search options cover the cached DynamicConv generator only' % (what, type(self).__name__))
+        return opts
+
     def _check_attention(self, beam_size=1):
         """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
         sample (greedy, top-k, nucleus)."""
@@ -205,7 +277,13 @@ class CaptionModel(Model):
         if isinstance(attns, AttnMaps):
             out['attns'], out['attn_steps'] = attns.maps, attns.steps
         else:
-            out['attns'] = attns
+            out['attns'] = [] if isinstance(attns, DecodeInfo) else attns
+        if torch.is_tensor(out.get('log_probs')):
+            # 'scores': the hypothesis' score - the (tempered) log-prob sum; beam search: normalised by beam_len_penalty
+            info = attns if isinstance(attns, DecodeInfo) else None
+            out['scores'] = info.scores if info is not None and info.scores is not None else out['log_probs'].sum(-1)
+            if info is not None and info.nbest is not None:
+                out['gen_ids_nbest'], out['log_probs_nbest'], out['scores_nbest'] = info.nbest
         return out
 
     def reset_graphs(self):
@@ -441,8 +519,11 @@ class CaptionModel(Model):
         return ' '.join(str(int(i)) for i in ids if int(i) != 2)
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        'scores' [B]: the score of every caption (sum of its log-probs; beam search with `beam_len_penalty` alpha: * len ** -alpha).
+        n_best = n (2..beam_size): also 'gen_ids_nbest' [B, n, L], 'log_probs_nbest' [B, n, L - 1], 'scores_nbest' [B, n] - the
+        n best hypotheses of the beam, best first ('gen_ids' / 'log_probs' stay hypothesis 0).
         attention=True (greedy / top-k / nucleus, DynamicConv decoders): 'attns' is a dict name -> fp32 device tensor
         [B, steps, n_layers, S_name + 2] of head-averaged attention weights, one row per generated token and decoder layer
         (steps = gen_ids.shape[1] - 1; columns: the S context positions, the learned bias_k key, the zero key), and
@@ -452,8 +533,10 @@ class CaptionModel(Model):
         reference's per-word view.  Default: 'attns' is [] on the cached generators."""
         if attention:
             self._check_attention(beam_size)
+        self._check_options(beam_size, attention, n_best)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention)
+        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
+                                                   **({'n_best': n_best} if n_best != 1 else {}))
         return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
 
     def caption_attention(self, batch, gen, bpe=None):
@@ -467,7 +550,7 @@ class CaptionModel(Model):
                 and next(self.parameters()).is_cuda)
 
     @torch.no_grad()
-    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False):
+    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
@@ -488,6 +571,7 @@ class CaptionModel(Model):
                 yield from self.generate_stream(batches, forward=True)  # nothing to decode / no static-batch decode loop
                 return
         self._check_beam(beam_size)
+        self._check_options(beam_size, attention, n_best)
         it = iter(batches)
         main = torch.cuda.current_stream()
         lane_streams = [streams.get('decode_lane_%d' % i) for i in range(lanes)]
@@ -513,7 +597,7 @@ class CaptionModel(Model):
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln) if beam_size > 1 else
+                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best) if beam_size > 1 else
                          self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention))
                 gens.append(g)
             live = list(range(len(group)))
@@ -540,7 +624,7 @@ class CaptionModel(Model):
                     o = od
                 yield b, o
 
-    def generate_stream(self, batches, beam_size=1, forward=False, attention=False):
+    def generate_stream(self, batches, beam_size=1, forward=False, attention=False, n_best=1):
         """Captions for a sequence of batches (the test-set loop of tell/commands/evaluate.py:118-160) with the frozen
         encoders of batch N+1 launched on their own streams BEFORE the decode loop of batch N is issued - the trainer's
         schedule applied to generation.  Numerics are those of `generate` / `forward` batch by batch: the encoders read
@@ -563,6 +647,10 @@ class CaptionModel(Model):
                 raise ValueError('attention=True goes with generate, not with forward=True')
             self._check_attention(beam_size)
         gen_kw = {'attention': True} if attention else {}
+        if n_best != 1:
+            if forward:
+                raise ValueError('n_best goes with generate, not with forward=True')
+            gen_kw['n_best'] = n_best
         it = iter(batches)
         cur = next(it, None)
         enc = None
@@ -584,7 +672,8 @@ class CaptionModel(Model):
     # ---- :399-494 -----------------------------------------------------------------
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
-    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False):
+    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1):
+        opts = self._check_options(beam_size, attention, n_best, gen_len)
         if attention:
             # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
             # flow with the legacy need_attn export, which stays what it is)
@@ -600,8 +689,8 @@ class CaptionModel(Model):
             return lps, ids, []
         self._check_beam(beam_size)
         if beam_size > 1:
-            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos)
-        if self.fast_generation:
+            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best)
+        if self.fast_generation or opts is not None:         # (the search options live in the cached generator)
             return self._generate_cached(caption_ids, contexts, gen_len, eos)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
 
@@ -635,7 +724,10 @@ class CaptionModel(Model):
         dev = caption_ids.device
         kv = dec.project_contexts(contexts)
         sampling = self._sampling()
-        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention)
+        opts = self._check_options(1, attention, 1, gen_len)
+        # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
+        ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
+        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban)
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous()
@@ -651,6 +743,8 @@ class CaptionModel(Model):
             ids.fill_(self.padding_idx)
             lps.zero_()
             done_step.fill_(gen_len)
+            if ban is not None:
+                step.ban_source(ids, fin8)
         else:
             ids = torch.full((B, gen_len + 1), self.padding_idx, dtype=torch.long, device=dev)
             lps = torch.zeros(B, gen_len, dtype=torch.float32, device=dev)
@@ -682,6 +776,8 @@ class CaptionModel(Model):
             if i % check_every == 0 and bool(fin8.all()):
                 break
         for i in range(0 if fused else gen_len):
+            if ban is not None:
+                step.ban_source(ids, finished.to(torch.uint8))
             tok, lp = step(i, cur)
             yield i
             tok = tok.long().view(B)
@@ -706,7 +802,7 @@ class CaptionModel(Model):
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
         return lps[:, :steps], ids[:, :steps + 1], attns
 
-    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False):
+    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None):
         """-> step(i, cur [B,1]) -> (token [B,1], log-prob [B,1]) - or, with topk=k, the k best (tokens [B,1,k],
         log-probs [B,1,k]) of every row - for the cached greedy / beam generators; step.reorder(rows) permutes the
         rows of the incremental state (beam search).
@@ -724,9 +820,37 @@ class CaptionModel(Model):
         attention=True: the step also exports the head-averaged attention weights of every (layer, context) into static
         fp32 buffers [gen_len, B, S + 2] (decode.AttnSink, handed out as step.attn), slot = step index: from the host in an
         eager step, from the device counter in a captured one (single-step and multi-step graphs alike).  ('attn',) joins
-        the signature only then: the captures without maps are keyed and recorded exactly as before."""
+        the signature only then: the captures without maps are keyed and recorded exactly as before.
+
+        ban = (n, min_len, eos): the head's last launch becomes two - tell_decode_ban_list over the caller's histories
+        (step.ban_source(hist [B, L] int64, finished [B] uint8): static buffers of the caller's book when the step is
+        captured) with the step index from the host or from the device counter, then tell_adaptive_logprob_topk_banned (k = 1
+        for the greedy decode).  opts: the caller's whole option tuple; it joins the signature when given (a captured
+        bookkeeping launch differs with it), the default captures are keyed and recorded exactly as before."""
         dec = self.decoder
         names = [n for layer_kv in kv[:1] for n in layer_kv]
+        if ban is not None and (sample is not None or attention):
+            raise ValueError('no_repeat_ngram_size / min_len do not combine with sampling or attention maps')
+        ban_src = {}
+
+        def ban_source(hist, fin):
+            """The histories the ban lists are built from (before every eager step; once when the buffers are static)."""
+            if hist.dtype != torch.long or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1 or \
+                    hist.shape[1] > 256 or fin.dtype != torch.uint8 or fin.numel() != B or not fin.is_contiguous():
+                raise ValueError('ban_source: hist int64 [%d, L <= 256] and finished uint8 [%d] expected' % (B, B))
+            ban_src['hist'], ban_src['fin'] = hist, fin
+            if 'ban' not in ban_src or ban_src['ban'].shape[1] < hist.shape[1] + 1 or ban_src['ban'].device != hist.device:
+                ban_src['ban'] = torch.zeros(B, hist.shape[1] + 1, dtype=torch.int32, device=hist.device)
+                ban_src['n_ban'] = torch.zeros(B, dtype=torch.int32, device=hist.device)
+
+        def banned_head(x, sidx):
+            hist = ban_src['hist']
+            step_dev = sidx if torch.is_tensor(sidx) else None
+            ops.call('tell_decode_ban_list', hist, hist.stride(0), hist.shape[1], ban_src['fin'], B,
+                     0 if step_dev is not None else int(sidx), step_dev, int(ban[0]), int(ban[1]), int(ban[2]),
+                     ban_src['ban'], ban_src['ban'].stride(0), ban_src['n_ban'])
+            tok, lp = dec.adaptive_softmax.topk(x, max(int(topk), 1), ban=(ban_src['ban'], ban_src['n_ban']))
+            return (tok, lp) if topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
 
         def make_sink(device):
             from ..decode import AttnSink
@@ -734,6 +858,8 @@ class CaptionModel(Model):
                               for n, pair in lk.items()} for lk in kv], gen_len)
 
         def make_head(seed_dev):
+            if ban is not None:
+                return banned_head
             if sample is not None:
                 topp = sample[2] if len(sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
                 if topp is not None:
@@ -756,6 +882,7 @@ class CaptionModel(Model):
             eager_step.attn = sink
             eager_step.reorder = lambda rows: dec.reorder_incremental_state(state, rows)
             eager_step.seed = seed_word
+            eager_step.ban_source = ban_source
             return eager_step
         dev, dtype = kv[0][names[0]][0].device, kv[0][names[0]][0].dtype
         # lane: decode loops that are in flight TOGETHER (generate_lanes: two caption batches decoded on two streams) own
@@ -767,6 +894,8 @@ class CaptionModel(Model):
                           ('nucleus', int(sample[0]), float(sample[1]), float(sample[2]))),)
         if attention:                                             # (... and so are the sampling ones)
             sig = sig + (('attn',),)
+        if ban is not None or opts is not None:                   # (... and the ones without search options)
+            sig = sig + (('search', tuple(ban or ()), tuple(opts or ())),)
         cache = self.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -776,13 +905,15 @@ class CaptionModel(Model):
             cache.clear()
             self.__dict__['_decode_graphs_stamp'] = stamp
         h = cache.get(sig)
+        if h is not None:
+            ban_src = h['ban_src']                                # (the captured launches hold these buffers' addresses)
         if h is None:
             if len(cache) >= graphs.MAX_SIGNATURES:
                 cache.pop(next(iter(cache)))
             h = cache[sig] = {
                 # counter[0]: the position offset the kernels of a replay read; counter[1]: the NEXT step's offset when
                 # the bookkeeping launch is part of the captured step (`ig`, below)
-                'graph': None, 'counter': torch.zeros(2, dtype=torch.int32, device=dev), 'book': {},
+                'graph': None, 'counter': torch.zeros(2, dtype=torch.int32, device=dev), 'book': {}, 'ban_src': ban_src,
                 'seed': torch.zeros(1, dtype=torch.int32, device=dev),      # the sampling seed (written per caption batch)
                 'cur': torch.zeros(B, 1, dtype=torch.long, device=dev),
                 'kv': None,
@@ -977,31 +1108,42 @@ class CaptionModel(Model):
         step.book = book
         step.seed = h['seed']
         step.attn = h.get('attn')
+        step.ban_source = ban_source
+        step.sig = sig
+        step.handle = h
         step.counter_out = c_out                                  # (base 1: the offset of step i is i - 1)
         step.back = h['state'].get('_back')                       # ancestor table of the DynamicConv rings, or None
         return step
 
     @torch.no_grad()
-    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0):
-        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane))
+    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1):
+        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best))
 
-    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0):
+    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1):
         """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
         only samples top-1, transformer_faces_objects.py:443-464).  B*K rows (row = b*K + j) stay resident; the
         projected K/V of the static contexts are computed once per caption and replicated per beam; the DynamicConv
         input buffers are reordered by parent with the reference's `reorder_incremental_state` contract
         (dynamic.py:338-342).  Score = sum of token log-probs (no length penalty); a finished hypothesis keeps its
-        score and is extended with pad only.  -> (log_probs [B,steps], ids [B,steps+1] of the best hypothesis, [])."""
+        score and is extended with pad only.  -> (log_probs [B,steps], ids [B,steps+1] of the best hypothesis, []).
+        With search options: `beam_len_penalty` alpha ranks the candidates by sum * len ** -alpha (len:
+        generated tokens, </s> included; frozen when a hypothesis ends), `no_repeat_ngram_size` / `min_len` ban tokens per
+        hypothesis before its K best are taken.  The third result is a DecodeInfo (an empty list) with .scores [B] and, for
+        n_best = n > 1, .nbest = (ids [B,n,steps+1], log_probs [B,n,steps], scores [B,n])."""
         dec = self.decoder
         B, K = caption_ids.shape[0], int(beam_size)
         dev = caption_ids.device
         pad = self.padding_idx
+        opts = self._check_options(K, False, n_best, gen_len)
+        alpha = opts[0] if opts is not None else 0.0
+        ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
         rep = lambda t, dim: t.repeat_interleave(K, dim=dim).contiguous()           # noqa: E731
         # contexts, masks and projected K/V stay at batch B: the attention modules present the K hypotheses of a
         # sample as K query positions of that sample (modules/attention.py), nothing is replicated per beam
         ctx = {k_: v_ for k_, v_ in contexts.items() if torch.is_tensor(v_)}
         kv = dec.project_contexts(contexts)
-        step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane)
+        step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
+                                    opts=(opts + (int(eos),)) if opts is not None else None)
         cur = rep(caption_ids[:, 0:1], 0)
         finished = (cur[:, 0] == eos).view(B, K)
         fused = caption_ids.is_cuda and hasattr(step, 'cur') and K <= 8 and gen_len + 1 <= 256
@@ -1015,10 +1157,19 @@ class CaptionModel(Model):
             cum.fill_(float('-inf'))
             seqs.fill_(pad)
             lps.zero_()
+            if alpha:
+                nb = step.book('beam_norm', lambda: dict(len=torch.empty(B, K, dtype=torch.int32, device=dev),
+                                                         inv_norm=torch.empty(gen_len + 2, dtype=torch.float32, device=dev)))
+                hyp_len, inv_norm = nb['len'], nb['inv_norm']
+                hyp_len.zero_()
+                inv_norm.copy_(inv_norm_table(alpha, gen_len + 1))
         else:
             cum = torch.full((B, K), float('-inf'), dtype=torch.float32, device=dev)
             seqs = torch.full((B, K, gen_len + 1), pad, dtype=torch.long, device=dev)
             lps = torch.zeros(B, K, gen_len, dtype=torch.float32, device=dev)
+            if alpha:
+                hyp_len = torch.zeros(B, K, dtype=torch.long, device=dev)
+                inv_norm = inv_norm_table(alpha, gen_len + 1).to(dev)
         cum[:, 0] = 0.0                                     # all K rows start identical: only hypothesis 0 counts
         seqs[:, :, 0] = cur.view(B, K)
         base = (torch.arange(B, device=dev) * K).view(B, 1)
@@ -1032,8 +1183,16 @@ class CaptionModel(Model):
             ring = step.back is not None
             inv_temp = 1.0 / float(self.sampling_temp)
 
+            if ban is not None:
+                step.ban_source(seqs.view(B * K, gen_len + 1), fin8.view(B * K))
+
             def book(out, i, step_dev):
                 tk, lp = out
+                if alpha:
+                    ops.call('tell_beam_update_norm', tk, lp, cum, fin8, seqs, lps, step.cur, rows, hyp_len, inv_norm, B, K,
+                             gen_len + 1, int(i), int(pad), int(eos), inv_temp, step.back, step.back.shape[0] if ring else 0,
+                             step.counter_out, step_dev)
+                    return
                 ops.call('tell_beam_update', tk, lp, cum, fin8, seqs, lps, step.cur, rows, B, K, gen_len + 1, int(i), int(pad),
                          int(eos), inv_temp, step.back, step.back.shape[0] if ring else 0, step.counter_out, step_dev)
             i = 0
@@ -1054,6 +1213,8 @@ class CaptionModel(Model):
                     break
         for i in range(0 if fused else gen_len):
             # each hypothesis contributes its own K best tokens (the best K of K x V always lie among them)
+            if ban is not None:
+                step.ban_source(seqs.view(B * K, -1).contiguous(), finished.to(torch.uint8).view(B * K).contiguous())
             tk, lp = step(i, cur)
             tk, lp = tk.view(B, K, K).long(), lp.view(B, K, K) / self.sampling_temp
             # a finished hypothesis has ONE continuation: pad, at no cost
@@ -1062,7 +1223,18 @@ class CaptionModel(Model):
             first[0] = True
             lp = torch.where(fin, torch.where(first, torch.zeros_like(lp), torch.full_like(lp, float('-inf'))), lp)
             tk = torch.where(fin, torch.full_like(tk, pad), tk)
-            top, idx = (cum.unsqueeze(-1) + lp).view(B, K * K).topk(K, dim=1)       # sorted, best first
+            raw = (cum.unsqueeze(-1) + lp).view(B, K * K)
+            if alpha:
+                # candidates of a live hypothesis have i + 1 tokens, a finished one keeps its length; one fp32 multiply
+                cand_len = torch.where(finished, hyp_len, torch.full_like(hyp_len, i + 1)).unsqueeze(-1).expand(B, K, K)
+                score = raw * inv_norm[cand_len.reshape(B, K * K)]
+                score = torch.where(torch.isnan(score), torch.full_like(score, float('-inf')), score)
+                # (the lowest candidate index wins a tie: a stable descending sort)
+                idx = torch.sort(score, dim=1, descending=True, stable=True)[1][:, :K]
+                top = raw.gather(1, idx)
+                hyp_len = cand_len.reshape(B, K * K).gather(1, idx)
+            else:
+                top, idx = raw.topk(K, dim=1)                                       # sorted, best first
             parent = idx // K
             tok = tk.view(B, K * K).gather(1, idx)
             rows = (base + parent).view(-1)
@@ -1081,11 +1253,18 @@ class CaptionModel(Model):
                 n_steps = i + 1
                 break
         best = seqs[:, 0]                                    # topk keeps hypotheses sorted by score
-        steps = int((best[:, 1:] != pad).sum(1).max())       # one sync: length of the longest best caption
+        n_best = int(n_best)
+        # one sync: length of the longest best caption (n_best > 1: of the longest of the n best)
+        steps = int((best[:, 1:] != pad).sum(1).max()) if n_best == 1 else int((seqs[:, :n_best, 1:] != pad).sum(2).max())
         steps = max(min(steps, n_steps), 1)
+        info = DecodeInfo()
+        scores = cum * inv_norm[hyp_len.long()] if alpha else cum      # (the multiply the ranking used)
+        info.scores = scores[:, 0].clone()
+        if n_best > 1:
+            info.nbest = (seqs[:, :n_best, :steps + 1].clone(), lps[:, :n_best, :steps].clone(), scores[:, :n_best].clone())
         if fused:                                            # (the static buffers belong to the stepper)
-            return lps[:, 0, :steps].clone(), best[:, :steps + 1].clone(), []
-        return lps[:, 0, :steps], best[:, :steps + 1], []
+            return lps[:, 0, :steps].clone(), best[:, :steps + 1].clone(), info
+        return lps[:, 0, :steps], best[:, :steps + 1], info
 
     @torch.no_grad()
     def _generate_reference_flow(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2):

@@ -74,11 +74,13 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k):
-        """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search)."""
+    def topk(self, X, k, ban=None):
+        """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
+        ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
+        (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans)."""
         B, T, E = X.shape
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), topk=k)
+                                            self.head.class_proj.weight, self._tails(), topk=k, ban=ban)
         return tok.view(B, T, k), lp.view(B, T, k)
 
     def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None):

@@ -1765,7 +1765,24 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
     return token, token_lp, None
 
 
-def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None):
+def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None):
+    """The top-k head's last launch: tell_adaptive_logprob_topk, or - ban = (ban int32 [N, ld_ban], n_ban int32 [N]) -
+    tell_adaptive_logprob_topk_banned.  -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
+    tokens = torch.empty(N, k, dtype=torch.int32, device=head.device)
+    lps = torch.empty(N, k, dtype=torch.float32, device=head.device)
+    if ban is None:
+        call('tell_adaptive_logprob_topk', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
+             lds[2], ns[2], N, int(k), tokens, lps)
+    else:
+        bans, n_ban = ban
+        if bans.shape[0] != N or n_ban.shape[0] != N or bans.dtype != torch.int32 or n_ban.dtype != torch.int32:
+            raise ValueError('logprob_topk: ban int32 [%d, ld] and n_ban int32 [%d] expected' % (N, N))
+        call('tell_adaptive_logprob_topk_banned', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
+             tl[2], lds[2], ns[2], N, int(k), bans, bans.stride(0), n_ban, tokens, lps)
+    return tokens, lps, None
+
+
+def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p]): one top-k (with p: nucleus) draw per row instead of the arg-max
@@ -1779,7 +1796,7 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
-        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample)
+        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
     def logits(a, w):                    # fp32 rows start on 16 bytes (see AdaptiveLossFn): vector stores in the epilogue
@@ -1796,11 +1813,9 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if sample is not None and not want_full:
         return logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample)
     if topk:
-        tokens = torch.empty(N, topk, dtype=torch.int32, device=dev)
-        lps = torch.empty(N, topk, dtype=torch.float32, device=dev)
-        call('tell_adaptive_logprob_topk', head, head.stride(0), c0, n_tails, tl[0], ld[0], nn_[0], tl[1], ld[1],
-             nn_[1], tl[2], ld[2], nn_[2], N, int(topk), tokens, lps)
-        return tokens, lps, None
+        return logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban)
+    if ban is not None:
+        raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
     full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
     token = torch.empty(N, dtype=torch.int32, device=dev)
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
