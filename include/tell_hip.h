@@ -545,6 +545,23 @@ int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,
                                  float* token_lp, tell_stream_t stream);
+/* forced tokens (caption completion): runs BEHIND the pick kernel of the step (arg-max, banned top-k,
+ * sample, nucleus, beam top-k) over the tokens int32 / lps fp32 [rows, k] it has just written, k = 1..8, with the same logits.
+ * prefix int64 [n_samples, P] (ld_prefix), plen int32 [n_samples]: the tokens a sample's caption starts with (after <s>).
+ * Row r belongs to sample (row_ids ? row_ids[r] : r) / beams; the step index i is `step`, or *step_dev + 1 when step_dev is
+ * given (the device counter of a captured decode step).  A row with i < min(plen[sample], P) is FORCED:
+ *   tokens[r][0] = prefix[sample][i]; lps[r][0] = that token's log-prob exactly as tell_adaptive_logprob_argmax writes it
+ *   (logit - lse_head; a tail token adds head_lsm[c0 + c] - lse_tail; no temperature, no renormalisation, no ban list) -
+ *   bit for bit token_lp where the forced token is the arg-max; entries 1 .. k - 1 become (-inf, pad).  `pad` must be a token
+ *   of the vocabulary: tell_beam_update lets a (-inf) candidate survive as a filler hypothesis when a sample has fewer than K
+ *   finite candidates, and its token is the next step's embedding lookup.
+ * Every other row is FREE: left as the pick kernel wrote it, its workgroup leaves before it requests a logit.  Only the head
+ * and the forced token's own tail are reduced; register / streaming forms and capacity rule of tell_adaptive_logprob_argmax. */
+int tell_adaptive_logprob_forced(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                 int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                 int rows, int k, const long* prefix, long ld_prefix, int P, const int* plen,
+                                 int n_samples, const int* row_ids, int beams, int step, const int* step_dev, int pad,
+                                 int* tokens, float* lps, tell_stream_t stream);
 /* top-k sampling with a temperature (transformer_faces_objects.py:38-55, 443-470: lprobs.topk(k), / T, torch.multinomial).
  * Per row r at step i with seed s:
  *   1. candidates: the k (1..64) largest log-probs of the full adaptive softmax, each computed as in

@@ -751,6 +751,159 @@ extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int
   return tell_check_launch("logprob_argmax");
 }
 
+// ------------------------------------------------------------------ forced tokens (caption completion)
+// Runs BEHIND the mode's pick kernel, over the tokens / lps [rows, k] it has just written.  A row whose sample still has
+// prefix left at this step (i < plen[sample]) gets tokens[r][0] = prefix[sample][i] and lps[r][0] = that token's log-prob
+// exactly as the arg-max kernels write it; entries 1 .. k - 1 become (-inf, pad).  Every other row leaves before a single
+// logit is requested.  One 1024-thread workgroup per row; only the head and the forced token's own tail are reduced, with
+// the reductions of logprob_regs_kernel (REGS) / logprob_argmax_kernel (streaming): same grouping, same order, same bits.
+struct ForcedArgs {
+  const long* prefix; long ld_prefix; int P;
+  const int* plen; int n_samples;
+  const int* row_ids; int beams;
+  int step; const int* step_dev;
+  int pad, k;
+  int* tokens; float* lps;
+};
+// log-sum-exp of one register-resident segment: logprob_regs_kernel's loads, per-thread pairing, wave and cross-wave order
+template <int S>
+__device__ __forceinline__ float forced_lse_regs(const float* __restrict__ row, int n, float* red) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  f4 x[LPF_CAP[S]];
+#pragma unroll
+  for (int q = 0; q < LPF_CAP[S]; ++q) {
+    const int j = (q * 1024 + tid) * 4;
+    f4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (j + 3 < n) v = *reinterpret_cast<const f4*>(row + j);
+    else if (j < n) {
+      v.x = row[j];
+      if (j + 1 < n) v.y = row[j + 1];
+      if (j + 2 < n) v.z = row[j + 2];
+    }
+    x[q] = v;
+  }
+  float m = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < LPF_CAP[S]; ++q) m = fmaxf(fmaxf(m, fmaxf(x[q].x, x[q].y)), fmaxf(x[q].z, x[q].w));
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  float mx = red[0];
+#pragma unroll
+  for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int q = 0; q < LPF_CAP[S]; ++q)
+    t += (__expf(x[q].x - mx) + __expf(x[q].y - mx)) + (__expf(x[q].z - mx) + __expf(x[q].w - mx));
+  t = wave_sum(t);
+  if (lane == 0) red[wave] = t;
+  __syncthreads();
+  float sm = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) sm += red[w];
+  __syncthreads();
+  return mx + __logf(sm);
+}
+// ... and of a streamed one: logprob_argmax_kernel's two passes
+__device__ __forceinline__ float forced_lse_stream(const float* __restrict__ row, int n, float* red) {
+  float mx = -INFINITY;
+#pragma unroll 4
+  for (int j = threadIdx.x; j < n; j += 1024) mx = fmaxf(mx, row[j]);
+  mx = block_max(mx, red);
+  float s = 0.f;
+#pragma unroll 4
+  for (int j = threadIdx.x; j < n; j += 1024) s += __expf(row[j] - mx);
+  s = block_sum(s, red);
+  return mx + __logf(s);
+}
+template <bool REGS>
+__global__ __launch_bounds__(1024) void logprob_forced_kernel(LogProbArgs p, ForcedArgs a) {
+  __shared__ float red[16];
+  const int r = blockIdx.x;
+  // (uniform over the workgroup: everything below depends on the row alone)
+  const int row = a.row_ids ? a.row_ids[r] : r;
+  const int sample = row / a.beams;
+  if (row < 0 || sample >= a.n_samples) return;
+  const int i = a.step_dev ? *a.step_dev + 1 : a.step;
+  int pl = a.plen[sample];
+  pl = pl > a.P ? a.P : pl;
+  if (i < 0 || i >= pl) return;                              // a free row: the pick stands, no logit is read
+  const long t = a.prefix[(long)sample * a.ld_prefix + i];
+  const float* hrow = p.head + (long)r * p.ld_head;
+  // the forced token's segment: 0 = head, c + 1 = tail c at offset `local`
+  int seg = -1, local = 0;
+  if (t >= 0 && t < p.c0) { seg = 0; local = (int)t; }
+  else if (t >= p.c0) {
+    long base = p.c0;
+    for (int c = 0; c < p.n_tails; ++c) {
+      if (t < base + p.tail_n[c]) { seg = c + 1; local = (int)(t - base); break; }
+      base += p.tail_n[c];
+    }
+  }
+  float lp = -INFINITY;
+  int tok = a.pad;                                           // (an id outside the vocabulary: the host check refuses it)
+  if (seg >= 0) {
+    const float lse_h = REGS ? forced_lse_regs<0>(hrow, p.head_n, red) : forced_lse_stream(hrow, p.head_n, red);
+    tok = (int)t;
+    if (seg == 0) lp = hrow[local] - lse_h;
+    else {
+      const int c = seg - 1;
+      const float* trow = p.tail[c] + (long)r * p.ld_tail[c];
+      const int n = p.tail_n[c];
+      float lse_t;
+      if (!REGS) lse_t = forced_lse_stream(trow, n, red);
+      else if (c == 0) lse_t = forced_lse_regs<1>(trow, n, red);
+      else if (c == 1) lse_t = forced_lse_regs<2>(trow, n, red);
+      else lse_t = forced_lse_regs<3>(trow, n, red);
+      const float off = (hrow[p.c0 + c] - lse_h) - lse_t;
+      lp = trow[local] + off;
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.tokens[(long)r * a.k] = tok;
+    a.lps[(long)r * a.k] = lp;
+    for (int q = 1; q < a.k; ++q) { a.tokens[(long)r * a.k + q] = a.pad; a.lps[(long)r * a.k + q] = -INFINITY; }
+  }
+}
+extern "C" int tell_adaptive_logprob_forced(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                            int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                            int rows, int k, const long* prefix, long ld_prefix, int P, const int* plen,
+                                            int n_samples, const int* row_ids, int beams, int step, const int* step_dev,
+                                            int pad, int* tokens, float* lps, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_forced: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 8, "logprob_forced: 1 <= k <= 8");
+  TELL_REQUIRE(prefix && plen && P >= 1 && ld_prefix >= P && n_samples >= 1, "logprob_forced: prefix [n_samples, P] and plen [n_samples]");
+  TELL_REQUIRE(beams >= 1 && (row_ids || (long)n_samples * beams >= rows), "logprob_forced: rows / beams exceeds n_samples");
+  TELL_REQUIRE(step_dev || step >= 0, "logprob_forced: step >= 0");
+  TELL_REQUIRE(tokens && lps, "logprob_forced: tokens and lps [rows, k]");
+  const int vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(pad >= 0 && pad < vocab, "logprob_forced: pad must be a token of the vocabulary (it is the next step's input of a filler hypothesis)");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n_tails > 0 ? n0 : 0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n_tails > 1 ? n1 : 0;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n_tails > 2 ? n2 : 0;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  ForcedArgs a;
+  a.prefix = prefix; a.ld_prefix = ld_prefix; a.P = P; a.plen = plen; a.n_samples = n_samples; a.row_ids = row_ids;
+  a.beams = beams; a.step = step; a.step_dev = step_dev; a.pad = pad; a.k = k; a.tokens = tokens; a.lps = lps;
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    hipLaunchKernelGGL((logprob_forced_kernel<true>), dim3(rows), dim3(1024), 0, stream, p, a);
+    return tell_check_launch("logprob_forced (registers)");
+  }
+  hipLaunchKernelGGL((logprob_forced_kernel<false>), dim3(rows), dim3(1024), 0, stream, p, a);
+  return tell_check_launch("logprob_forced");
+}
+
 // ------------------------------------------------------------------ top-k sampling with a temperature
 // transformer_faces_objects.py:443-470 with sampling_topk = k: lprobs.topk(k), / T, torch.multinomial.  Per row, exactly
 // (include/tell_hip.h, DESIGN.md "Top-k sampling"): the k largest log-probs of the full adaptive softmax (value descending,

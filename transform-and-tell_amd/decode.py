@@ -208,14 +208,15 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
     -> (token int32 [N], log-prob fp32 [N], None); topk = k > 0 (beam search): the k best of every row, best first,
     (tokens int32 [N,k], log-probs fp32 [N,k], None); sample = (k, inv_temp, seed_dev, row_ids, step): the last launch is
     the top-k draw instead of the arg-max (ops.logprob_sample); ban = (ban, n_ban) with topk: the last launch is
-    tell_adaptive_logprob_topk_banned (ops.logprob_topk)."""
+    tell_adaptive_logprob_topk_banned (ops.logprob_topk); force (caption completion): one more launch behind that pick,
+    tell_adaptive_logprob_forced over the same logits (ops.logprob_forced) - without it the launches are what they were."""
     if ban is not None and (not topk or sample is not None):
         raise ValueError('head_step: a ban list goes with topk = k >= 1')
     N, E = x2.shape
@@ -258,15 +259,18 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         ns = [e.shape[0] for e in embs] + [0] * (3 - n_tails)
         tl = [logits[:, offs[1 + i]:] if i < n_tails else None for i in range(3)]
         lds = [LD if i < n_tails else 0 for i in range(3)]
+
+        def forced(picked):
+            return picked if force is None else ops.logprob_forced(logits, LD, c0, n_tails, tl, lds, ns, N, picked, force)
         if sample is not None:
-            return ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample)
+            return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample))
         if topk:
-            return ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban)
+            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban))
         token = torch.empty(N, dtype=torch.int32, device=dev)
         token_lp = torch.empty(N, dtype=torch.float32, device=dev)
         call('tell_adaptive_logprob_argmax', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
              ns[2], N, None, 0, token, token_lp)
-        return token, token_lp, None
+        return forced((token, token_lp, None))
     w_all = ops._cached(emb0, ('whead_all', class_proj._version, class_proj.data_ptr()) +
                         tuple((p._version, p.data_ptr()) for p in projs),
                         lambda: torch.cat([ops.weight(emb0), ops.weight(class_proj)] + [ops.weight(p) for p in projs],
@@ -297,15 +301,18 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         ops.gemm(big[0]['a'], big[0]['b'], out=big[0]['out'])
     elif big:       # two dependent launches of 235 / 473 column tiles (12 + 16 us) -> one launch of 708
         ops.gemm_grouped(big)
+
+    def forced(picked):
+        return picked if force is None else ops.logprob_forced(head, ld, c0, n_tails, tl, lds, ns, N, picked, force)
     if sample is not None:
-        return ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample)
+        return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample))
     if topk:
-        return ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban)
+        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban))
     token = torch.empty(N, dtype=torch.int32, device=dev)
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
     call('tell_adaptive_logprob_argmax', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
          ns[2], N, None, 0, token, token_lp)
-    return token, token_lp, None
+    return forced((token, token_lp, None))
 
 
 class PackedKV:

@@ -94,8 +94,11 @@ class BaselineGloveModel(Model):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1):
+    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None):
         _refuse_search_options(self, n_best=n_best)
+        if prefix is not None:
+            raise ValueError('prefix: %s decodes with an LSTM decoder, whose step has its own decision launch; a forced '
+                             'prefix is out of scope there (DESIGN.md section 17)' % type(self).__name__)
         if attention:
             raise ValueError('attention=True: %s decodes with an LSTM decoder; attention maps are exported for the DynamicConv '
                              'decoders only (its dot attention is not covered)' % type(self).__name__)
@@ -206,12 +209,18 @@ class TransformerGloveModel(CaptionModel):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1):
+    def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1,
+                 prefix=None):
         if attention:
             self._check_attention(beam_size)
         self._check_options(beam_size, attention, n_best)
+        pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention,
-                                                   **({'n_best': n_best} if n_best != 1 else {}))
-        return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
+                                                   **({'n_best': n_best} if n_best != 1 else {}),
+                                                   **({'prefix': pfx} if pfx is not None else {}))
+        out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
+        if pfx is not None:
+            out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)
+        return out

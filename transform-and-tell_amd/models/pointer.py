@@ -167,9 +167,11 @@ class PointerModelBase(CaptionModel):
 
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None):
         if attention:
             self._check_attention(beam_size)
+        if prefix is not None:
+            self._check_prefix(prefix, 0)                             # (refused: the copy decision is out of scope)
         self._check_beam(beam_size)
         self._check_options(beam_size, attention, n_best)
         self._require_masks(context)

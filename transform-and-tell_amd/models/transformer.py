@@ -114,6 +114,47 @@ def check_beam_options(beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, 
     return float(a), int(n), int(m)
 
 
+def check_prefix(prefix, batch_size, vocab_size, gen_len=DEFAULT_GEN_LEN, pad=1, eos=2):
+    """The forced caption prefix of the cached generators: int64 [B, P], the caption tokens AFTER <s>,
+    right-padded with `pad`; plen[r] = the number of leading non-pad tokens (0: the row decodes freely).  </s> may only be
+    the last token of a row's prefix, ids lie in 0..vocab_size - 1, P <= gen_len, B = batch_size.
+    -> (prefix int64 [B, P] on the CPU, plen int32 [B]), or None for prefix = None; ValueError otherwise."""
+    if prefix is None:
+        return None
+    if not torch.is_tensor(prefix) or prefix.dtype != torch.long or prefix.dim() != 2:
+        raise ValueError('prefix must be an int64 tensor [B, P] of the caption tokens after <s> (got %s)' % (
+            '%s %s' % (prefix.dtype, tuple(prefix.shape)) if torch.is_tensor(prefix) else type(prefix).__name__))
+    B, P = prefix.shape
+    if B != int(batch_size):
+        raise ValueError('prefix has %d rows, the batch has %d' % (B, int(batch_size)))
+    if P > int(gen_len):
+        raise ValueError('prefix is %d tokens wide, generation stops after gen_len = %d' % (P, int(gen_len)))
+    pf = prefix.detach().cpu().contiguous()
+    real = pf != int(pad)
+    plen = real.sum(1)
+    if P and not bool((real == (torch.arange(P).unsqueeze(0) < plen.unsqueeze(1))).all()):
+        raise ValueError('prefix: a token follows a pad (rows are right-padded with %d)' % int(pad))
+    if P and bool((real & ((pf < 0) | (pf >= int(vocab_size)))).any()):
+        raise ValueError('prefix: token ids must lie in 0..%d' % (int(vocab_size) - 1))
+    if P and bool(((pf == int(eos)) & real & (torch.arange(P).unsqueeze(0) != (plen - 1).unsqueeze(1))).any()):
+        raise ValueError('prefix: </s> (%d) may only be the last token of a row\'s prefix' % int(eos))
+    return pf, plen.to(torch.int32)
+
+
+def encode_prefix(texts, bpe=None, pad=1):
+    """Caption starts as a `prefix` tensor: every string is encoded as the indexer encodes a caption
+    (data/indexers.RobertaTokenIndexer.encode) without <s> and without the closing </s>; '' or None gives a free row.
+    bpe: a RobertaBPE (default: the installed roberta-base files).  -> int64 [len(texts), P] right-padded with `pad`."""
+    from ..data.indexers import RobertaTokenIndexer
+    indexer = RobertaTokenIndexer(bpe=bpe, padding_value=pad)
+    rows = [indexer.encode(t)[0][1:-1] if t else [] for t in texts]
+    P = max([len(r) for r in rows] + [1])
+    out = torch.full((len(rows), P), int(pad), dtype=torch.long)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = torch.tensor(r, dtype=torch.long)
+    return out
+
+
 def inv_norm_table(alpha, L):
     """The length-penalty table of tell_beam_update_norm: fp32 [L + 1], [0] = 1, [l] = float32(float64(l) ** -alpha)."""
     import numpy as np
@@ -259,6 +300,17 @@ class CaptionModel(Model):
             raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
                              'search options cover the cached DynamicConv generator only' % (what, type(self).__name__))
         return opts
+
+    def _check_prefix(self, prefix, batch_size, gen_len=DEFAULT_GEN_LEN, eos=2):
+        """generate(prefix=...): check_prefix against this model; the cached DynamicConv generators only - the LSTM decoders
+        and the copy models end their decode step in a decision launch of their own.  -> (prefix, plen) or None."""
+        if prefix is None:
+            return None
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('prefix: %s has a decode step with its own decision launch (LSTM decoders, copy models such as '
+                             'transformer_pointer / transformer_pointer_2); a forced prefix is out of scope there: it covers '
+                             'the cached DynamicConv generator only' % type(self).__name__)
+        return check_prefix(prefix, batch_size, self.decoder.adaptive_softmax.vocab_size, gen_len, self.padding_idx, eos)
 
     def _check_attention(self, beam_size=1):
         """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
@@ -519,8 +571,13 @@ class CaptionModel(Model):
         return ' '.join(str(int(i)) for i in ids if int(i) != 2)
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        prefix (caption completion): int64 [B, P], the tokens every caption starts with after <s>,
+        right-padded with padding_idx (`check_prefix`; `encode_prefix` builds it from strings).  Row r's first plen[r] steps take
+        the prefix token instead of the model's pick - inside the decode step, every mode of the cached generators - and
+        report the model's log-prob of it; 'gen_ids' is <s>, the prefix, the generated rest, 'log_probs' has one entry per
+        step (forced steps: the teacher-forced log-probs), 'prefix_len' [B] is plen.  None: exactly the launches of before.
         'scores' [B]: the score of every caption (sum of its log-probs; beam search with `beam_len_penalty` alpha: * len ** -alpha).
         n_best = n (2..beam_size): also 'gen_ids_nbest' [B, n, L], 'log_probs_nbest' [B, n, L - 1], 'scores_nbest' [B, n] - the
         n best hypotheses of the beam, best first ('gen_ids' / 'log_probs' stay hypothesis 0).
@@ -534,10 +591,36 @@ class CaptionModel(Model):
         if attention:
             self._check_attention(beam_size)
         self._check_options(beam_size, attention, n_best)
+        # (prefix=None reads nothing of the batch here: the default path is the path of before)
+        pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
-                                                   **({'n_best': n_best} if n_best != 1 else {}))
-        return self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
+                                                   **({'n_best': n_best} if n_best != 1 else {}),
+                                                   **({'prefix': pfx} if pfx is not None else {}))
+        out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
+        if pfx is not None:
+            out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)
+        return out
+
+    @torch.no_grad()
+    def score_captions(self, batch):
+        """How likely the model finds the batch's OWN captions: the caption after <s>, its </s> included, is forced token by
+        token through the greedy cached generator (generate(prefix=...)).  -> {'log_probs' [B, T - 1]: the teacher-forced
+        log-prob of every caption token (0 behind a row's </s>), 'scores' [B]: their sum, 'prefix_len' [B]: tokens scored}.
+        The captions may be at most gen_len (100) tokens long."""
+        cap = batch['caption'][self.index]
+        prefix = cap[:, 1:].contiguous()
+        f = {k: (dict(v) if isinstance(v, dict) else v) for k, v in batch.items()
+             if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds', 'encoded')}
+        out = self.generate(**f, prefix=prefix)
+        plen = out['prefix_len']
+        lp = out['log_probs']
+        T = prefix.shape[1]
+        full = lp.new_zeros(lp.shape[0], T)
+        n = min(T, lp.shape[1])
+        full[:, :n] = lp[:, :n]
+        full = full * (torch.arange(T, device=lp.device).unsqueeze(0) < plen.unsqueeze(1))
+        return {'log_probs': full, 'scores': full.sum(1), 'prefix_len': plen}
 
     def caption_attention(self, batch, gen, bpe=None):
         """The reference's per-word attention view of `gen = generate(**batch, attention=True)` (attention_maps.py)."""
@@ -583,7 +666,7 @@ class CaptionModel(Model):
                     group.append(b)
             if not group:
                 return
-            gens, outs, heads, thirds = [], [None] * len(group), [], [None] * len(group)
+            gens, outs, heads, thirds, plens = [], [None] * len(group), [], [None] * len(group), []
             for ln, b in enumerate(group):
                 f = {k: v for k, v in b.items() if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds')}
                 if forward:
@@ -593,12 +676,18 @@ class CaptionModel(Model):
                     caption_ids, _, contexts = self._forward(**f)
                 # (sampling: the batch's seed is drawn here, in batch order - the draws of `generate` batch by batch)
                 seed = draw_seed() if self._sampling() is not None else None
+                if b.get('prefix') is not None and forward:
+                    raise ValueError('prefix goes with generate, not with forward=True')
+                pfx = self._check_prefix(b.get('prefix'), caption_ids.shape[0])
+                pkw = {'prefix': pfx} if pfx is not None else {}
+                plens.append(pfx[1] if pfx is not None else None)
                 ev = torch.cuda.Event()
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best) if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention))
+                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, **pkw)
+                         if beam_size > 1 else
+                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, **pkw))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -609,6 +698,8 @@ class CaptionModel(Model):
                         except StopIteration as done:
                             lp, ids, attns = done.value
                             outs[ln] = self._attn_output({'gen_ids': ids, 'log_probs': lp}, attns)
+                            if plens[ln] is not None:
+                                outs[ln]['prefix_len'] = plens[ln].to(ids.device, torch.long)
                             thirds[ln] = attns
                             live.remove(ln)
             for ln in range(len(group)):
@@ -665,20 +756,27 @@ class CaptionModel(Model):
             if enc is not None and enc.stale():
                 enc = self.encode(cur['context'], cur['image'])
             extra = {'encoded': enc} if enc is not None else {}
-            out = self(**cur, **extra) if forward else self.generate(**cur, beam_size=beam_size, **extra, **gen_kw)
+            if forward and cur.get('prefix') is not None:
+                raise ValueError('prefix goes with generate, not with forward=True')
+            out = self(**{k_: v_ for k_, v_ in cur.items() if k_ != 'prefix'}, **extra) if forward else self.generate(**cur, beam_size=beam_size, **extra, **gen_kw)
             yield cur, out
             cur, enc = nxt, ahead
 
     # ---- :399-494 -----------------------------------------------------------------
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
-    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1):
+    def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
+                  prefix=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
+        pkw = {}
+        if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
+            self._check_prefix(prefix[0], caption_ids.shape[0], gen_len, eos)
+            pkw = {'prefix': prefix}
         if attention:
             # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
             # flow with the legacy need_attn export, which stays what it is)
             self._check_attention(beam_size)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, **pkw)
         if not hasattr(self.decoder, 'project_contexts'):
             # a recurrent decoder behind this model class (expt/*/3_lstm_roberta: `lstm_decoder_flattened`): greedy
             # decode that carries the LSTM state.  (The reference's loop feeds such a decoder only the last token with
@@ -689,9 +787,9 @@ class CaptionModel(Model):
             return lps, ids, []
         self._check_beam(beam_size)
         if beam_size > 1:
-            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best)
-        if self.fast_generation or opts is not None:         # (the search options live in the cached generator)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos)
+            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, **pkw)
+        if self.fast_generation or opts is not None or pkw:  # (the search options live in the cached generator)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, **pkw)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
 
     @staticmethod
@@ -704,10 +802,12 @@ class CaptionModel(Model):
             return done.value
 
     @torch.no_grad()
-    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False):
-        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention))
+    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None):
+        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
+                                              **({'prefix': prefix} if prefix is not None else {})))
 
-    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False):
+    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
+                      prefix=None):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -718,7 +818,10 @@ class CaptionModel(Model):
         sampling_topk > 1: the head's last launch draws from the top k instead (tell_adaptive_logprob_sample), keyed on
         (seed, row, step) - `seed` (default: drawn now, draw_seed) goes into the stepper's device word before the first step.
         attention=True: every step also leaves its head-averaged attention weights in the stepper's sink (step.attn, one slot
-        per step); the third result is then an AttnMaps (maps {name: [B, steps, n_layers, S + 2] fp32}, steps [B]) instead of []."""
+        per step); the third result is then an AttnMaps (maps {name: [B, steps, n_layers, S + 2] fp32}, steps [B]) instead of [].
+        prefix = (tokens int64 [B, P], plen int32 [B]) of check_prefix: the stepper's forcing table is filled before the first step
+        and the head of every step ends in one more launch (tell_adaptive_logprob_forced); the bookkeeping is untouched - it
+        books a forced token exactly as a picked one."""
         dec = self.decoder
         B = caption_ids.shape[0]
         dev = caption_ids.device
@@ -727,7 +830,10 @@ class CaptionModel(Model):
         opts = self._check_options(1, attention, 1, gen_len)
         # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
         ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
-        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban)
+        step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
+                                    **({'prefix': True} if prefix is not None else {}))
+        if prefix is not None:
+            step.set_prefix(*prefix)
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous()
@@ -802,7 +908,8 @@ class CaptionModel(Model):
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
         return lps[:, :steps], ids[:, :steps + 1], attns
 
-    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None):
+    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
+                        prefix=False):
         """-> step(i, cur [B,1]) -> (token [B,1], log-prob [B,1]) - or, with topk=k, the k best (tokens [B,1,k],
         log-probs [B,1,k]) of every row - for the cached greedy / beam generators; step.reorder(rows) permutes the
         rows of the incremental state (beam search).
@@ -826,9 +933,34 @@ class CaptionModel(Model):
         (step.ban_source(hist [B, L] int64, finished [B] uint8): static buffers of the caller's book when the step is
         captured) with the step index from the host or from the device counter, then tell_adaptive_logprob_topk_banned (k = 1
         for the greedy decode).  opts: the caller's whole option tuple; it joins the signature when given (a captured
-        bookkeeping launch differs with it), the default captures are keyed and recorded exactly as before."""
+        bookkeeping launch differs with it), the default captures are keyed and recorded exactly as before.
+
+        prefix=True (caption completion): the stepper owns a forcing table - int64 [samples, gen_len] + int32 [samples], static,
+        filled per caption batch by step.set_prefix(tokens, plen) - and every head ends in tell_adaptive_logprob_forced with the
+        step index from the host or from the device counter.  ('prefix',) joins the signature: its own captured graph, one for
+        every prefix width; without it nothing is allocated, launched or keyed differently."""
         dec = self.decoder
         names = [n for layer_kv in kv[:1] for n in layer_kv]
+        n_hyp = max(int(topk), 1)
+        pfx = {}
+
+        def make_prefix(device):
+            return {'tab': torch.full((B // n_hyp, int(gen_len)), int(self.padding_idx), dtype=torch.long, device=device),
+                    'plen': torch.zeros(B // n_hyp, dtype=torch.int32, device=device)}
+
+        def set_prefix(tokens, plen):
+            if not pfx:
+                raise ValueError('set_prefix: the stepper was built without prefix=True')
+            if tokens.shape[0] != pfx['tab'].shape[0] or tokens.shape[1] > pfx['tab'].shape[1] or plen.numel() != tokens.shape[0]:
+                raise ValueError('set_prefix: tokens [%d, P <= %d] and plen [%d] expected' % (
+                    pfx['tab'].shape[0], pfx['tab'].shape[1], pfx['tab'].shape[0]))
+            pfx['tab'].fill_(int(self.padding_idx))
+            pfx['tab'][:, :tokens.shape[1]].copy_(tokens)
+            pfx['plen'].copy_(plen.to(torch.int32))
+
+        def fkw(sidx):
+            """The head's `force` argument at step index sidx (host int, or the device counter of a captured step)."""
+            return {'force': (pfx['tab'], pfx['plen'], None, n_hyp, sidx, int(self.padding_idx))} if pfx else {}
         if ban is not None and (sample is not None or attention):
             raise ValueError('no_repeat_ngram_size / min_len do not combine with sampling or attention maps')
         ban_src = {}
@@ -849,7 +981,7 @@ class CaptionModel(Model):
             ops.call('tell_decode_ban_list', hist, hist.stride(0), hist.shape[1], ban_src['fin'], B,
                      0 if step_dev is not None else int(sidx), step_dev, int(ban[0]), int(ban[1]), int(ban[2]),
                      ban_src['ban'], ban_src['ban'].stride(0), ban_src['n_ban'])
-            tok, lp = dec.adaptive_softmax.topk(x, max(int(topk), 1), ban=(ban_src['ban'], ban_src['n_ban']))
+            tok, lp = dec.adaptive_softmax.topk(x, max(int(topk), 1), ban=(ban_src['ban'], ban_src['n_ban']), **fkw(sidx))
             return (tok, lp) if topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
 
         def make_sink(device):
@@ -863,16 +995,19 @@ class CaptionModel(Model):
             if sample is not None:
                 topp = sample[2] if len(sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
                 if topp is not None:
-                    return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, topp=topp)
-                return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx)
+                    return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, topp=topp,
+                                                                       **fkw(sidx))
+                return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, **fkw(sidx))
             if topk:
-                return lambda x, sidx: dec.adaptive_softmax.topk(x, topk)
-            return lambda x, sidx: dec.adaptive_softmax.greedy(x)
+                return lambda x, sidx: dec.adaptive_softmax.topk(x, topk, **fkw(sidx))
+            return lambda x, sidx: dec.adaptive_softmax.greedy(x, **fkw(sidx))
         if not graphs.ENABLED or self.training or not torch.is_tensor(kv[0][names[0]][0]) or \
                 not kv[0][names[0]][0].is_cuda:
             state = {}
             seed_word = torch.zeros(1, dtype=torch.int32, device=next(dec.parameters()).device)
             head = make_head(seed_word)
+            if prefix:
+                pfx.update(make_prefix(seed_word.device))
 
             sink = make_sink(seed_word.device) if attention else None
 
@@ -883,6 +1018,7 @@ class CaptionModel(Model):
             eager_step.reorder = lambda rows: dec.reorder_incremental_state(state, rows)
             eager_step.seed = seed_word
             eager_step.ban_source = ban_source
+            eager_step.set_prefix = set_prefix
             return eager_step
         dev, dtype = kv[0][names[0]][0].device, kv[0][names[0]][0].dtype
         # lane: decode loops that are in flight TOGETHER (generate_lanes: two caption batches decoded on two streams) own
@@ -896,6 +1032,8 @@ class CaptionModel(Model):
             sig = sig + (('attn',),)
         if ban is not None or opts is not None:                   # (... and the ones without search options)
             sig = sig + (('search', tuple(ban or ()), tuple(opts or ())),)
+        if prefix:                                                # (... and every one without a forced prefix)
+            sig = sig + (('prefix',),)
         cache = self.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -959,6 +1097,10 @@ class CaptionModel(Model):
                 h['attn'] = make_sink(dev)
             h['ig'] = bool(_dec.IN_GRAPH_BOOK and dtype == torch.bfloat16 and _dec.usable(dec, probe, h['state'], kv) and
                            _dec.embed_usable(dec.embedder, h['cur'], h['state']))
+            if prefix:
+                h['pfx'] = make_prefix(dev)
+        if prefix:
+            pfx.update(h['pfx'])                                  # (the captured launches hold these buffers' addresses)
         for lk, ls in zip(kv, h['kv']):
             for n, pair in lk.items():
                 if not isinstance(ls[n], tuple):                  # decode.PackedKV
@@ -1109,6 +1251,7 @@ class CaptionModel(Model):
         step.seed = h['seed']
         step.attn = h.get('attn')
         step.ban_source = ban_source
+        step.set_prefix = set_prefix
         step.sig = sig
         step.handle = h
         step.counter_out = c_out                                  # (base 1: the offset of step i is i - 1)
@@ -1116,10 +1259,11 @@ class CaptionModel(Model):
         return step
 
     @torch.no_grad()
-    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1):
-        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best))
+    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
+        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best,
+                                            **({'prefix': prefix} if prefix is not None else {})))
 
-    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1):
+    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
         """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
         only samples top-1, transformer_faces_objects.py:443-464).  B*K rows (row = b*K + j) stay resident; the
         projected K/V of the static contexts are computed once per caption and replicated per beam; the DynamicConv
@@ -1129,7 +1273,10 @@ class CaptionModel(Model):
         With search options: `beam_len_penalty` alpha ranks the candidates by sum * len ** -alpha (len:
         generated tokens, </s> included; frozen when a hypothesis ends), `no_repeat_ngram_size` / `min_len` ban tokens per
         hypothesis before its K best are taken.  The third result is a DecodeInfo (an empty list) with .scores [B] and, for
-        n_best = n > 1, .nbest = (ids [B,n,steps+1], log_probs [B,n,steps], scores [B,n])."""
+        n_best = n > 1, .nbest = (ids [B,n,steps+1], log_probs [B,n,steps], scores [B,n]).
+        prefix = (tokens, plen) of check_prefix: during a sample's forced steps every hypothesis' candidate list is the forced
+        token and K - 1 fillers (-inf, pad), so only slot 0 stays live - as at step 0 - and the beam opens at the first free
+        step; the bookkeeping is untouched."""
         dec = self.decoder
         B, K = caption_ids.shape[0], int(beam_size)
         dev = caption_ids.device
@@ -1143,7 +1290,10 @@ class CaptionModel(Model):
         ctx = {k_: v_ for k_, v_ in contexts.items() if torch.is_tensor(v_)}
         kv = dec.project_contexts(contexts)
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
-                                    opts=(opts + (int(eos),)) if opts is not None else None)
+                                    opts=(opts + (int(eos),)) if opts is not None else None,
+                                    **({'prefix': True} if prefix is not None else {}))
+        if prefix is not None:
+            step.set_prefix(*prefix)
         cur = rep(caption_ids[:, 0:1], 0)
         finished = (cur[:, 0] == eos).view(B, K)
         fused = caption_ids.is_cuda and hasattr(step, 'cur') and K <= 8 and gen_len + 1 <= 256

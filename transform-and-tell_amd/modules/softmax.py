@@ -74,16 +74,16 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k, ban=None):
+    def topk(self, X, k, ban=None, force=None):
         """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
         ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
         (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans)."""
         B, T, E = X.shape
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), topk=k, ban=ban)
+                                            self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force)
         return tok.view(B, T, k), lp.view(B, T, k)
 
-    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None):
+    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None):
         """One top-k draw with temperature per position (transformer_faces_objects.py:443-470: lprobs.topk(k), / temp,
         multinomial), fused like `greedy`: -> (token [B, T], log-prob [B, T] WITHOUT the temperature).  seed_dev: int32 [1]
         device word holding the seed; step: host step index or the int32 [1] device counter of a captured step (step - 1);
@@ -95,13 +95,15 @@ class AdaptiveSoftmax(nn.Module):
         if topp is not None:
             sample = sample + (float(topp),)
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), sample=sample)
+                                            self.head.class_proj.weight, self._tails(), sample=sample, force=force)
         return tok.view(B, T), lp.view(B, T)
 
-    def greedy(self, X):
+    def greedy(self, X, force=None):
         """Fused arg-max over the full vocabulary (get_log_prob + topk(1),
-        transformer_faces_objects.py:443-464) without materialising [N, vocab]."""
+        transformer_faces_objects.py:443-464) without materialising [N, vocab].
+        force (here, in `topk` and in `sample`): the forcing table of a caption completion (ops.logprob_forced) - rows with
+        prefix left take the prefix token and its log-prob instead of the pick."""
         B, T, E = X.shape
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails())
+                                            self.head.class_proj.weight, self._tails(), force=force)
         return tok.view(B, T), lp.view(B, T)

@@ -1782,11 +1782,32 @@ def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None):
     return tokens, lps, None
 
 
-def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None):
+def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
+    """Caption completion: tell_adaptive_logprob_forced behind the pick kernel, in place over picked = (tokens int32 [N] or
+    [N, k], log-probs fp32 alike, None) and the logits that pick was taken from.  force = (prefix int64 [n_samples, P], plen
+    int32 [n_samples], row_ids None or int32 [N], beams, step, pad): step the host step index, or an int32 [1] device
+    counter holding step - 1 (a captured decode step's).  -> picked."""
+    prefix, plen, row_ids, beams, step, pad = force
+    tokens, lps = picked[0], picked[1]
+    k = tokens.numel() // max(N, 1)
+    if prefix.dtype != torch.long or prefix.dim() != 2 or prefix.stride(1) != 1 or plen.dtype != torch.int32 or \
+            plen.numel() != prefix.shape[0] or not plen.is_contiguous() or not tokens.is_contiguous() or \
+            not lps.is_contiguous() or tokens.numel() != N * k or lps.numel() != N * k:
+        raise ValueError('logprob_forced: prefix int64 [n, P], plen int32 [n] and contiguous tokens / lps [%d, k] expected' % N)
+    step_dev = step if torch.is_tensor(step) else None
+    call('tell_adaptive_logprob_forced', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
+         ns[2], N, int(k), prefix, prefix.stride(0), prefix.shape[1], plen, prefix.shape[0], row_ids, int(beams),
+         0 if step_dev is not None else int(step), step_dev, int(pad), tokens, lps)
+    return picked
+
+
+def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p]): one top-k (with p: nucleus) draw per row instead of the arg-max
-    (logprob_sample)."""
+    (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced)."""
+    if force is not None and want_full:
+        raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
@@ -1796,7 +1817,7 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
-        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban)
+        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
     def logits(a, w):                    # fp32 rows start on 16 bytes (see AdaptiveLossFn): vector stores in the epilogue
@@ -1810,10 +1831,13 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
         tl[i] = logits(h, weight(emb))
         ld[i], nn_[i] = tl[i].stride(0), tl[i].shape[1]
     vocab = c0 + sum(nn_)
+
+    def forced(picked):
+        return picked if force is None else logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
     if sample is not None and not want_full:
-        return logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample)
+        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample))
     if topk:
-        return logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban)
+        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban))
     if ban is not None:
         raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
     full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
@@ -1821,7 +1845,7 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
     call('tell_adaptive_logprob_argmax', head, head.stride(0), c0, n_tails, tl[0], ld[0], nn_[0], tl[1], ld[1],
          nn_[1], tl[2], ld[2], nn_[2], N, full, vocab if want_full else 0, token, token_lp)
-    return token, token_lp, full
+    return forced((token, token_lp, full))
 
 
 LN2 = math.log(2.0)
