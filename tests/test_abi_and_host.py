@@ -270,3 +270,82 @@ def test_signature_cache_lru_and_thrash_guard():
         i += 1
     assert i > graphs.THRASH_FREEZE // 2 and c.evictions == ev
     assert sight(2000) == 'captured' and c.evictions == ev + 1                            # thawed: the LRU gets another chance
+
+
+def test_graphs_capture_registers_resets_and_passes_through(monkeypatch):
+    """graphs.capture with recording stand-ins for hip.call / hip.tile_slots / hip.bound_stream / torch.cuda.graph: the step
+    pointers given are registered before the graph context is entered (those not given are never touched), the contexts are
+    entered in the order no_gc -> tile_slots -> graph -> bound_stream, graph_kw reaches torch.cuda.graph untouched, and a
+    body that raises still leaves every registered pointer at None and the collector as it was."""
+    import gc
+    from tell_amd import graphs
+    log = []
+
+    def ctx(name):
+        class Ctx:
+            def __init__(self, *args, **kw):
+                log.append((name, 'init', args, kw))
+
+            def __enter__(self):
+                log.append((name, 'enter', gc.isenabled()))
+                return self
+
+            def __exit__(self, *exc):
+                log.append((name, 'exit'))
+                return False
+        return Ctx
+    monkeypatch.setattr(graphs.hip, 'call', lambda name, *args: log.append(('call', name) + args))
+    monkeypatch.setattr(graphs.hip, 'tile_slots', ctx('tile_slots'))
+    monkeypatch.setattr(graphs.hip, 'bound_stream', ctx('bound_stream'))
+    monkeypatch.setattr(torch.cuda, 'graph', ctx('graph'))
+    g, rng, pos = object(), object(), object()
+    for was in (True, False):
+        try:
+            del log[:]
+            (gc.enable if was else gc.disable)()
+            with graphs.capture(g, rng=rng, pos=pos, pool='a pool', capture_error_mode='thread_local') as held:
+                log.append(('body', gc.isenabled()))
+            state = gc.isenabled()
+        finally:
+            gc.enable()
+        assert state is was
+        assert type(held).__name__ == 'Ctx' and ('tile_slots', 'init', (), {}) in log
+        assert [e for e in log if e[0] == 'call'] == [
+            ('call', 'tell_set_rng_step_ptr', rng), ('call', 'tell_set_pos_step_ptr', pos),
+            ('call', 'tell_set_rng_step_ptr', None), ('call', 'tell_set_pos_step_ptr', None)]    # (pos_next: never touched)
+        assert ('graph', 'init', (g,), {'pool': 'a pool', 'capture_error_mode': 'thread_local'}) in log
+        order = [e[:2] for e in log if e[1] in ('enter', 'exit') or e[0] in ('call', 'body')]
+        assert order == [('call', 'tell_set_rng_step_ptr'), ('call', 'tell_set_pos_step_ptr'), ('tile_slots', 'enter'),
+                         ('graph', 'enter'), ('bound_stream', 'enter'), ('body', False), ('bound_stream', 'exit'),
+                         ('graph', 'exit'), ('tile_slots', 'exit'), ('call', 'tell_set_rng_step_ptr'),
+                         ('call', 'tell_set_pos_step_ptr')]
+        assert all(e[2] is False for e in log if e[1] == 'enter')              # the collector is off before anything opens
+        # a body that raises: all three pointers back to None, every context left, the collector as before
+        try:
+            del log[:]
+            (gc.enable if was else gc.disable)()
+            with pytest.raises(RuntimeError, match='boom'):
+                with graphs.capture(g, rng=rng, pos=pos, pos_next=rng):
+                    raise RuntimeError('boom')
+            state = gc.isenabled()
+        finally:
+            gc.enable()
+        assert state is was
+        assert ('graph', 'init', (g,), {}) in log
+        assert [e[0] for e in log if e[1:2] == ('exit',)] == ['bound_stream', 'graph', 'tile_slots']
+        assert [e for e in log if e[0] == 'call'][3:] == [
+            ('call', 'tell_set_rng_step_ptr', None), ('call', 'tell_set_pos_step_ptr', None),
+            ('call', 'tell_set_pos_next_ptr', None)]
+    # a registration that fails: what was registered before it is still reset, no capture is opened
+    del log[:]
+
+    def failing(name, *args):
+        log.append(('call', name) + args)
+        if name == 'tell_set_pos_step_ptr' and args[0] is not None:
+            raise RuntimeError('no such word')
+    monkeypatch.setattr(graphs.hip, 'call', failing)
+    with pytest.raises(RuntimeError, match='no such word'):
+        with graphs.capture(g, rng=rng, pos=pos):
+            log.append(('body',))
+    assert ('body',) not in log and not [e for e in log if e[1:2] == ('enter',)]
+    assert ('call', 'tell_set_rng_step_ptr', None) in log and ('call', 'tell_set_pos_step_ptr', None) in log

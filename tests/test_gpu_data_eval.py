@@ -183,14 +183,14 @@ def test_evaluate_forward_through_lanes_equals_forward_batch_by_batch(beam):
 @pytest.mark.parametrize('beam', [1, 4])
 def test_several_decode_steps_per_graph_replay_equal_one_step_per_replay(beam):
     """From its first all-finished test on, a generation loop replays ONE graph that holds `check_every` consecutive decode
-    steps (CaptionModel._decode_stepper: step.multi - the bookkeeping launch that ends a recorded step leaves the next
+    steps (models/stepper.py DecodeStepper.multi - the bookkeeping launch that ends a recorded step leaves the next
     step's position offset in the device counter, so recorded steps chain on the device as single replays do).  Ids and
     log-probabilities must equal the one-step-per-replay loop bit for bit, over two generations of the same stepper (the
     second replays every graph from its first token on), and the multi-step graph must really have been recorded."""
     import tell_amd
     from tell_amd.build import build_model
     from tell_amd.data import synthetic_batch
-    from tell_amd.models import transformer as tr
+    from tell_amd.models import stepper as tr
     tell_amd.set_compute_dtype(torch.bfloat16)
     keep = tr.MULTI_STEP_GRAPHS
     try:
@@ -203,6 +203,9 @@ def test_several_decode_steps_per_graph_replay_equal_one_step_per_replay(beam):
         tr.MULTI_STEP_GRAPHS = False
         single = [model.generate(**clone(b), beam_size=beam) for b in batches]
         torch.cuda.synchronize()
+        # (flag off: the single-step graphs only - the toggle reaches the stepper)
+        assert model.__dict__['_decode_graphs'] and not [k for h in model.__dict__['_decode_graphs'].values() for k in h
+                                                         if isinstance(k, tuple) and k[:1] == ('multi',)]
         model.__dict__['_decode_graphs'].clear()
         tr.MULTI_STEP_GRAPHS = True
         for rep in range(2):

@@ -301,7 +301,7 @@ def test_fullsize_captured_sampling_step(fullsize):
     step per replay agree bit for bit.  (Graphs off, this model decodes layer by layer - other bf16 rounding points, so
     the eager comparison is test_golden_model_sampling_fp32's.)"""
     import tell_amd
-    from tell_amd.models import transformer as tr
+    from tell_amd.models import stepper as tr
     model, batches = fullsize
     b = batches[0]
 

@@ -31,7 +31,7 @@ MAX_ROWS = int(os.environ.get('TELL_DECODE_ROWS', '256'))
 # (csrc/decode.hip FOLD): 12 LayerNorm launches per step become one (the head's input).  TELL_DECODE_FOLD=0: round-4 form.
 FOLD = os.environ.get('TELL_DECODE_FOLD', '1') != '0'
 HEAD_GROUPED = os.environ.get('TELL_HEAD_GROUPED', '1') != '0'      # A/B aid: the two tail-table products as one launch
-# the generation loop's projected K / V cache HEAD-MAJOR ([B, H, S, 64]: models/transformer.py _decode_stepper); 0 = [S, B, E]
+# the generation loop's projected K / V cache HEAD-MAJOR ([B, H, S, 64]: models/stepper.py DecodeStepper); 0 = [S, B, E]
 KV_HEAD_MAJOR = os.environ.get('TELL_KV_HEAD_MAJOR', '1') != '0'
 # ... and, on top of it, PACKED for the matrix cores (PackedKV below; tell_attn_decode_packed); 0 = the VALU kernel on the
 # head-major cache
@@ -122,7 +122,7 @@ def usable(dec, X, incremental_state, kv_cache):
 
 
 _SPLIT_WS = {}
-CUR_LANE = [0]          # which decode lane is being issued / recorded (models/transformer.py): lanes own their split workspace
+CUR_LANE = [0]          # which decode lane is being issued / recorded (models/stepper.py): lanes own their split workspace
 
 
 def split_workspace(device):
@@ -322,7 +322,7 @@ class PackedKV:
     lanes, 8] (lane l = key l & 15 of the tile, elements half * 32 + (l >> 4) * 8 ..), vt [Bc, H, Sp / 32 blocks, 4 row tiles
     of the head width, 64 lanes, 8] (lane l = dimension tile * 16 + (l & 15), the block's keys 4 g + r | 16 + 4 g + r of k-group
     g = l >> 4 - the order the probabilities leave the score tiles in); mask [Bc, Sp] uint8 (1 = masked).  Built once per
-    stepper (models/transformer.py), refilled per caption batch by `fill` (one permuting copy per operand and caption batch -
+    DecodeStepper cache entry (models/stepper.py), refilled per caption batch by `fill` (one permuting copy per operand and caption batch -
     against a hundred decode steps that read it)."""
 
     def __init__(self, mod, S, Bc, device):

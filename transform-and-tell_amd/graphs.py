@@ -7,6 +7,7 @@ on: one launch per step.  Kernel arguments are frozen at capture; dropout stays 
 counter (`rng=True`, csrc/common.h tell_step_salt); inputs are copied into the captured static buffers.
 
 TELL_GRAPHS=0 disables capture; a failed capture falls back to eager execution for that signature."""
+import contextlib
 import os
 
 import torch
@@ -33,6 +34,28 @@ class no_gc:
         if self.was:
             gc.enable()
         return False
+
+
+@contextlib.contextmanager
+def capture(g, rng=None, pos=None, pos_next=None, **graph_kw):
+    """`with graphs.capture(g, rng=counter) as held:` - the one place a stream capture into the CUDAGraph g is opened.
+    rng / pos / pos_next: the device words the captured kernels read their dropout step, position offset and next position
+    offset from (tell_set_rng_step_ptr / tell_set_pos_step_ptr / tell_set_pos_next_ptr); those given are registered before
+    the capture opens and set back to None when it ends, however it ends.  graph_kw goes to torch.cuda.graph untouched.
+    Inside: the collector is off (no_gc) and launches go to the CAPTURING stream (hip.bound_stream).  Yields the
+    hip.tile_slots object - the tile-counter slots the captured resident GEMM launches took: keep it next to g when the
+    capture succeeded (dropping it gives the slots back to the free list)."""
+    ptrs = [(name, word) for name, word in (('tell_set_rng_step_ptr', rng), ('tell_set_pos_step_ptr', pos),
+                                            ('tell_set_pos_next_ptr', pos_next)) if word is not None]
+    try:
+        for name, word in ptrs:
+            hip.call(name, word)
+        with no_gc(), hip.tile_slots() as held, torch.cuda.graph(g, **graph_kw), hip.bound_stream():
+            yield held
+    finally:
+        for name, _ in ptrs:
+            hip.call(name, None)
+
 
 ENABLED = os.environ.get('TELL_GRAPHS', '1') != '0'
 
@@ -174,18 +197,11 @@ class GraphedCall:
                 static_in = x.clone()
                 counter = torch.zeros(1, dtype=torch.int32, device=x.device) if self.rng else None
                 g = torch.cuda.CUDAGraph()
-                held = hip.tile_slots()                 # tile-counter slots of the captured resident GEMMs: back to the
-                try:                                    # free list when this entry is evicted (held.__del__)
-                    if counter is not None:
-                        hip.call('tell_set_rng_step_ptr', counter)
-                    # thread_local: calls made by OTHER threads while we capture (the RCCL watchdog of a data-parallel
-                    # run polls events) must not invalidate the capture; everything captured is issued from this thread
-                    with no_gc(), held, torch.cuda.graph(g, capture_error_mode='thread_local'):
-                        with hip.bound_stream():        # launches must go to the CAPTURING stream
-                            static_out = self.fn(static_in)
-                finally:
-                    if counter is not None:
-                        hip.call('tell_set_rng_step_ptr', None)
+                # thread_local: calls made by OTHER threads while we capture (the RCCL watchdog of a data-parallel
+                # run polls events) must not invalidate the capture; everything captured is issued from this thread
+                # (held: tile-counter slots of the captured resident GEMMs, back to the free list when this entry is evicted)
+                with capture(g, rng=counter, capture_error_mode='thread_local') as held:
+                    static_out = self.fn(static_in)
                 slots.append({'graph': g, 'static_in': static_in, 'static_out': static_out, 'counter': counter,
                               'tile_slots': held})
             e.update(state='ready', slots=slots, turn=0, replays=1)

@@ -9,10 +9,7 @@ import torch.nn as nn
 
 from .. import graphs, ops, streams
 from ..common.registrable import Registrable
-
-# decode steps per graph replay once a generation loop is past its first all-finished test (CaptionModel._decode_stepper: multi)
-MULTI_STEP_GRAPHS = os.environ.get('TELL_MULTI_STEP_GRAPHS', '1') != '0'
-
+from .stepper import DecodeStepper
 
 _OVERLAP = os.environ.get('TELL_ENCODER_OVERLAP', '1') != '0'
 # where the PREFETCHED ResNet pass of the next batch is enqueued: 'own' = its side stream (three streams share the chip),
@@ -596,7 +593,7 @@ class CaptionModel(Model):
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
-                                                   **({'prefix': pfx} if pfx is not None else {}))
+                                                   prefix=pfx)
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
             out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)
@@ -635,7 +632,7 @@ class CaptionModel(Model):
     @torch.no_grad()
     def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
-        own captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
+        own DecodeStepper - captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
         chain fits beside the first.  The host alternates the lanes' graph replays (one replay per lane and token).  The
         encoders of a group of batches run first (eval mode: no randomness, results identical to `generate`).
@@ -679,15 +676,14 @@ class CaptionModel(Model):
                 if b.get('prefix') is not None and forward:
                     raise ValueError('prefix goes with generate, not with forward=True')
                 pfx = self._check_prefix(b.get('prefix'), caption_ids.shape[0])
-                pkw = {'prefix': pfx} if pfx is not None else {}
                 plens.append(pfx[1] if pfx is not None else None)
                 ev = torch.cuda.Event()
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, **pkw)
+                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx)
                          if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, **pkw))
+                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -768,15 +764,13 @@ class CaptionModel(Model):
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
                   prefix=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
-        pkw = {}
         if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
             self._check_prefix(prefix[0], caption_ids.shape[0], gen_len, eos)
-            pkw = {'prefix': prefix}
         if attention:
             # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
             # flow with the legacy need_attn export, which stays what it is)
             self._check_attention(beam_size)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, **pkw)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, prefix=prefix)
         if not hasattr(self.decoder, 'project_contexts'):
             # a recurrent decoder behind this model class (expt/*/3_lstm_roberta: `lstm_decoder_flattened`): greedy
             # decode that carries the LSTM state.  (The reference's loop feeds such a decoder only the last token with
@@ -787,9 +781,9 @@ class CaptionModel(Model):
             return lps, ids, []
         self._check_beam(beam_size)
         if beam_size > 1:
-            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, **pkw)
-        if self.fast_generation or opts is not None or pkw:  # (the search options live in the cached generator)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, **pkw)
+            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix)
+        if self.fast_generation or opts is not None or prefix is not None:  # (the search options live in the cached generator)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
 
     @staticmethod
@@ -803,6 +797,7 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None):
+        # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
                                               **({'prefix': prefix} if prefix is not None else {})))
 
@@ -831,14 +826,14 @@ class CaptionModel(Model):
         # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
         ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
-                                    **({'prefix': True} if prefix is not None else {}))
+                                    prefix=prefix is not None)
         if prefix is not None:
             step.set_prefix(*prefix)
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous()
         finished = cur[:, 0] == eos
-        fused = caption_ids.is_cuda and hasattr(step, 'cur')      # one bookkeeping launch per token (tell_greedy_update)
+        fused = caption_ids.is_cuda and step.static              # one bookkeeping launch per token (tell_greedy_update)
         if fused:
             # the histories live in STATIC buffers of the stepper (the bookkeeping launch is part of the captured step)
             bk = step.book('greedy', lambda: dict(
@@ -869,18 +864,7 @@ class CaptionModel(Model):
                 tok, lp = out
                 ops.call('tell_greedy_update', tok.reshape(B), lp.reshape(B), fin8, ids, ids.stride(0), lps, lps.stride(0),
                          done_step, step.cur, B, int(i), int(eos), inv_temp, step.counter_out, step_dev)
-        i = 0
-        while fused and i < gen_len:
-            # (the bookkeeping launch of step i - 1 left the position offset of step i in the device counter: no fill launch;
-            #  the host's part of a step is ONE graph replay - and from the first all-finished test on, of `check_every` steps)
-            n = check_every if (i >= check_every and i % check_every == 0 and i + check_every <= gen_len) else 1
-            if n == 1 or not step.multi(i, n, book):
-                n = 1
-                step(i, None, counter_set=i > 0, post=book)
-            i += n
-            yield i - 1
-            if i % check_every == 0 and bool(fin8.all()):
-                break
+            yield from step.steps(gen_len, check_every, book, fin8)
         for i in range(0 if fused else gen_len):
             if ban is not None:
                 step.ban_source(ids, finished.to(torch.uint8))
@@ -910,358 +894,14 @@ class CaptionModel(Model):
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
                         prefix=False):
-        """-> step(i, cur [B,1]) -> (token [B,1], log-prob [B,1]) - or, with topk=k, the k best (tokens [B,1,k],
-        log-probs [B,1,k]) of every row - for the cached greedy / beam generators; step.reorder(rows) permutes the
-        rows of the incremental state (beam search).
-
-        With graphs enabled the decode step (about 150 launches of a few microseconds each, host-bound when issued
-        one by one) is captured ONCE per (batch, context shapes) signature and replayed: every tensor it touches is
-        static - the DynamicConv input buffers have their final K-1 rows from the start (zero history), the
-        projected K/V and masks are copied into fixed buffers per caption batch, and the position offset comes from
-        the graph's device step counter (embed_finalize reads it, like the dropout kernels).
-
-        sample = (k, T): every step draws from the top k at temperature T (AdaptiveSoftmax.sample) with the seed in the
-        device word step.seed and the step index from the host (eager) or from the device counter (captured: every replay of
-        the single-step and the multi-step graphs draws fresh numbers); (k, T) is part of the capture's signature.
-
-        attention=True: the step also exports the head-averaged attention weights of every (layer, context) into static
-        fp32 buffers [gen_len, B, S + 2] (decode.AttnSink, handed out as step.attn), slot = step index: from the host in an
-        eager step, from the device counter in a captured one (single-step and multi-step graphs alike).  ('attn',) joins
-        the signature only then: the captures without maps are keyed and recorded exactly as before.
-
-        ban = (n, min_len, eos): the head's last launch becomes two - tell_decode_ban_list over the caller's histories
-        (step.ban_source(hist [B, L] int64, finished [B] uint8): static buffers of the caller's book when the step is
-        captured) with the step index from the host or from the device counter, then tell_adaptive_logprob_topk_banned (k = 1
-        for the greedy decode).  opts: the caller's whole option tuple; it joins the signature when given (a captured
-        bookkeeping launch differs with it), the default captures are keyed and recorded exactly as before.
-
-        prefix=True (caption completion): the stepper owns a forcing table - int64 [samples, gen_len] + int32 [samples], static,
-        filled per caption batch by step.set_prefix(tokens, plen) - and every head ends in tell_adaptive_logprob_forced with the
-        step index from the host or from the device counter.  ('prefix',) joins the signature: its own captured graph, one for
-        every prefix width; without it nothing is allocated, launched or keyed differently."""
-        dec = self.decoder
-        names = [n for layer_kv in kv[:1] for n in layer_kv]
-        n_hyp = max(int(topk), 1)
-        pfx = {}
-
-        def make_prefix(device):
-            return {'tab': torch.full((B // n_hyp, int(gen_len)), int(self.padding_idx), dtype=torch.long, device=device),
-                    'plen': torch.zeros(B // n_hyp, dtype=torch.int32, device=device)}
-
-        def set_prefix(tokens, plen):
-            if not pfx:
-                raise ValueError('set_prefix: the stepper was built without prefix=True')
-            if tokens.shape[0] != pfx['tab'].shape[0] or tokens.shape[1] > pfx['tab'].shape[1] or plen.numel() != tokens.shape[0]:
-                raise ValueError('set_prefix: tokens [%d, P <= %d] and plen [%d] expected' % (
-                    pfx['tab'].shape[0], pfx['tab'].shape[1], pfx['tab'].shape[0]))
-            pfx['tab'].fill_(int(self.padding_idx))
-            pfx['tab'][:, :tokens.shape[1]].copy_(tokens)
-            pfx['plen'].copy_(plen.to(torch.int32))
-
-        def fkw(sidx):
-            """The head's `force` argument at step index sidx (host int, or the device counter of a captured step)."""
-            return {'force': (pfx['tab'], pfx['plen'], None, n_hyp, sidx, int(self.padding_idx))} if pfx else {}
-        if ban is not None and (sample is not None or attention):
-            raise ValueError('no_repeat_ngram_size / min_len do not combine with sampling or attention maps')
-        ban_src = {}
-
-        def ban_source(hist, fin):
-            """The histories the ban lists are built from (before every eager step; once when the buffers are static)."""
-            if hist.dtype != torch.long or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1 or \
-                    hist.shape[1] > 256 or fin.dtype != torch.uint8 or fin.numel() != B or not fin.is_contiguous():
-                raise ValueError('ban_source: hist int64 [%d, L <= 256] and finished uint8 [%d] expected' % (B, B))
-            ban_src['hist'], ban_src['fin'] = hist, fin
-            if 'ban' not in ban_src or ban_src['ban'].shape[1] < hist.shape[1] + 1 or ban_src['ban'].device != hist.device:
-                ban_src['ban'] = torch.zeros(B, hist.shape[1] + 1, dtype=torch.int32, device=hist.device)
-                ban_src['n_ban'] = torch.zeros(B, dtype=torch.int32, device=hist.device)
-
-        def banned_head(x, sidx):
-            hist = ban_src['hist']
-            step_dev = sidx if torch.is_tensor(sidx) else None
-            ops.call('tell_decode_ban_list', hist, hist.stride(0), hist.shape[1], ban_src['fin'], B,
-                     0 if step_dev is not None else int(sidx), step_dev, int(ban[0]), int(ban[1]), int(ban[2]),
-                     ban_src['ban'], ban_src['ban'].stride(0), ban_src['n_ban'])
-            tok, lp = dec.adaptive_softmax.topk(x, max(int(topk), 1), ban=(ban_src['ban'], ban_src['n_ban']), **fkw(sidx))
-            return (tok, lp) if topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
-
-        def make_sink(device):
-            from ..decode import AttnSink
-            return AttnSink([{n: torch.zeros(int(gen_len), B, int(pair[0].shape[0]) + 2, dtype=torch.float32, device=device)
-                              for n, pair in lk.items()} for lk in kv], gen_len)
-
-        def make_head(seed_dev):
-            if ban is not None:
-                return banned_head
-            if sample is not None:
-                topp = sample[2] if len(sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
-                if topp is not None:
-                    return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, topp=topp,
-                                                                       **fkw(sidx))
-                return lambda x, sidx: dec.adaptive_softmax.sample(x, sample[0], sample[1], seed_dev, sidx, **fkw(sidx))
-            if topk:
-                return lambda x, sidx: dec.adaptive_softmax.topk(x, topk, **fkw(sidx))
-            return lambda x, sidx: dec.adaptive_softmax.greedy(x, **fkw(sidx))
-        if not graphs.ENABLED or self.training or not torch.is_tensor(kv[0][names[0]][0]) or \
-                not kv[0][names[0]][0].is_cuda:
-            state = {}
-            seed_word = torch.zeros(1, dtype=torch.int32, device=next(dec.parameters()).device)
-            head = make_head(seed_word)
-            if prefix:
-                pfx.update(make_prefix(seed_word.device))
-
-            sink = make_sink(seed_word.device) if attention else None
-
-            def eager_step(i, cur):
-                kw = {'attn_sink': sink.at(int(i))} if sink is not None else {}
-                return head(dec({self.index: cur}, contexts, incremental_state=state, kv_cache=kv, **kw)[0][:, -1:], int(i))
-            eager_step.attn = sink
-            eager_step.reorder = lambda rows: dec.reorder_incremental_state(state, rows)
-            eager_step.seed = seed_word
-            eager_step.ban_source = ban_source
-            eager_step.set_prefix = set_prefix
-            return eager_step
-        dev, dtype = kv[0][names[0]][0].device, kv[0][names[0]][0].dtype
-        # lane: decode loops that are in flight TOGETHER (generate_lanes: two caption batches decoded on two streams) own
-        # their graphs, static buffers, counters and split-reduction workspace
-        sig = (B, dtype, topk, int(gen_len), tuple((n, tuple(kv[0][n][0].shape), tuple(kv[0][n][1].shape)) for n in names),
-               dec.embedder.token_embedder_position.weights.data_ptr(), int(lane))
-        if sample is not None:                                    # (greedy and beam signatures are unchanged)
-            sig = sig + ((('sample', int(sample[0]), float(sample[1])) if len(sample) == 2 else
-                          ('nucleus', int(sample[0]), float(sample[1]), float(sample[2]))),)
-        if attention:                                             # (... and so are the sampling ones)
-            sig = sig + (('attn',),)
-        if ban is not None or opts is not None:                   # (... and the ones without search options)
-            sig = sig + (('search', tuple(ban or ()), tuple(opts or ())),)
-        if prefix:                                                # (... and every one without a forced prefix)
-            sig = sig + (('prefix',),)
-        cache = self.__dict__.setdefault('_decode_graphs', {})
-        # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
-        # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
-        # load_state_dict): every capture belongs to one state of the weights and is dropped with it
-        stamp = (ops.rt.weights_epoch(), sum(p._version for p in dec.parameters()))
-        if self.__dict__.get('_decode_graphs_stamp') != stamp:
-            cache.clear()
-            self.__dict__['_decode_graphs_stamp'] = stamp
-        h = cache.get(sig)
-        if h is not None:
-            ban_src = h['ban_src']                                # (the captured launches hold these buffers' addresses)
-        if h is None:
-            if len(cache) >= graphs.MAX_SIGNATURES:
-                cache.pop(next(iter(cache)))
-            h = cache[sig] = {
-                # counter[0]: the position offset the kernels of a replay read; counter[1]: the NEXT step's offset when
-                # the bookkeeping launch is part of the captured step (`ig`, below)
-                'graph': None, 'counter': torch.zeros(2, dtype=torch.int32, device=dev), 'book': {}, 'ban_src': ban_src,
-                'seed': torch.zeros(1, dtype=torch.int32, device=dev),      # the sampling seed (written per caption batch)
-                'cur': torch.zeros(B, 1, dtype=torch.long, device=dev),
-                'kv': None,
-                # (key-padding masks as the uint8 the attention kernels read: converted once per caption batch)
-                'ctx': {k: torch.empty_like(v, dtype=torch.uint8 if v.dtype == torch.bool else v.dtype)
-                        for k, v in contexts.items() if torch.is_tensor(v)},
-                'state': dec.static_incremental_state(B, dev, dtype, beam=bool(topk)),
-            }
-            po = dec.embedder.token_embedder_position            # the table must already cover the longest caption
-            po.next_start(gen_len + 2, None)
-            # The static copy of the projected K / V.  Where the weight-streaming step takes this batch (decode.usable: all
-            # four attentions of a layer are one tell_attn_decode launch) the copy is HEAD-MAJOR - [B, H, S, 64], handed on
-            # as [S, B, H, 64] views: the keys a (sample, head) workgroup walks are one contiguous block instead of 128-byte
-            # pieces a whole [B, 2E] projection row (128 KB at B = 32) apart.  The re-layout rides on the copy into the
-            # static buffers that the captured step needs anyway, once per caption batch.
-            from .. import decode as _dec
-            probe = torch.empty(1, B, dec.embedder.get_output_dim(), dtype=dtype, device=dev)
-            hm = _dec.KV_HEAD_MAJOR and dtype == torch.bfloat16 and _dec.usable(dec, probe, h['state'], kv)
-
-            def static_like(t, mod):
-                if hm and t.shape[0] > 0 and t.dim() == 3 and t.shape[2] == mod.num_heads * 64:
-                    S_, Bc, H_ = t.shape[0], t.shape[1], mod.num_heads
-                    return torch.empty(Bc, H_, S_, 64, dtype=t.dtype, device=t.device).permute(2, 0, 1, 3)
-                return torch.empty_like(t)
-            # (measured, B = 32: packed 28.6 -> 22.6-24.9 us per launch at beam 4; with ONE hypothesis per sample the VALU kernel on
-            #  the head-major cache is the faster one, 18.7 against 20.4 us - packed from two hypotheses per sample on)
-            n_cached = kv[0][names[0]][0].shape[1] if kv[0][names[0]][0].dim() == 3 else B
-            several = B >= _dec.PACKED_MIN_HYP * max(int(n_cached), 1)
-            layer_pk = (B > _dec.MAX_ROWS and dtype == torch.bfloat16 and bool(h['state'].get('_ring')) and
-                        _dec.layer_path_takes_packed(dec))     # (the layer-by-layer step above MAX_ROWS rows)
-            if _dec.KV_PACKED and several and (hm or layer_pk):
-                # ... or PACKED for the matrix cores: keys head-major with the two virtual keys appended, values transposed
-                # and permuted (decode.PackedKV); one launch per layer reads all four contexts (tell_attn_decode_packed)
-                h['kv'] = [{n: _dec.PackedKV(layer.context_attns[n], pair[0].shape[0], pair[0].shape[1], dev)
-                            for n, pair in lk.items()} for lk, layer in zip(kv, dec.layers)]
-            else:
-                h['kv'] = [{n: tuple(static_like(t, layer.context_attns[n]) for t in pair) for n, pair in lk.items()}
-                           for lk, layer in zip(kv, dec.layers)]
-            # in-graph bookkeeping needs the step's first kernel to be tell_embed_gather_step (it publishes the counter)
-            if attention:
-                if topk:
-                    raise ValueError('attention maps: one hypothesis per sample only (no beam search)')
-                h['attn'] = make_sink(dev)
-            h['ig'] = bool(_dec.IN_GRAPH_BOOK and dtype == torch.bfloat16 and _dec.usable(dec, probe, h['state'], kv) and
-                           _dec.embed_usable(dec.embedder, h['cur'], h['state']))
-            if prefix:
-                h['pfx'] = make_prefix(dev)
-        if prefix:
-            pfx.update(h['pfx'])                                  # (the captured launches hold these buffers' addresses)
-        for lk, ls in zip(kv, h['kv']):
-            for n, pair in lk.items():
-                if not isinstance(ls[n], tuple):                  # decode.PackedKV
-                    mk = contexts.get(n + '_mask')
-                    ls[n].fill(pair[0], pair[1], mk)
-                    continue
-                for t, s in zip(pair, ls[n]):
-                    s.copy_(t.view(s.shape) if s.dim() == 4 else t)
-        for k, s in h['ctx'].items():
-            s.copy_(contexts[k])
-        dec.reset_static_state(h['state'])
-        pos_key = dec.embedder.token_embedder_position._state_key
-        h['state'].pop(pos_key, None)
-
-        head = make_head(h['seed'])
-
-        c_cur, c_next = h['counter'][0:1], h['counter'][1:2]
-        # where a bookkeeping launch leaves the next step's offset: the word the embedder's kernel reads (in-graph
-        # bookkeeping), or the counter itself
-        c_out = c_next if h['ig'] else c_cur
-
-        def run(sidx):
-            """sidx: the step index for a sampling head - the host's int, or c_cur inside a captured step (i - 1 there)."""
-            from .. import decode as _dec2
-            prev_lane = _dec2.CUR_LANE[0]
-            _dec2.CUR_LANE[0] = int(lane)
-            try:
-                kw = {}
-                if attention:
-                    # slot = step index: the host's in an eager step; captured, the counter holds i - 1 (base 1)
-                    kw['attn_sink'] = h['attn'].at(1, sidx) if torch.is_tensor(sidx) else h['attn'].at(int(sidx))
-                out = dec({self.index: h['cur']}, h['ctx'], incremental_state=h['state'], kv_cache=h['kv'], **kw)
-                return head(out[0][:, -1:], sidx)
-            finally:
-                _dec2.CUR_LANE[0] = prev_lane
-
-        def eager(i, post):
-            res = run(int(i))
-            if post is not None:
-                post(res, i, None)
-            return res
-
-        def step(i, cur, counter_set=False, post=None):
-            """post(out, i, step_dev): the caller's per-token bookkeeping launch (over static buffers: step.book).  With
-            in-graph bookkeeping it is recorded as the LAST launch of the captured step."""
-            if cur is not None:                                   # (None: the caller already wrote step.cur)
-                h['cur'].copy_(cur)
-            if h['graph'] is None and i != 1:
-                return eager(i, post)                             # warm step(s) before the capture, or fallback
-            if h['graph'] is None:                                # i == 1: the host position state is 1 now
-                inside = post is not None and h['ig']
-                # the host's part of the step's position state as THIS capture sees it (step.multi records further steps
-                # with the same constants: the device counter is what moves a recorded step along)
-                h['host_ints'] = {k_: v_ for k_, v_ in h['state'].items() if isinstance(v_, int) and not isinstance(v_, bool)}
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    try:
-                        ops.call('tell_set_rng_step_ptr', c_cur)
-                        ops.call('tell_set_pos_step_ptr', c_cur)
-                        if inside:
-                            ops.call('tell_set_pos_next_ptr', c_next)
-                        # (the captured step's resident GEMM launches keep their tile-counter slots until this entry is
-                        #  dropped - `held` gives them back, like StepGraph / GraphedCall do)
-                        with graphs.no_gc(), ops.hip.tile_slots() as held, torch.cuda.graph(g):
-                            with ops.hip.bound_stream():
-                                h['out'] = run(c_cur)
-                                if inside:
-                                    post(h['out'], i, c_cur)
-                        h['tile_slots'] = held
-                    finally:
-                        ops.call('tell_set_rng_step_ptr', None)
-                        ops.call('tell_set_pos_step_ptr', None)
-                        ops.call('tell_set_pos_next_ptr', None)
-                    h['graph'], h['base'], h['graph_has_post'] = g, 1, inside
-                except Exception as exc:                          # noqa: BLE001 - stay eager for this signature
-                    h['graph'], h['error'] = False, repr(exc)
-                    return eager(i, post)
-            if h['graph'] is False:
-                return eager(i, post)
-            if not counter_set:
-                # position offset of this step (may be -1): into the word the step's first kernel reads
-                (c_next if h.get('graph_has_post') else c_cur).fill_(i - h['base'])
-            h['graph'].replay()
-            if post is not None and not h.get('graph_has_post'):
-                post(h['out'], i, None)
-            return h['out']
-
-        def multi(i, n, post):
-            """Steps i .. i + n - 1 as ONE graph replay (n consecutive steps recorded into one graph: the bookkeeping launch
-            that ends a recorded step leaves the position offset of the next one in the device counter, so the steps chain
-            on the device exactly as n single replays would - what goes is the per-replay cost between them, ~25 us of a
-            360-490 us step).  Needs the single-step graph with in-graph bookkeeping (captured at step 1) and the counter
-            already set by step i - 1's bookkeeping launch.  -> False: not available, issue the steps one by one."""
-            if not h.get('graph') or not h.get('graph_has_post') or post is None or i < 2 or not MULTI_STEP_GRAPHS:
-                return False
-            key = ('multi', int(n))
-            g = h.get(key)
-            if g is None:
-                saved = {k_: h['state'].get(k_) for k_ in h['host_ints']}
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    try:
-                        ops.call('tell_set_rng_step_ptr', c_cur)
-                        ops.call('tell_set_pos_step_ptr', c_cur)
-                        ops.call('tell_set_pos_next_ptr', c_next)
-                        with graphs.no_gc(), ops.hip.tile_slots() as held, torch.cuda.graph(g):
-                            with ops.hip.bound_stream():
-                                for j in range(int(n)):
-                                    h['state'].update(h['host_ints'])   # the constants of the single-step capture
-                                    post(run(c_cur), i + j, c_cur)
-                        h[key + ('slots',)] = held
-                    finally:
-                        ops.call('tell_set_rng_step_ptr', None)
-                        ops.call('tell_set_pos_step_ptr', None)
-                        ops.call('tell_set_pos_next_ptr', None)
-                        h['state'].update(saved)
-                    h[key] = g
-                except Exception as exc:                          # noqa: BLE001 - keep the single-step replays
-                    h[key], h['multi_error'] = False, repr(exc)
-                    return False
-            if g is False:
-                return False
-            g.replay()
-            return True
-
-        def book(kind, make):
-            if kind not in h['book']:
-                h['book'][kind] = make()
-            return h['book'][kind]
-
-        def reorder(rows, group=0):                               # in place: the buffers are part of the graph
-            if h['state'].get('_ring'):                           # rings: only the ancestor table changes
-                dec.reorder_incremental_state(h['state'], rows)
-                return
-            bufs = [s for k_, s in h['state'].items() if 'Conv1dTBC' in k_ and torch.is_tensor(s) and s.shape[0] > 0]
-            if (group and 1 <= group <= 8 and bufs and all(s.dtype == torch.bfloat16 and s.is_contiguous() and
-                                                           s.shape[2] == 1024 for s in bufs) and len(bufs) <= 8):
-                # rows[r] lies inside r's group of `group` hypotheses: every layer's buffer in ONE launch
-                ops.call('tell_reorder_rows', len(bufs), ops._ptr_array(bufs), ops._int_array([s.shape[0] for s in bufs]),
-                         rows, bufs[0].shape[1], 1024, int(group))
-                return
-            for s in bufs:
-                s.copy_(s.index_select(1, rows))
-        step.reorder = reorder
-        step.multi = multi
-        step.cur = h['cur']
-        step.book = book
-        step.seed = h['seed']
-        step.attn = h.get('attn')
-        step.ban_source = ban_source
-        step.set_prefix = set_prefix
-        step.sig = sig
-        step.handle = h
-        step.counter_out = c_out                                  # (base 1: the offset of step i is i - 1)
-        step.back = h['state'].get('_back')                       # ancestor table of the DynamicConv rings, or None
-        return step
+        """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
+        the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
+        return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
+                             opts=opts, prefix=prefix)
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
-        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best,
-                                            **({'prefix': prefix} if prefix is not None else {})))
+        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best, prefix=prefix))
 
     def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
         """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
@@ -1290,13 +930,12 @@ class CaptionModel(Model):
         ctx = {k_: v_ for k_, v_ in contexts.items() if torch.is_tensor(v_)}
         kv = dec.project_contexts(contexts)
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
-                                    opts=(opts + (int(eos),)) if opts is not None else None,
-                                    **({'prefix': True} if prefix is not None else {}))
+                                    opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None)
         if prefix is not None:
             step.set_prefix(*prefix)
         cur = rep(caption_ids[:, 0:1], 0)
         finished = (cur[:, 0] == eos).view(B, K)
-        fused = caption_ids.is_cuda and hasattr(step, 'cur') and K <= 8 and gen_len + 1 <= 256
+        fused = caption_ids.is_cuda and step.static and K <= 8 and gen_len + 1 <= 256
         if fused:
             bk = step.book('beam', lambda: dict(
                 cum=torch.empty(B, K, dtype=torch.float32, device=dev), fin8=torch.empty(B, K, dtype=torch.uint8, device=dev),
@@ -1345,22 +984,15 @@ class CaptionModel(Model):
                     return
                 ops.call('tell_beam_update', tk, lp, cum, fin8, seqs, lps, step.cur, rows, B, K, gen_len + 1, int(i), int(pad),
                          int(eos), inv_temp, step.back, step.back.shape[0] if ring else 0, step.counter_out, step_dev)
-            i = 0
-            while i < gen_len:
+
+            def host_book(out, i):
                 # (time-ordered buffers - fp32 parity mode: the bookkeeping stays a host-side launch and one more launch
                 #  re-orders every layer's rows by parent)
-                n = check_every if (ring and i >= check_every and i % check_every == 0 and i + check_every <= gen_len) else 1
-                if n == 1 or not step.multi(i, n, book):
-                    n = 1
-                    out = step(i, None, counter_set=i > 0, post=book if ring else None)
-                    if not ring:
-                        book(out, i, None)
-                        step.reorder(rows, K)
-                i += n
-                yield i - 1
-                if i % check_every == 0 and bool(fin8.all()):
-                    n_steps = i
-                    break
+                book(out, i, None)
+                step.reorder(rows, K)
+            # (multi-step replays need the bookkeeping inside the captured step: ring buffers only)
+            n_steps = yield from step.steps(gen_len, check_every, book if ring else None, fin8, multi=ring,
+                                            after=None if ring else host_book)
         for i in range(0 if fused else gen_len):
             # each hypothesis contributes its own K best tokens (the best K of K x V always lie among them)
             if ban is not None:

@@ -25,7 +25,7 @@ import os
 
 import torch
 
-from .. import graphs, hip, ops
+from .. import graphs, ops
 from .. import runtime as rt
 
 ENABLED = os.environ.get('TELL_STEP_GRAPH', '1') != '0'
@@ -153,27 +153,25 @@ class StepGraph:
         counter = torch.zeros(1, dtype=torch.int32, device=dev)
         saved = (model.n_samples, model.n_batches, tr.optimizer.step_count)
         g = torch.cuda.CUDAGraph()
-        held = hip.tile_slots()                 # (csrc/gemm.hip tile counters: released when this entry is dropped)
         tr._capturing = True
         try:
             ops.drop_trainable_cache()          # working weights of trainable parameters are rebuilt inside the graph
-            hip.call('tell_set_rng_step_ptr', counter)
             if self.shared_pool and self.pool is None:
                 self.pool = torch.cuda.graph_pool_handle()
-            with graphs.no_gc(), held, torch.cuda.graph(g, pool=self.pool if self.shared_pool else None,
-                                                        capture_error_mode='thread_local'):
-                with hip.bound_stream():
-                    encs = EncodedBatch()
-                    encs.stack, encs.x_image = st_big
-                    encs.article_mask = st_small['ctx'] == model.padding_idx
-                    kw = {k: st_small[k] for k in ('face_embeds', 'obj_embeds') if k in st_small}
-                    out = model(context={idx: st_small['ctx']}, image=batch['image'], caption={idx: st_small['cap']},
-                                encoded=encs, **kw)
-                    loss = out['loss']
-                    tr._flag_loss(loss)
-                    tr._backward(loss)
-                    if not tr.dp and not tr.defer_update:
-                        tr.optimizer.launch(grad_scale=1.0, zero_grad=True, skip=tr.skip)
+            # (held: csrc/gemm.hip tile counters, released when this entry is dropped)
+            with graphs.capture(g, rng=counter, pool=self.pool if self.shared_pool else None,
+                                capture_error_mode='thread_local') as held:
+                encs = EncodedBatch()
+                encs.stack, encs.x_image = st_big
+                encs.article_mask = st_small['ctx'] == model.padding_idx
+                kw = {k: st_small[k] for k in ('face_embeds', 'obj_embeds') if k in st_small}
+                out = model(context={idx: st_small['ctx']}, image=batch['image'], caption={idx: st_small['cap']},
+                            encoded=encs, **kw)
+                loss = out['loss']
+                tr._flag_loss(loss)
+                tr._backward(loss)
+                if not tr.dp and not tr.defer_update:
+                    tr.optimizer.launch(grad_scale=1.0, zero_grad=True, skip=tr.skip)
             e.update(state='ready', graph=g, small=st_small, big=st_big, counter=counter, replays=1,
                      loss=loss.detach(), sample_size=out['sample_size'], tile_slots=held)
         except Exception as exc:                # noqa: BLE001 - any capture problem -> this signature stays eager
@@ -183,7 +181,6 @@ class StepGraph:
                 raise
         finally:
             tr._capturing = False
-            hip.call('tell_set_rng_step_ptr', None)
             model.n_samples, model.n_batches, tr.optimizer.step_count = saved
             ops.drop_trainable_cache()          # entries made while capturing point into the graph's pool
             rt.bump_weights_epoch()
