@@ -612,6 +612,39 @@ int tell_adaptive_logprob_nucleus(const float* head, long ld_head, int c0, int n
 int tell_nucleus_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp, float p,
                             const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,
                             float* lps, tell_stream_t stream);
+/* two more truncation rules over the full adaptive softmax, no top-k cut.  Shared, per row: lp_t as
+ * in tell_adaptive_logprob_argmax; a_t = (lp_t - lp_max) * inv_temp, one fp32 subtract then one fp32 multiply; w_t =
+ * exp(a_t).  The draw (u(seed, row, step) scaled by the members' weight sum, the first member IN TOKEN-ID ORDER whose
+ * running weight exceeds it, the last member if rounding leaves none), tokens / lps (the pick's lp WITHOUT the temperature),
+ * row_ids, step, step_dev, seed_dev, the register / streaming forms and vocab < 2^19 as for tell_adaptive_logprob_nucleus.
+ *
+ * min-p: a token is a member iff a_t >= log_minp, log_minp = float32(log(m)) formed by the caller in fp64, 0 < m <= 1 (so
+ * log_minp <= 0).  The comparison follows the multiply directly - nothing can be contracted, numpy float32 restates the
+ * member set exactly.  The best token (a = 0) is always a member; m = 1 keeps the tokens tied with the maximum.  No
+ * threshold search: the maximum, the members' weight sum (64-bit fixed point, as the nucleus masses), the id-order draw.
+ * nuc_size (optional): the number of members per row. */
+int tell_adaptive_logprob_minp(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                               int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                               int rows, float inv_temp, float log_minp, const uint32_t* seed_dev, const int* row_ids,
+                               int step, const int* step_dev, int* tokens, float* lps, int* nuc_size,
+                               tell_stream_t stream);
+/* locally typical sampling, 0 < tau <= 1:
+ *   1. W = sum w_t and S = sum w_t * a_t, fp32 in a fixed order (a thread's elements in static order, the wave, the 16 waves
+ *      in order); c = -S / W >= 0: the entropy of the tempered distribution minus the surprise of its best token;
+ *   2. d_t = |a_t + c| (the add is a single rounded fp32 add, never an FMA with the multiply of a_t: given c, numpy float32
+ *      restates d_t bit for bit): the distance between the token's surprise and the entropy;
+ *   3. members: the shortest prefix of the order (d ascending, lower id first on ties) whose weight reaches tau * (total
+ *      weight); at least one token; tokens that tie at the boundary enter in id order until the mass is reached.  The
+ *      boundary is found as the nucleus' (exact 2^44 fixed-point histogram masses over a quarter-nat digit of d, then the
+ *      bytes of the key); the key of a token is ~bits(d): larger is better, never 0.  The masses weigh a token with
+ *      exp((a_t + c) - c), i.e. a_t after one rounding at the size of c (a relative 2^-24 * c of the weight);
+ *   4. the draw and the outputs as above.
+ * nuc_size, nuc_key (the key of the worst member) and typ_c (fp32, the c of step 1) are optional, NULL in the product path. */
+int tell_adaptive_logprob_typical(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                  int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                  int rows, float inv_temp, float tau, const uint32_t* seed_dev, const int* row_ids,
+                                  int step, const int* step_dev, int* tokens, float* lps, int* nuc_size,
+                                  uint32_t* nuc_key, float* typ_c, tell_stream_t stream);
 
 /* per-token bookkeeping of the greedy decode loop (transformer_faces_objects.py:443-494) for all B rows in one launch:
    unfinished rows record tok / lp * inv_temp at step i, rows emitting eos are marked finished (done_step = i + 1),

@@ -925,6 +925,7 @@ struct SampleArgs {
   const uint32_t* seed_dev; const int* row_ids; int step; const int* step_dev;
   int* tokens; float* lps;
   float topp; int* nuc_size; uint32_t* nuc_key;       // the nucleus entry point only (tell_adaptive_logprob_nucleus)
+  float* typ_c;                                       // tell_adaptive_logprob_typical only (topp: its tau; min-p: log_minp)
 };
 struct SampleSmem {
   int hist[256];
@@ -1358,6 +1359,7 @@ struct NucleusSmem {
   uint32_t klo, khi;                                            // the keys of the crossing coarse bin span klo .. khi
   float ref_max;                                                // the row's maximum log-prob, re-read in every pass (see nucleus_row)
   int best, last, cnt;
+  uint32_t tau;                                                 // the typical rule's boundary key, re-read in its id passes
 };
 __device__ __forceinline__ float nuc_weight(uint32_t key, float lmax, float inv_temp) {
   return __expf((key_lp(key) - lmax) * inv_temp);
@@ -1367,6 +1369,51 @@ __device__ __forceinline__ unsigned long long nuc_fx(float w) { return (unsigned
 __device__ __forceinline__ int nuc_coarse(uint32_t key, float lmax, float inv_temp) {
   return 255 - (int)fminf((lmax - key_lp(key)) * inv_temp * 4.f, 255.f);
 }
+// What a rule (nucleus, locally typical, min-p: DESIGN.md sections 14 and 19) makes of the 32-bit word a row element is held
+// as (0 = not a token) and of the row's reference value `ref` (NucleusSmem::ref_max): the search key (larger = better), the
+// weight, the coarse digit (monotone in the key) and the key as reported.  KIND picks the membership test of nucleus_draw_row.
+struct NucleusRule {                                            // word = lp_key(lp); ref = the row's maximum log-prob
+  static constexpr int KIND = 0;
+  static __device__ __forceinline__ uint32_t cmp(uint32_t w) { return w; }
+  static __device__ __forceinline__ float weight(uint32_t w, float ref, float inv_temp) { return nuc_weight(w, ref, inv_temp); }
+  static __device__ __forceinline__ int coarse(uint32_t w, float ref, float inv_temp) { return nuc_coarse(w, ref, inv_temp); }
+  static __device__ __forceinline__ uint32_t report(uint32_t tau) { return tau; }
+};
+// word = typ_word(x), x = a + c the token's surprise relative to the entropy (a = (lp - lp_max) * inv_temp, c = ref): bit 31
+// the sign of x, bits 0..30 the inverted bits of d = |x| - a non-negative float orders as its bit pattern, inverted the
+// smaller d is the larger key, and no d gives 0.  The weight exp(a) is recovered as exp(x - c).
+__device__ __forceinline__ uint32_t typ_word(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) | (~u & 0x7fffffffu);
+}
+// a = (lp - lmax) * inv_temp and x = a + c, each operation rounded on its own: contraction is switched off here (the
+// __fmul_rn / __fadd_rn of this toolchain are plain operators, which the compiler fuses into an FMA like any others), so
+// that numpy float32 restates a and x bit for bit
+__device__ __forceinline__ float typ_a(float lp, float lmax, float inv_temp) {
+#pragma clang fp contract(off)
+  const float s = lp - lmax;
+  return s * inv_temp;
+}
+__device__ __forceinline__ float typ_x(float lp, float lmax, float inv_temp, float c) {
+#pragma clang fp contract(off)
+  const float s = lp - lmax;
+  const float a = s * inv_temp;
+  return a + c;
+}
+struct TypicalRule {
+  static constexpr int KIND = 1;
+  static __device__ __forceinline__ uint32_t cmp(uint32_t w) { return w & 0x7fffffffu; }
+  static __device__ __forceinline__ float weight(uint32_t w, float ref, float) {
+    return __expf(__uint_as_float((w & 0x80000000u) | (~w & 0x7fffffffu)) - ref);
+  }
+  static __device__ __forceinline__ int coarse(uint32_t w, float, float) {      // 255 - quarter nats of d, clamped
+    return 255 - (int)fminf(__uint_as_float(~w & 0x7fffffffu) * 4.f, 255.f);
+  }
+  static __device__ __forceinline__ uint32_t report(uint32_t tau) { return tau | 0x80000000u; }     // ~bits(d)
+};
+struct MinpRule : NucleusRule {                                 // words and weights of the nucleus; tau = the bits of log_minp
+  static constexpr int KIND = 2;
+};
 // hist complete after the first barrier; bins taken from 255 down: the bin in which the running mass reaches the target.
 // topp > 0 (the first pass): the target is set here, ceil(topp * total mass), at least 1.  Wave 0 decides, everyone reads.
 __device__ __forceinline__ void nucleus_decide(NucleusSmem& sm, float topp) {
@@ -1396,12 +1443,9 @@ __device__ __forceinline__ void nucleus_decide(NucleusSmem& sm, float topp) {
   }
   __syncthreads();
 }
-template <class Each, class Sweep>
-__device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep, uint32_t thread_max, int row,
-                                            const SampleArgs& a, NucleusSmem& sm) {
+// the row's maximum key from the threads' maxima; leaves hist zeroed and best / last / cnt / klo / khi reset (one barrier)
+__device__ __forceinline__ uint32_t nucleus_row_max(uint32_t thread_max, NucleusSmem& sm) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float inv_temp = a.inv_temp;
-  // the maximum key
   uint32_t kmax = thread_max;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
@@ -1411,70 +1455,17 @@ __device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep
   __syncthreads();
 #pragma unroll
   for (int w = 0; w < 16; ++w) kmax = max(kmax, (uint32_t)sm.ttot[0][w]);
-  // 1. the coarse digit over the whole row
-  {
-    const float lmax = key_lp(kmax);
-    if (tid == 0) sm.ref_max = lmax;
-    each([&](uint32_t key, int) {
-      const unsigned long long fx = key ? nuc_fx(nuc_weight(key, lmax, inv_temp)) : 0ull;
-      if (fx) atomicAdd(&sm.hist[nuc_coarse(key, lmax, inv_temp)], fx);          // (a peaked row: most of the vocabulary is 0)
-    });
-  }
-  nucleus_decide(sm, a.topp);
-  unsigned long long above = sm.above;
-  // the crossing coarse bin is a key range (the digit is monotone in the key): klo .. khi, the bin's smallest and largest key
-  {
-    const int g = sm.sel;
-    const float lmax = sm.ref_max;
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-    each([&](uint32_t key, int) {
-      if (key && nuc_coarse(key, lmax, inv_temp) == g) { lo = min(lo, key); hi = max(hi, key); }
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
-      hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
-    }
-    if (lane == 0) { atomicMin(&sm.klo, lo); atomicMax(&sm.khi, hi); }
-    __syncthreads();
-  }
-  // 2. the key's bytes inside that range.  A byte that klo and khi share (with all bytes above it) is the same in every
-  //    participant: its pass is skipped - typically the top byte (a quarter nat rarely spans two exponents), often
-  //    the next.  klo / khi / ref_max are re-read from LDS in every pass: filters and weights computed from register values
-  //    are loop-invariant, and the compiler would keep 64 of each per thread of the register form live across the passes
-  //    (293 VGPRs spilled).
-  uint32_t pre = 0, msk = 0;
-  for (int sh = 24; sh >= 0; sh -= 8) {
-    if (((sm.klo ^ sm.khi) >> sh) == 0) {                        // (uniform)
-      pre |= sm.klo & (0xFFu << sh);
-      msk |= 0xFFu << sh;
-      continue;
-    }
-    if (tid < 256) sm.hist[tid] = 0;
-    __syncthreads();
-    const uint32_t klo = sm.klo, khi = sm.khi;
-    const float lmax = sm.ref_max;
-    each([&](uint32_t key, int) {
-      if (key >= klo && key <= khi && (key & msk) == pre) {
-        const unsigned long long fx = nuc_fx(nuc_weight(key, lmax, inv_temp));
-        if (fx) atomicAdd(&sm.hist[(key >> sh) & 255], fx);
-      }
-    });
-    nucleus_decide(sm, 0.f);
-    pre |= (uint32_t)sm.sel << sh;
-    msk |= 0xFFu << sh;
-    above += sm.above;
-  }
-  // tau = pre: `ties` keys equal it, the prefix takes the m lowest ids of them
-  const uint32_t tau = pre;
+  return kmax;
+}
+// 3. id order, shared by the rules.  Members by KIND - nucleus: key > tau, and of the keys equal to tau all (!cut) or the m
+// lowest ids; typical: the same on Rule::cmp with the ties up to id_cut; min-p: (lp - ref) * inv_temp >= the float whose bits
+// tau holds.  The pick is the first member whose running weight exceeds t; lp_of(word, id) is its untempered log-prob.
+template <class Rule, class Sweep, class LpOf>
+__device__ __forceinline__ void nucleus_draw_row(const Sweep& sweep, const LpOf& lp_of, uint32_t tau, bool cut, int m, int id_cut,
+                                                 float t, int row, const SampleArgs& a, NucleusSmem& sm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float inv_temp = a.inv_temp;
   const float lmax = sm.ref_max;
-  const unsigned long long fx_tau = nuc_fx(nuc_weight(tau, lmax, inv_temp));     // (> 0: its bin reached a target >= 1)
-  const int ties = (int)(sm.bucket / fx_tau);
-  int m = (int)((sm.need + fx_tau - 1) / fx_tau);
-  m = m > ties ? ties : m;
-  const bool cut = m < ties;                                   // (uniform)
-  const float t = sample_args_u(a, row) * ((float)(above + (unsigned long long)m * fx_tau) * (1.f / NUC_FX));
-  // 3. id order
   float carry = 0.f;
   int tie_carry = 0, par = 0;
   int best = 0x7fffffff, last = -1, cnt = 0;
@@ -1482,9 +1473,17 @@ __device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep
   sweep([&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, int id0) {
     const uint32_t k[4] = {k0, k1, k2, k3};
     bool mem[4];
+    if constexpr (Rule::KIND == 1) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) mem[e] = k[e] > tau || (!cut && k[e] == tau);
-    if (cut) {
+      for (int e = 0; e < 4; ++e) mem[e] = Rule::cmp(k[e]) > tau || (Rule::cmp(k[e]) == tau && id0 + e <= id_cut);
+    } else if constexpr (Rule::KIND == 2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mem[e] = k[e] != 0u && typ_a(key_lp(k[e]), lmax, inv_temp) >= __uint_as_float(tau);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mem[e] = k[e] > tau || (!cut && k[e] == tau);
+    }
+    if (Rule::KIND == 0 && cut) {
       int tc = 0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) tc += k[e] == tau ? 1 : 0;
@@ -1511,7 +1510,7 @@ __device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep
     float run = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      run += mem[e] ? nuc_weight(k[e], lmax, inv_temp) : 0.f;
+      run += mem[e] ? Rule::weight(k[e], lmax, inv_temp) : 0.f;
       s[e] = run;
     }
     float incl = run;
@@ -1551,15 +1550,185 @@ __device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep
   if (lane == 0) { atomicMin(&sm.best, wb); atomicMax(&sm.last, wl); atomicAdd(&sm.cnt, wc); }
   __syncthreads();
   const int pick = sm.best != 0x7fffffff ? sm.best : sm.last;   // (no running sum above t: rounding at the top end - the last member)
-  if (best == pick) { a.tokens[row] = pick; a.lps[row] = key_lp(best_key); }
-  else if (sm.best == 0x7fffffff && last == pick) { a.tokens[row] = pick; a.lps[row] = key_lp(last_key); }
+  if (best == pick) { a.tokens[row] = pick; a.lps[row] = lp_of(best_key, pick); }
+  else if (sm.best == 0x7fffffff && last == pick) { a.tokens[row] = pick; a.lps[row] = lp_of(last_key, pick); }
   if (tid == 0) {
     if (a.nuc_size) a.nuc_size[row] = sm.cnt;
-    if (a.nuc_key) a.nuc_key[row] = tau;
+    if (Rule::KIND != 2 && a.nuc_key) a.nuc_key[row] = Rule::report(tau);
   }
+}
+// steps 1-3 after nucleus_row_max: `ref` is the rule's reference value (the maximum log-prob; the typical rule's c), a.topp
+// the share of the total mass to reach.  `each` hands out (word, token id) - the id is only read by the typical rule.
+template <class Rule, class Each, class Sweep, class LpOf>
+__device__ __forceinline__ void nucleus_search_row(const Each& each, const Sweep& sweep, const LpOf& lp_of, float ref, int row,
+                                                   const SampleArgs& a, NucleusSmem& sm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float inv_temp = a.inv_temp;
+  // 1. the coarse digit over the whole row
+  {
+    const float lmax = ref;
+    if (tid == 0) sm.ref_max = lmax;
+    each([&](uint32_t key, int) {
+      const unsigned long long fx = key ? nuc_fx(Rule::weight(key, lmax, inv_temp)) : 0ull;
+      if (fx) atomicAdd(&sm.hist[Rule::coarse(key, lmax, inv_temp)], fx);        // (a peaked row: most of the vocabulary is 0)
+    });
+  }
+  nucleus_decide(sm, a.topp);
+  unsigned long long above = sm.above;
+  // the crossing coarse bin is a key range (the digit is monotone in the key): klo .. khi, the bin's smallest and largest key
+  {
+    const int g = sm.sel;
+    const float lmax = sm.ref_max;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    each([&](uint32_t key, int) {
+      if (key && Rule::coarse(key, lmax, inv_temp) == g) { lo = min(lo, Rule::cmp(key)); hi = max(hi, Rule::cmp(key)); }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
+      hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
+    }
+    if (lane == 0) { atomicMin(&sm.klo, lo); atomicMax(&sm.khi, hi); }
+    __syncthreads();
+  }
+  // 2. the key's bytes inside that range.  A byte that klo and khi share (with all bytes above it) is the same in every
+  //    participant: its pass is skipped - typically the top byte (a quarter nat rarely spans two exponents), often
+  //    the next.  klo / khi / ref_max are re-read from LDS in every pass: filters and weights computed from register values
+  //    are loop-invariant, and the compiler would keep 64 of each per thread of the register form live across the passes
+  //    (293 VGPRs spilled).
+  uint32_t pre = 0, msk = 0;
+  for (int sh = 24; sh >= 0; sh -= 8) {
+    if (((sm.klo ^ sm.khi) >> sh) == 0) {                        // (uniform)
+      pre |= sm.klo & (0xFFu << sh);
+      msk |= 0xFFu << sh;
+      continue;
+    }
+    if (tid < 256) sm.hist[tid] = 0;
+    __syncthreads();
+    const uint32_t klo = sm.klo, khi = sm.khi;
+    const float lmax = sm.ref_max;
+    each([&](uint32_t word, int) {
+      const uint32_t key = Rule::cmp(word);
+      if (key >= klo && key <= khi && (key & msk) == pre) {
+        const unsigned long long fx = nuc_fx(Rule::weight(word, lmax, inv_temp));
+        if (fx) atomicAdd(&sm.hist[(key >> sh) & 255], fx);
+      }
+    });
+    nucleus_decide(sm, 0.f);
+    pre |= (uint32_t)sm.sel << sh;
+    msk |= 0xFFu << sh;
+    above += sm.above;
+  }
+  const uint32_t tau = pre;
+  if constexpr (Rule::KIND == 1) {
+    // the tokens at distance tau need not weigh the same (x = +d and x = -d), so the ties are not counted off: when there
+    // are several, the mass target left inside them picks the id up to which they enter - three more passes, over the
+    // digits of 2^19 - 1 - id (lower ids first), with the same masses and the same decision
+    if (tid == 0) sm.tau = tau;
+    int tc = 0;
+    each([&](uint32_t word, int) { tc += Rule::cmp(word) == tau ? 1 : 0; });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tc += __shfl_xor(tc, o, 64);
+    if (lane == 0) sm.ttot[0][wave] = tc;
+    __syncthreads();
+    int ties = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) ties += sm.ttot[0][w];
+    unsigned long long mass = above + sm.bucket;
+    int id_cut = 0x7fffffff;
+    if (ties > 1) {                                             // (uniform)
+      mass = above;
+      uint32_t ipre = 0, imsk = 0;
+      for (int sh = 16; sh >= 0; sh -= 8) {
+        if (tid < 256) sm.hist[tid] = 0;
+        __syncthreads();
+        const uint32_t tv = sm.tau;
+        const float c = sm.ref_max;
+        each([&](uint32_t word, int id) {
+          const uint32_t inv = 0x7FFFFu - (uint32_t)id;
+          if (Rule::cmp(word) == tv && (inv & imsk) == ipre) {
+            const unsigned long long fx = nuc_fx(Rule::weight(word, c, inv_temp));
+            if (fx) atomicAdd(&sm.hist[(inv >> sh) & 255], fx);
+          }
+        });
+        nucleus_decide(sm, 0.f);
+        ipre |= (uint32_t)sm.sel << sh;
+        imsk |= 0xFFu << sh;
+        mass += sm.above;
+      }
+      mass += sm.bucket;                                        // (the last bin holds one token: the last tie to enter)
+      id_cut = 0x7FFFF - (int)ipre;
+    }
+    const float t = sample_args_u(a, row) * ((float)mass * (1.f / NUC_FX));
+    nucleus_draw_row<Rule>(sweep, lp_of, tau, false, 0, id_cut, t, row, a, sm);
+  } else {
+    // tau = pre: `ties` keys equal it, the prefix takes the m lowest ids of them
+    const float lmax = sm.ref_max;
+    const unsigned long long fx_tau = nuc_fx(Rule::weight(tau, lmax, inv_temp));   // (> 0: its bin reached a target >= 1)
+    const int ties = (int)(sm.bucket / fx_tau);
+    int m = (int)((sm.need + fx_tau - 1) / fx_tau);
+    m = m > ties ? ties : m;
+    const bool cut = m < ties;                                   // (uniform)
+    const float t = sample_args_u(a, row) * ((float)(above + (unsigned long long)m * fx_tau) * (1.f / NUC_FX));
+    nucleus_draw_row<Rule>(sweep, lp_of, tau, cut, m, 0, t, row, a, sm);
+  }
+}
+template <class Each, class Sweep>
+__device__ __forceinline__ void nucleus_row(const Each& each, const Sweep& sweep, uint32_t thread_max, int row,
+                                            const SampleArgs& a, NucleusSmem& sm) {
+  const uint32_t kmax = nucleus_row_max(thread_max, sm);
+  nucleus_search_row<NucleusRule>(each, sweep, [](uint32_t key, int) { return key_lp(key); }, key_lp(kmax), row, a, sm);
+}
+// min-p (tell_adaptive_logprob_minp): the maximum, the members' mass, the id-order draw; a.topp is log_minp
+template <class Each, class Sweep>
+__device__ __forceinline__ void minp_row(const Each& each, const Sweep& sweep, uint32_t thread_max, int row,
+                                         const SampleArgs& a, NucleusSmem& sm) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float lmax = key_lp(nucleus_row_max(thread_max, sm));
+  if (tid == 0) sm.ref_max = lmax;                              // (the draw re-reads it: see nucleus_search_row, 2.)
+  const float inv_temp = a.inv_temp, thr = a.topp;
+  unsigned long long mass = 0;
+  each([&](uint32_t key, int) {
+    if (key && typ_a(key_lp(key), lmax, inv_temp) >= thr) mass += nuc_fx(nuc_weight(key, lmax, inv_temp));
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o, 64);
+  if (lane == 0) sm.hist[wave] = mass;
+  __syncthreads();
+  unsigned long long all = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) all += sm.hist[w];               // (>= 2^44: the best token weighs 1)
+  const float t = sample_args_u(a, row) * ((float)all * (1.f / NUC_FX));
+  nucleus_draw_row<MinpRule>(sweep, [](uint32_t key, int) { return key_lp(key); }, __float_as_uint(thr), false, 0, 0, t, row,
+                             a, sm);
+}
+// locally typical (tell_adaptive_logprob_typical), after nucleus_row_max: W and S over the row's lp keys in a fixed order,
+// -> c.  red: 2 x 16 floats.
+template <class Each>
+__device__ __forceinline__ float typical_c(const Each& each, float lmax, float inv_temp, float (*red)[16]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float W = 0.f, S = 0.f;
+  each([&](uint32_t key, int) {
+    if (key) {
+      const float x = typ_a(key_lp(key), lmax, inv_temp), w = __expf(x);
+      W += w;
+      S += w * x;
+    }
+  });
+  W = wave_sum(W);
+  S = wave_sum(S);
+  if (lane == 0) { red[0][wave] = W; red[1][wave] = S; }
+  __syncthreads();
+  W = 0.f; S = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) { W += red[0][w]; S += red[1][w]; }
+  return S < 0.f ? -S / W : 0.f;
 }
 // The register-resident form: loads, maxima, sums and log-probs exactly as logprob_regs_kernel / logprob_sample_regs_kernel
 // (a tiny p is the register arg-max bit for bit); every pass runs over registers, the logits cross HBM once.
+// RULE 0: the nucleus; 1: locally typical - the lp keys are overwritten with the words of TypicalRule, and the picking
+// thread recovers lp from its one logit in memory with the arithmetic that formed the key; 2: min-p.
+template <int RULE>
 __global__ __launch_bounds__(1024) void logprob_nucleus_regs_kernel(LogProbArgs p, SampleArgs a) {
   __shared__ float red[4][16];
   __shared__ NucleusSmem sm;
@@ -1663,7 +1832,7 @@ __global__ __launch_bounds__(1024) void logprob_nucleus_regs_kernel(LogProbArgs 
 #pragma unroll
       for (int q = 0; q < LPF_CAP[s]; ++q)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) f(key[(LPF_OFF[s] + q) * 4 + e], 0);
+        for (int e = 0; e < 4; ++e) f(key[(LPF_OFF[s] + q) * 4 + e], base[s] + (q * 1024 + tid) * 4 + e);
   };
   auto sweep = [&](auto chunk) {                              // chunk (s, q): ids base[s] + q * 4096 .. + 4095, four per thread
 #pragma unroll
@@ -1675,10 +1844,30 @@ __global__ __launch_bounds__(1024) void logprob_nucleus_regs_kernel(LogProbArgs 
           chunk(key[e0], key[e0 + 1], key[e0 + 2], key[e0 + 3], base[s] + (q * 1024 + tid) * 4);
         }
   };
-  nucleus_row(each, sweep, tmax, i, a, sm);
+  if constexpr (RULE == 0) nucleus_row(each, sweep, tmax, i, a, sm);
+  else if constexpr (RULE == 2) minp_row(each, sweep, tmax, i, a, sm);
+  else {
+    const float lmax = key_lp(nucleus_row_max(tmax, sm));
+    if (tid == 0) sm.ref_max = lmax;
+    const float c = typical_c(each, lmax, a.inv_temp, red);
+    const float lm2 = sm.ref_max;                             // (from LDS: the a of typical_c must not stay live, see nucleus_search_row)
+#pragma unroll
+    for (int e = 0; e < 64; ++e) key[e] = key[e] ? typ_word(typ_x(key_lp(key[e]), lm2, a.inv_temp, c)) : 0u;
+    if (tid == 0 && a.typ_c) a.typ_c[i] = c;
+    __syncthreads();
+    auto lp_of = [&](uint32_t, int id) {
+      float v = rowp[0][id < p.c0 ? id : 0] - lse_h;
+#pragma unroll
+      for (int s = 1; s < 4; ++s)
+        if (id >= base[s] && id < base[s] + n[s]) v = rowp[s][id - base[s]] + off[s];
+      return v;
+    };
+    nucleus_search_row<TypicalRule>(each, sweep, lp_of, c, i, a, sm);
+  }
 }
 // Any row: the log-probs with the arithmetic of logprob_argmax_kernel, read from memory in every pass (a chunk of pass 3 is
 // 1024 consecutive ids, one per thread).
+template <int RULE>
 __global__ __launch_bounds__(1024) void logprob_nucleus_stream_kernel(LogProbArgs p, SampleArgs a) {
   __shared__ float red[16];
   __shared__ NucleusSmem sm;
@@ -1734,7 +1923,30 @@ __global__ __launch_bounds__(1024) void logprob_nucleus_stream_kernel(LogProbArg
   };
   uint32_t tmax = 0;
   each([&](uint32_t key, int) { tmax = max(tmax, key); });
-  nucleus_row(each, sweep, tmax, i, a, sm);
+  if constexpr (RULE == 0) nucleus_row(each, sweep, tmax, i, a, sm);
+  else if constexpr (RULE == 2) minp_row(each, sweep, tmax, i, a, sm);
+  else {
+    __shared__ float red2[2][16];
+    const float lmax = key_lp(nucleus_row_max(tmax, sm)), inv_temp = a.inv_temp;
+    const float c = typical_c(each, lmax, inv_temp, red2);
+    if (tid == 0 && a.typ_c) a.typ_c[i] = c;
+    auto word = [&](uint32_t key) { return key ? typ_word(typ_x(key_lp(key), lmax, inv_temp, c)) : 0u; };
+    auto each_t = [&](auto f) { each([&](uint32_t key, int id) { f(word(key), id); }); };
+    auto sweep_t = [&](auto chunk) {
+      sweep([&](uint32_t k0, uint32_t, uint32_t, uint32_t, int id0) { chunk(word(k0), 0u, 0u, 0u, id0); });
+    };
+    auto lp_of = [&](uint32_t, int id) {
+      if (id < p.c0) return hrow[id] - lse_h;
+      float v = 0.f;
+      int base = p.c0;
+      for (int c2 = 0; c2 < p.n_tails; ++c2) {
+        if (id >= base && id < base + p.tail_n[c2]) v = (p.tail[c2] + (long)i * p.ld_tail[c2])[id - base] + off[c2];
+        base += p.tail_n[c2];
+      }
+      return v;
+    };
+    nucleus_search_row<TypicalRule>(each_t, sweep_t, lp_of, c, i, a, sm);
+  }
 }
 extern "C" int tell_adaptive_logprob_nucleus(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                              int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
@@ -1769,9 +1981,68 @@ extern "C" int tell_adaptive_logprob_nucleus(const float* head, long ld_head, in
     else hipLaunchKernelGGL(logprob_sample_stream_kernel<true>, dim3(rows), dim3(1024), 0, stream, q, a);
     return tell_check_launch("logprob_nucleus (top-k)");
   }
-  if (regs) hipLaunchKernelGGL(logprob_nucleus_regs_kernel, dim3(rows), dim3(1024), 0, stream, q, a);
-  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel, dim3(rows), dim3(1024), 0, stream, q, a);
+  if (regs) hipLaunchKernelGGL(logprob_nucleus_regs_kernel<0>, dim3(rows), dim3(1024), 0, stream, q, a);
+  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel<0>, dim3(rows), dim3(1024), 0, stream, q, a);
   return tell_check_launch("logprob_nucleus");
+}
+
+// ------------------------------------------------------------------ min-p and locally typical sampling
+// include/tell_hip.h tell_adaptive_logprob_minp / _typical: the nucleus kernels under another rule (RULE 2 / 1 above).
+template <int RULE>
+static int truncation_launch(const char* what, const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2, int rows,
+                             SampleArgs a, hipStream_t stream) {
+  LogProbArgs q;
+  q.head = head; q.ld_head = ld_head; q.head_n = c0 + n_tails; q.c0 = c0; q.n_tails = n_tails; q.rows = rows;
+  q.tail[0] = tail0; q.ld_tail[0] = ld0; q.tail_n[0] = n0;
+  q.tail[1] = tail1; q.ld_tail[1] = ld1; q.tail_n[1] = n1;
+  q.tail[2] = tail2; q.ld_tail[2] = ld2; q.tail_n[2] = n2;
+  q.log_probs = nullptr; q.ld_lp = 0; q.token = nullptr; q.token_lp = nullptr;
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs = tell_opt(OPT_ARGMAX_REGS) != 0 && aligned && q.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
+                    (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096);
+  if (regs) hipLaunchKernelGGL(logprob_nucleus_regs_kernel<RULE>, dim3(rows), dim3(1024), 0, stream, q, a);
+  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel<RULE>, dim3(rows), dim3(1024), 0, stream, q, a);
+  return tell_check_launch(what);
+}
+extern "C" int tell_adaptive_logprob_minp(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                          int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                          int rows, float inv_temp, float log_minp, const uint32_t* seed_dev,
+                                          const int* row_ids, int step, const int* step_dev, int* tokens, float* lps,
+                                          int* nuc_size, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_minp: up to 3 tails");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_minp: inv_temp > 0");
+  TELL_REQUIRE(log_minp <= 0.f, "logprob_minp: log_minp = log(m) with 0 < m <= 1");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_minp: seed_dev, tokens and lps are required");
+  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(vocab >= 1 && vocab < (1L << 19), "logprob_minp: 1 <= vocab < 2^19");
+  if (rows <= 0) return TELL_OK;
+  SampleArgs a;
+  a.k = 0; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = log_minp; a.nuc_size = nuc_size; a.nuc_key = nullptr; a.typ_c = nullptr;
+  return truncation_launch<2>("logprob_minp", head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows,
+                              a, stream);
+}
+extern "C" int tell_adaptive_logprob_typical(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                             int rows, float inv_temp, float tau, const uint32_t* seed_dev,
+                                             const int* row_ids, int step, const int* step_dev, int* tokens, float* lps,
+                                             int* nuc_size, uint32_t* nuc_key, float* typ_c, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_typical: up to 3 tails");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_typical: inv_temp > 0");
+  TELL_REQUIRE(tau > 0.f && tau <= 1.f, "logprob_typical: 0 < tau <= 1");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_typical: seed_dev, tokens and lps are required");
+  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(vocab >= 1 && vocab < (1L << 19), "logprob_typical: 1 <= vocab < 2^19");
+  if (rows <= 0) return TELL_OK;
+  SampleArgs a;
+  a.k = 0; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = tau; a.nuc_size = nuc_size; a.nuc_key = nuc_key; a.typ_c = typ_c;
+  return truncation_launch<1>("logprob_typical", head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2,
+                              rows, a, stream);
 }
 
 // the nucleus of given candidates (sorted best first, as tell_sample_candidates takes them): one thread per row

@@ -9,7 +9,7 @@ import math
 import torch
 
 from .. import ops
-from .transformer import CaptionModel, Model, check_beam_options, check_sampling, draw_seed
+from .transformer import CaptionModel, Model, check_beam_options, check_sampling, draw_seed, set_sampling
 
 
 def _refuse_search_options(model, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, n_best=1):
@@ -31,9 +31,13 @@ class BaselineGloveModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
                  weigh_bert=False, initializer=None, resnet=None, sampling_topp=None, beam_len_penalty=0.0,
-                 no_repeat_ngram_size=0, min_len=0):
+                 no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
         super().__init__(vocab)
         _refuse_search_options(self, beam_len_penalty, no_repeat_ngram_size, min_len)
+        for name, v in (('sampling_minp', sampling_minp), ('sampling_typical', sampling_typical)):
+            if v is not None:
+                raise ValueError('%s=%r: %s has a decode step with its own decision launch (LSTM decoder); min-p and typical '
+                                 'sampling cover the cached DynamicConv generator only' % (name, v, type(self).__name__))
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
         if resnet is None:
@@ -171,7 +175,7 @@ class TransformerGloveModel(CaptionModel):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024, dropout=0.1,
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
                  use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None,
-                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -180,11 +184,11 @@ class TransformerGloveModel(CaptionModel):
             resnet = resnet152()
         self.resnet = resnet
         self.use_context, self.padding_idx, self.evaluate_mode = use_context, padding_value, evaluate_mode
-        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
-        self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
+        set_sampling(self, sampling_topk, sampling_temp, sampling_topp, sampling_minp, sampling_typical)
         self.beam_len_penalty, self.no_repeat_ngram_size, self.min_len = check_beam_options(
             beam_len_penalty, no_repeat_ngram_size, min_len)
         self._check_options()
+        self._check_truncation()
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0

@@ -96,7 +96,8 @@ class DecodeStepper:
                dec.embedder.token_embedder_position.weights.data_ptr(), self.lane)
         if sample is not None:                                    # (greedy and beam signatures are unchanged)
             sig = sig + ((('sample', int(sample[0]), float(sample[1])) if len(sample) == 2 else
-                          ('nucleus', int(sample[0]), float(sample[1]), float(sample[2]))),)
+                          ('nucleus', int(sample[0]), float(sample[1]), float(sample[2])) if len(sample) == 3 else
+                          (str(sample[3]), int(sample[0]), float(sample[1]), float(sample[2]))),)
         if attention:                                             # (... and so are the sampling ones)
             sig = sig + (('attn',),)
         if ban is not None or opts is not None:                   # (... and the ones without search options)
@@ -245,7 +246,8 @@ class DecodeStepper:
             return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
         if self.sample is not None:
             topp = self.sample[2] if len(self.sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
-            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, topp=topp, force=force)
+            rule = self.sample[3] if len(self.sample) > 3 else None      # 'minp' / 'typical': topp is m / tau
+            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, topp=topp, force=force, rule=rule)
         if self.topk:
             return soft.topk(x, self.topk, force=force)
         return soft.greedy(x, force=force)

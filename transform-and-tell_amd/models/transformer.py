@@ -64,10 +64,26 @@ class Model(nn.Module, Registrable):
 MAX_SAMPLING_TOPK = 64          # tell_adaptive_logprob_sample's exact top-k
 
 
-def check_sampling(sampling_topk, sampling_temp, sampling_topp=None):
+def check_sampling(sampling_topk, sampling_temp, sampling_topp=None, sampling_minp=None, sampling_typical=None):
     """The caption models' `sampling_topk` / `sampling_temp` (transformer_faces_objects.py:38-55): top-k sampling with a
     temperature, 1 <= k <= 64 (k = 1: the arg-max token) and T > 0.  -> (k, T); ValueError otherwise.
-    With `sampling_topp` = p (nucleus sampling, 0 < p <= 1): k is 0 (no top-k cut) or 2..64 -> (k, T, p)."""
+    With `sampling_topp` = p (nucleus sampling, 0 < p <= 1): k is 0 (no top-k cut) or 2..64 -> (k, T, p).
+    With `sampling_minp` = m (min-p, 0 < m <= 1) or `sampling_typical` = tau (locally typical sampling, 0 < tau <= 1;
+    DESIGN.md section 19): at most one of the three, and sampling_topk must be 0 -> (0, T, m, 'minp') / (0, T, tau, 'typical')."""
+    rules = [(n, v) for n, v in (('sampling_topp', sampling_topp), ('sampling_minp', sampling_minp),
+                                 ('sampling_typical', sampling_typical)) if v is not None]
+    if len(rules) > 1:
+        raise ValueError('%s do not combine: one truncation rule per model' % ' and '.join('%s=%r' % r for r in rules))
+    if sampling_minp is not None or sampling_typical is not None:
+        name, v = rules[0]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) <= 1.0:
+            raise ValueError('%s must be a number with 0 < %s <= 1, or None (got %r)'
+                             % (name, 'm' if name == 'sampling_minp' else 'tau', v))
+        k = sampling_topk
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or k != 0:
+            raise ValueError('with %s, sampling_topk must be 0: the rule takes no top-k cut (got sampling_topk=%r)' % (name, k))
+        _, temp = check_sampling(2, sampling_temp)
+        return 0, temp, float(v), name[len('sampling_'):]
     if sampling_topp is not None:
         p = sampling_topp
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
@@ -198,10 +214,79 @@ def nucleus_definition(lp, temp, topp, topk=0, u=None):
     return out
 
 
+def _id_order_draw(out, members, wm, u):
+    import numpy as np
+    run = np.cumsum(wm)
+    out['cdf'] = run / run[-1]
+    out['token'] = None
+    if u is not None:
+        hit = np.nonzero(run > float(u) * run[-1])[0]
+        out['token'] = int(members[hit[0]] if hit.size else members[-1])
+    return out
+
+
+def minp_definition(lp, temp, minp, u=None):
+    """The definition of min-p sampling (include/tell_hip.h tell_adaptive_logprob_minp) on one row of log-probs.  The member
+    set is the kernel's float32 statement - a = (lp - max lp) * float32(1 / T), one fp32 subtract and one fp32 multiply; member
+    iff a >= float32(log(m)) - so lp is taken as fp32; the weights of the draw are fp64.
+    -> dict: members (ascending ids), a (fp32 [V]), threshold (float32(log m)), cdf (running weight of the members in id order,
+    normalised), token (the pick for u, or None)."""
+    import numpy as np
+    lp32 = np.asarray(lp, dtype=np.float32).reshape(-1)
+    a = (lp32 - lp32.max()) * np.float32(1.0 / float(temp))
+    thr = np.float32(math.log(float(minp)))
+    members = np.nonzero(a >= thr)[0]
+    lp64 = lp32.astype(np.float64)
+    wm = np.exp((lp64[members] - lp64.max()) / float(temp))
+    return _id_order_draw({'members': members, 'a': a, 'threshold': thr}, members, wm, u)
+
+
+def typical_definition(lp, temp, tau, c=None, u=None):
+    """The definition of locally typical sampling (include/tell_hip.h tell_adaptive_logprob_typical) on one row of log-probs:
+    a = (lp - max lp) / T, w = exp(a), c = -(sum w a) / (sum w), d = |a + c|; the members are the shortest prefix of the order
+    (d ascending, lower id first on ties) whose weight reaches tau * (total weight).  Mass sums in fp64.  c = None: everything
+    in fp64.  c given (the kernel's fp32 c): the ORDER is taken from the kernel's fp32 d = |(lp - max lp) * float32(1 / T) + c|
+    (fp32 subtract, multiply, add), so that only the masses differ from the kernel's.
+    -> dict: members (ascending ids), order (all ids, best first), c (the fp64 c), boundary (d of the worst member), key
+    (~bits of float32(boundary): the kernel's nuc_key), margin (as nucleus_definition's, relative to the total weight), cdf,
+    token."""
+    import numpy as np
+    lp64 = np.asarray(lp, dtype=np.float64).reshape(-1)
+    a = (lp64 - lp64.max()) / float(temp)
+    w = np.exp(a)
+    total = w.sum()
+    c64 = -float((w * a).sum() / total)
+    if c is None:
+        d = np.abs(a + c64)
+    else:
+        lp32 = np.asarray(lp, dtype=np.float32).reshape(-1)
+        d = np.abs((lp32 - lp32.max()) * np.float32(1.0 / float(temp)) + np.float32(c))
+        assert d.dtype == np.float32
+    order = np.lexsort((np.arange(d.size), d))
+    cum = np.cumsum(w[order])
+    target = float(tau) * cum[-1]
+    n = min(int(np.searchsorted(cum, target, side='left')) + 1, order.size)
+    members = np.sort(order[:n])
+    margin = min(cum[n - 1] - target, target - (cum[n - 2] if n > 1 else 0.0)) / cum[-1]
+    bound = d[order[n - 1]]
+    out = {'members': members, 'order': order, 'c': c64, 'boundary': float(bound), 'margin': float(abs(margin)),
+           'key': int(~np.array([bound], dtype=np.float32).view(np.uint32)[0] & np.uint32(0xFFFFFFFF))}
+    return _id_order_draw(out, members, w[members], u)
+
+
 def draw_seed():
     """The seed of one batch's sampled decode: 31 bits from torch's default CPU generator (torch.manual_seed makes the
     captions reproducible)."""
     return int(torch.randint(0, 1 << 31, (1,)).item())
+
+
+def set_sampling(model, sampling_topk, sampling_temp, sampling_topp=None, sampling_minp=None, sampling_typical=None):
+    """check_sampling, kept on the model: sampling_topk / _temp / _topp / _minp / _typical."""
+    model.sampling_topk, model.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp, sampling_minp,
+                                                              sampling_typical)[:2]
+    model.sampling_topp = None if sampling_topp is None else float(sampling_topp)
+    model.sampling_minp = None if sampling_minp is None else float(sampling_minp)
+    model.sampling_typical = None if sampling_typical is None else float(sampling_typical)
 
 
 class AttnMaps(namedtuple('AttnMaps', 'maps steps')):
@@ -220,7 +305,7 @@ class CaptionModel(Model):
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
                  initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
-                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0):
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -234,11 +319,11 @@ class CaptionModel(Model):
         self.use_context = use_context
         self.padding_idx = padding_value
         self.evaluate_mode = evaluate_mode
-        self.sampling_topk, self.sampling_temp = check_sampling(sampling_topk, sampling_temp, sampling_topp)[:2]
-        self.sampling_topp = None if sampling_topp is None else float(sampling_topp)
+        set_sampling(self, sampling_topk, sampling_temp, sampling_topp, sampling_minp, sampling_typical)
         self.beam_len_penalty, self.no_repeat_ngram_size, self.min_len = check_beam_options(
             beam_len_penalty, no_repeat_ngram_size, min_len)
         self._check_options()
+        self._check_truncation()
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -251,14 +336,35 @@ class CaptionModel(Model):
 
     def _sampling(self):
         """-> (k, T) when generation samples (sampling_topk > 1), None for the arg-max decode (sampling_topk = 1);
-        (k, T, p) with nucleus sampling (sampling_topp = p; k = 0: no top-k cut)."""
+        (k, T, p) with nucleus sampling (sampling_topp = p; k = 0: no top-k cut); (0, T, m, 'minp') with sampling_minp = m and
+        (0, T, tau, 'typical') with sampling_typical = tau."""
         k = int(self.sampling_topk)
+        for rule in ('minp', 'typical'):
+            v = getattr(self, 'sampling_' + rule, None)
+            if v is not None:
+                return (0, float(self.sampling_temp), float(v), rule)
         p = getattr(self, 'sampling_topp', None)
         if p is not None:
             return (k, float(self.sampling_temp), float(p))
         return (k, float(self.sampling_temp)) if k > 1 else None
 
+    def _truncation(self):
+        """-> 'sampling_minp=0.1' / 'sampling_typical=0.9' when one of the two rules is set, else None."""
+        for name in ('sampling_minp', 'sampling_typical'):
+            if getattr(self, name, None) is not None:
+                return '%s=%r' % (name, getattr(self, name))
+        return None
+
+    def _check_truncation(self):
+        """sampling_minp / sampling_typical: the cached DynamicConv generator only."""
+        what = self._truncation()
+        if what and (not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts')):
+            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); min-p and '
+                             'typical sampling cover the cached DynamicConv generator only' % (what, type(self).__name__))
+
     def _check_beam(self, beam_size):
+        if int(beam_size) > 1 and self._truncation():
+            raise ValueError('beam search (beam_size %d) and %s do not combine' % (int(beam_size), self._truncation()))
         if int(beam_size) > 1 and getattr(self, 'sampling_topp', None) is not None:
             raise ValueError('beam search (beam_size %d) and nucleus sampling (sampling_topp %r) do not combine'
                              % (int(beam_size), self.sampling_topp))
@@ -287,6 +393,9 @@ class CaptionModel(Model):
         if not used:
             return None
         what = ' / '.join('%s=%r' % (u, n_best if u == 'n_best' else getattr(self, u)) for u in used)
+        if self._truncation():
+            raise ValueError('%s and %s do not combine: the search options apply to the arg-max and beam decodes'
+                             % (what, self._truncation()))
         if getattr(self, 'sampling_topp', None) is not None or int(getattr(self, 'sampling_topk', 1)) > 1:
             raise ValueError('%s and sampling (sampling_topk %r, sampling_topp %r) do not combine: the search options '
                              'apply to the arg-max and beam decodes' % (what, self.sampling_topk, self.sampling_topp))
@@ -1079,7 +1188,8 @@ class CaptionModel(Model):
             else:                                                                   # :443-470, topk + multinomial
                 rows = alive.nonzero().squeeze(1).to(torch.int32)
                 tok, lp = self.decoder.adaptive_softmax.sample(dec_out[0][:, -1:], sampling[0], sampling[1], seed_word, i,
-                                                               row_ids=rows, **({'topp': sampling[2]} if len(sampling) > 2 else {}))
+                                                               row_ids=rows, **({'topp': sampling[2]} if len(sampling) > 2 else {}),
+                                                               **({'rule': sampling[3]} if len(sampling) > 3 else {}))
             sel_ix = tok.long()
             sel_lp = lp / self.sampling_temp
             full_lp = sel_lp.new_zeros(B, 1)

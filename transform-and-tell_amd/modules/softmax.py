@@ -83,17 +83,20 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force)
         return tok.view(B, T, k), lp.view(B, T, k)
 
-    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None):
+    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None):
         """One top-k draw with temperature per position (transformer_faces_objects.py:443-470: lprobs.topk(k), / temp,
         multinomial), fused like `greedy`: -> (token [B, T], log-prob [B, T] WITHOUT the temperature).  seed_dev: int32 [1]
         device word holding the seed; step: host step index or the int32 [1] device counter of a captured step (step - 1);
         row_ids: int32 [B * T] original batch rows (compacted batches), default the row index
         (include/tell_hip.h tell_adaptive_logprob_sample).  topp = p: the nucleus draw instead (k = 0: no top-k cut;
-        tell_adaptive_logprob_nucleus) - the same launches up to the last one."""
+        tell_adaptive_logprob_nucleus) - the same launches up to the last one.  rule = 'minp' / 'typical': topp is that
+        rule's parameter (m / tau; k = 0; tell_adaptive_logprob_minp / tell_adaptive_logprob_typical)."""
         B, T, E = X.shape
         sample = (int(k), 1.0 / float(temp), seed_dev, row_ids, step)
         if topp is not None:
             sample = sample + (float(topp),)
+        if rule is not None:
+            sample = sample + (rule,)
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
                                             self.head.class_proj.weight, self._tails(), sample=sample, force=force)
         return tok.view(B, T), lp.view(B, T)

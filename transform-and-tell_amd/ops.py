@@ -1749,11 +1749,24 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
     sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
     int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
     counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None).
-    A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut)."""
+    A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut); a seventh names another
+    rule for the sixth: 'minp' (m: tell_adaptive_logprob_minp, log(m) formed here in fp64) or 'typical' (tau:
+    tell_adaptive_logprob_typical) - both over the whole row, k = 0."""
     k, inv_temp, seed_dev, row_ids, step = sample[:5]
     step_dev = step if torch.is_tensor(step) else None
     token = torch.empty(N, dtype=torch.int32, device=head.device)
     token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
+    if len(sample) > 6:
+        rule, value = sample[6], float(sample[5])
+        if rule not in ('minp', 'typical') or int(k) != 0:
+            raise ValueError('logprob_sample: rule %r with k = %r (minp / typical take no top-k cut)' % (rule, k))
+        rows = (head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2], ns[2], N)
+        draw = (seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token, token_lp)
+        if rule == 'minp':
+            call('tell_adaptive_logprob_minp', *rows, float(inv_temp), math.log(value), *draw, None)
+        else:
+            call('tell_adaptive_logprob_typical', *rows, float(inv_temp), value, *draw, None, None, None)
+        return token, token_lp, None
     if len(sample) > 5:
         call('tell_adaptive_logprob_nucleus', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
              lds[2], ns[2], N, int(k), float(inv_temp), float(sample[5]), seed_dev, row_ids,
@@ -1804,7 +1817,8 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
 def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
-    sample = (k, inv_temp, seed_dev, row_ids, step[, p]): one top-k (with p: nucleus) draw per row instead of the arg-max
+    sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
+    draw per row instead of the arg-max
     (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced)."""
     if force is not None and want_full:
         raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
