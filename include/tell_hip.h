@@ -289,6 +289,14 @@ int tell_beam_update_norm(const int* tk, const float* lp, float* cum, uint8_t* f
 int tell_decode_ban_list(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
                          const int* step_dev, int ngram, int min_len, int eos, int* ban, long ld_ban, int* n_ban,
                          tell_stream_t stream);
+/* The token counts of every decode row (repetition / presence / frequency penalties).  hist, finished,
+ * step and step_dev as tell_decode_ban_list.  Step i of a live row: pen_tok[r][0 .. n_pen[r]) holds the distinct tokens of
+ * h[0 .. i] in order of first occurrence, pen_cnt[r][e] = c_t, the number of positions of h[0 .. i] that hold pen_tok[r][e];
+ * nothing is written behind the list.  A finished row has n_pen[r] = 0.  pen_tok, pen_cnt int32 [rows, ld_pen >= L], n_pen
+ * int32 [rows]. */
+int tell_decode_token_counts(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
+                             const int* step_dev, int* pen_tok, int* pen_cnt, long ld_pen, int* n_pen,
+                             tell_stream_t stream);
 /* buf[i][p][r][:] <- buf[i][p][rows[r]][:] in place for n <= 8 bf16 buffers [planes[i], M, 1024] (HOST arrays); rows[r]
  * must lie inside r's group of K consecutive rows (dynamic.py:338-342 reorder_incremental_state, all layers at once) - for
  * input buffers kept in time order (the layer-by-layer fp32 step); the rings of tell_dynconv_step are never moved. */
@@ -541,6 +549,24 @@ int tell_adaptive_logprob_topk_banned(const float* head, long ld_head, int c0, i
                                       int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
                                       int rows, int k, const int* ban, long ld_ban, const int* n_ban, int* tokens,
                                       float* lps, tell_stream_t stream);
+/* tell_adaptive_logprob_topk over PENALISED scores.  pen_tok / pen_cnt int32 [rows, ld_pen], n_pen int32 [rows]: the row's
+ * list of (token t, count c_t) pairs (tell_decode_token_counts; at most 256 entries are read, tokens outside the vocabulary
+ * are ignored, a token is listed once); sub fp32 [n_sub] on the device, which the host builds as sub[0] = 0,
+ * sub[c] = float32(float64(alpha) + float64(beta) * c) (counts are clamped to n_sub - 1); theta finite, >= 1.  With lp_t the
+ * log-prob tell_adaptive_logprob_topk / _argmax computes for t (the log-sum-exps run over the whole row, nothing is
+ * renormalised), the score is
+ *     s_t = lp_t                               for a token that is not listed (c_t = 0)
+ *     s_t = min(lp_t, 0) * theta - sub[c_t]    for a listed one: a multiply and a subtract, two fp32 operations rounded one by
+ *                                              one (never an FMA); the min keeps s_t <= lp_t
+ * and the result is the k best (s, token) of the row, value descending, lower id first on ties; lps holds s.  n_pen[r] = 0
+ * gives the row of tell_adaptive_logprob_topk bit for bit, and so does a list with theta = 1 and sub = 0 wherever lp <= 0.
+ * k = 1..8 (k = 1: the greedy decode under penalties); vocab <= 2^18; register and streaming forms as
+ * tell_adaptive_logprob_topk (option argmax_regs). */
+int tell_adaptive_logprob_topk_penalised(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                         int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                         int rows, int k, const int* pen_tok, const int* pen_cnt, long ld_pen,
+                                         const int* n_pen, float theta, const float* sub, int n_sub, int* tokens, float* lps,
+                                         tell_stream_t stream);
 int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,
@@ -582,6 +608,16 @@ int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_
                                  int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
                                  int rows, int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids, int step,
                                  const int* step_dev, int* tokens, float* lps, tell_stream_t stream);
+/* tell_adaptive_logprob_sample over the penalised scores s of tell_adaptive_logprob_topk_penalised (same list arguments):
+ * the candidates are the k (1..64) largest s (value descending, lower id first), the weights exp((s_j - s_0) * inv_temp),
+ * u(seed, row, step) and the pick as above; out: the token and its s WITHOUT the temperature.  k = 1 is the penalised
+ * arg-max bit for bit.  vocab <= 2^18. */
+int tell_adaptive_logprob_sample_penalised(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                           int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2,
+                                           int n2, int rows, int k, float inv_temp, const uint32_t* seed_dev,
+                                           const int* row_ids, int step, const int* step_dev, const int* pen_tok,
+                                           const int* pen_cnt, long ld_pen, const int* n_pen, float theta, const float* sub,
+                                           int n_sub, int* tokens, float* lps, tell_stream_t stream);
 /* steps 2-5 above on given candidates: cand_tokens int32 / cand_lps fp32 [rows, k], each row sorted best first */
 int tell_sample_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp,
                            const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,

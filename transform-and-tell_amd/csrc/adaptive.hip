@@ -416,11 +416,66 @@ __device__ __forceinline__ void ban_stage(const BanArgs& ba, int row, int nb) {
   }
   __syncthreads();
 }
+// PEN (tell_adaptive_logprob_topk_penalised / _sample_penalised, include/tell_hip.h): the row's token list (tok / cnt
+// [i][0 .. n_pen[i]): the distinct tokens of its history with their counts, tell_decode_token_counts) becomes the same bitmap
+// plus, behind it in LDS, the list itself: the token and sub[count] of up to 256 entries.  A listed token's score is
+// s = min(lp, 0) * theta - sub[count], two fp32 operations rounded one by one; s <= lp, so the "beats my K-th best" return on
+// the unpenalised value stays valid and only the few elements that pass it test their bit.  n_pen[i] == 0 stages nothing.
+struct PenArgs { const int* tok; const int* cnt; long ld; const int* n_pen; const float* sub; int n_sub; float theta; int vocab; };
+struct NoPen {};
+__device__ __forceinline__ NoPen pen_pick() { return NoPen{}; }
+__device__ __forceinline__ const PenArgs& pen_pick(const PenArgs& a) { return a; }
+// the trailing argument of the top-k kernels: the ban list, or with PEN the penalty list
+template <bool PEN> struct ListOf { typedef BanArgs type; };
+template <> struct ListOf<true> { typedef PenArgs type; };
+#define PEN_MAX_LIST 256
+__device__ __forceinline__ int pen_count(const PenArgs& pa, int row) {
+  const int np = pa.n_pen[row];
+  const int cap = pa.ld < PEN_MAX_LIST ? (int)pa.ld : PEN_MAX_LIST;
+  return np < 0 ? 0 : (np > cap ? cap : np);
+}
+__device__ __forceinline__ int pen_count(const NoPen&, int) { return 0; }
+__device__ __forceinline__ int pen_count(const BanArgs&, int) { return 0; }
+template <int THREADS>
+__device__ __forceinline__ void pen_stage(const PenArgs& pa, int row, int np) {
+  const int words = (pa.vocab + 31) >> 5;
+  int* lt = reinterpret_cast<int*>(ban_bits + words);
+  float* ls = reinterpret_cast<float*>(ban_bits + words + PEN_MAX_LIST);
+  for (int w = threadIdx.x; w < words; w += THREADS) ban_bits[w] = 0u;
+  __syncthreads();
+  for (int e = threadIdx.x; e < np; e += THREADS) {
+    const int t = pa.tok[(long)row * pa.ld + e];
+    int c = pa.cnt[(long)row * pa.ld + e];
+    c = c < 0 ? 0 : (c > pa.n_sub - 1 ? pa.n_sub - 1 : c);
+    const bool ok = t >= 0 && t < pa.vocab;
+    lt[e] = ok ? t : -1;
+    ls[e] = pa.sub[c];
+    if (ok) atomicOr(&ban_bits[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+}
+template <int THREADS> __device__ __forceinline__ void pen_stage(const NoPen&, int, int) {}
+template <int THREADS> __device__ __forceinline__ void pen_stage(const BanArgs&, int, int) {}
+__device__ __forceinline__ bool pen_bit(int j) { return (ban_bits[j >> 5] >> (j & 31)) & 1u; }
+// token j has its bit set: its entry in the staged list -> s (the multiply and the subtract are not contracted)
+__device__ __forceinline__ float pen_score(const PenArgs& pa, int np, int j, float lp) {
+#pragma clang fp contract(off)
+  const int words = (pa.vocab + 31) >> 5;
+  const int* lt = reinterpret_cast<const int*>(ban_bits + words);
+  const float* ls = reinterpret_cast<const float*>(ban_bits + words + PEN_MAX_LIST);
+  float sv = 0.f;
+  for (int e = 0; e < np; ++e)
+    if (lt[e] == j) { sv = ls[e]; break; }
+  const float m = fminf(lp, 0.f) * pa.theta;
+  return m - sv;
+}
+__device__ __forceinline__ float pen_score(const NoPen&, int, int, float lp) { return lp; }
+__device__ __forceinline__ float pen_score(const BanArgs&, int, int, float lp) { return lp; }
 // (the register-resident kernel takes `ba` as a trailing argument that BAN = false never reads: its code stays the kernel's
 //  own, not an inlined body - this is the launch every greedy and beam step ends with)
-template <int K, bool BAN>
+template <int K, bool BAN, bool PEN = false>
 __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
-                                                            float* __restrict__ lps, BanArgs ba) {
+                                                            float* __restrict__ lps, typename ListOf<PEN>::type ba) {
   __shared__ float red[4][16];
   __shared__ float best_v[16];
   __shared__ int best_i[16];
@@ -435,7 +490,8 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
     n[c + 1] = c < p.n_tails ? p.tail_n[c] : 0;
   }
   int nb = 0;                                          // (requested before the row: its wait does not cover the row's loads)
-  if (BAN) { nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb); }
+  if constexpr (BAN) { nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb); }
+  if constexpr (PEN) nb = pen_count(ba, i);
   typedef float f4 __attribute__((ext_vector_type(4)));
   f4 x[16];
 #pragma unroll
@@ -452,7 +508,8 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
       }
       x[LPF_OFF[s] + q] = v;
     }
-  if (BAN && nb > 0) ban_stage<1024>(ba, i, nb);       // (nb is uniform over the workgroup)
+  if constexpr (BAN) { if (nb > 0) ban_stage<1024>(ba, i, nb); }   // (nb is uniform over the workgroup)
+  if constexpr (PEN) { if (nb > 0) pen_stage<1024>(ba, i, nb); }
   float mx[4], sm[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -503,6 +560,12 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
   auto consider = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
     if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
+    if constexpr (PEN) {
+      if (nb > 0 && pen_bit(j)) {
+        v = pen_score(ba, nb, j, v);
+        if (!better(v, j, tv[K - 1], ti[K - 1])) return;
+      }
+    }
     tv[K - 1] = v; ti[K - 1] = j;
 #pragma unroll
     for (int q = K - 1; q > 0; --q)
@@ -571,9 +634,9 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
 // Top-k variant for beam search: per row the k best (log-prob, token) pairs of the adaptive softmax, sorted best
 // first, without materialising [rows, vocab] (a beam of k only ever needs each hypothesis' own k best tokens).
 // Every thread keeps its k best in registers while streaming the row; the block then pops the global best k times.
-template <int K, bool BAN>
+template <int K, bool BAN, bool PEN = false>
 __device__ __forceinline__ void logprob_topk_body(const LogProbArgs& p, int k, int* __restrict__ tokens,
-                                                  float* __restrict__ lps, const BanArgs& ba) {
+                                                  float* __restrict__ lps, const typename ListOf<PEN>::type& ba) {
   __shared__ float red[4];
   __shared__ float best_v[4];
   __shared__ int best_i[4];
@@ -585,13 +648,23 @@ __device__ __forceinline__ void logprob_topk_body(const LogProbArgs& p, int k, i
   for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
   auto better = [](float v, int j, float w, int m) { return v > w || (v == w && j < m); };
   int nb = 0;
-  if (BAN) {
+  if constexpr (BAN) {
     nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb);
     if (nb > 0) ban_stage<256>(ba, i, nb);             // (nb is uniform over the workgroup)
+  }
+  if constexpr (PEN) {
+    nb = pen_count(ba, i);
+    if (nb > 0) pen_stage<256>(ba, i, nb);
   }
   auto push = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
     if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
+    if constexpr (PEN) {
+      if (nb > 0 && pen_bit(j)) {
+        v = pen_score(ba, nb, j, v);
+        if (!better(v, j, tv[K - 1], ti[K - 1])) return;
+      }
+    }
     tv[K - 1] = v; ti[K - 1] = j;
 #pragma unroll
     for (int q = K - 1; q > 0; --q)
@@ -657,6 +730,11 @@ __global__ __launch_bounds__(256) void logprob_topk_banned_kernel(LogProbArgs p,
                                                                   float* __restrict__ lps, BanArgs ba) {
   logprob_topk_body<K, true>(p, k, tokens, lps, ba);
 }
+template <int K>
+__global__ __launch_bounds__(256) void logprob_topk_penalised_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
+                                                                     float* __restrict__ lps, PenArgs pa) {
+  logprob_topk_body<K, false, true>(p, k, tokens, lps, pa);
+}
 extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c0, int n_tails,
                                           const float* tail0, long ld0, int n0, const float* tail1, long ld1,
                                           int n1, const float* tail2, long ld2, int n2, int rows, int k,
@@ -721,6 +799,58 @@ extern "C" int tell_adaptive_logprob_topk_banned(const float* head, long ld_head
   if (k <= 4) hipLaunchKernelGGL((logprob_topk_banned_kernel<4>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ba);
   else hipLaunchKernelGGL((logprob_topk_banned_kernel<8>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ba);
   return tell_check_launch("logprob_topk_banned");
+}
+
+// tell_adaptive_logprob_topk over penalised scores (include/tell_hip.h): pen_tok / pen_cnt int32 [rows, ld_pen], n_pen int32
+// [rows] (tell_decode_token_counts), sub fp32 [n_sub] on the device.
+static int pen_args(PenArgs& pa, int c0, int n_tails, int n0, int n1, int n2, const int* pen_tok, const int* pen_cnt,
+                    long ld_pen, const int* n_pen, float theta, const float* sub, int n_sub) {
+  TELL_REQUIRE(pen_tok && pen_cnt && n_pen && ld_pen >= 1, "logprob penalised: pen_tok / pen_cnt [rows, ld_pen] and n_pen [rows]");
+  TELL_REQUIRE(sub && n_sub >= 1, "logprob penalised: sub fp32 [n_sub >= 1]");
+  TELL_REQUIRE(theta >= 1.f && theta < INFINITY, "logprob penalised: theta finite and >= 1");
+  pa.tok = pen_tok; pa.cnt = pen_cnt; pa.ld = ld_pen; pa.n_pen = n_pen; pa.sub = sub; pa.n_sub = n_sub; pa.theta = theta;
+  pa.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(pa.vocab > 0 && pa.vocab <= (1 << 18), "logprob penalised: vocab <= 2^18 (the bitmap: 32 KB of LDS)");
+  return TELL_OK;
+}
+static size_t pen_lds(const PenArgs& pa) { return (size_t)(((pa.vocab + 31) >> 5) + 2 * PEN_MAX_LIST) * sizeof(unsigned); }
+extern "C" int tell_adaptive_logprob_topk_penalised(const float* head, long ld_head, int c0, int n_tails,
+                                                    const float* tail0, long ld0, int n0, const float* tail1, long ld1,
+                                                    int n1, const float* tail2, long ld2, int n2, int rows, int k,
+                                                    const int* pen_tok, const int* pen_cnt, long ld_pen, const int* n_pen,
+                                                    float theta, const float* sub, int n_sub, int* tokens, float* lps,
+                                                    hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk_penalised: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_penalised: 1 <= k <= 8");
+  TELL_REQUIRE(tokens && lps, "logprob_topk_penalised: tokens and lps [rows, k]");
+  PenArgs pa;
+  const int rc = pen_args(pa, c0, n_tails, n0, n1, n2, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
+  if (rc != TELL_OK) return rc;
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  const size_t lds = pen_lds(pa);
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    if (k == 1) {                                            // the arg-max form: its winner goes to p.token / p.token_lp
+      p.token = tokens; p.token_lp = lps;
+      hipLaunchKernelGGL((logprob_regs_kernel<1, false, true>), dim3(rows), dim3(1024), lds, stream, p, 1, tokens, lps, pa);
+    } else if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, pa);
+    else hipLaunchKernelGGL((logprob_regs_kernel<8, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, pa);
+    return tell_check_launch("logprob_topk_penalised (registers)");
+  }
+  if (k <= 4) hipLaunchKernelGGL((logprob_topk_penalised_kernel<4>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, pa);
+  else hipLaunchKernelGGL((logprob_topk_penalised_kernel<8>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, pa);
+  return tell_check_launch("logprob_topk_penalised");
 }
 
 extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails,
@@ -1112,8 +1242,13 @@ __device__ __forceinline__ void sample_row(const Each& each, const EachTies& eac
 // The register-resident form: loads, maxima, sums and log-probs exactly as logprob_regs_kernel (so k = 1 is its arg-max bit
 // for bit), then the log-probs become keys in place and every pass of the select runs over registers.  Same capacity and
 // alignment rules.
-template <bool NUC>
-__global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p, SampleArgs a) {
+// PEN (tell_adaptive_logprob_sample_penalised): the penalty list is staged like the top-k kernels' (pen_stage) and a listed
+// token's log-prob becomes its score where the keys are formed - one bit test per element; the select, sample_row, is untouched.
+// (the list arguments are a parameter pack that is empty without PEN: the unpenalised instantiations keep their signature,
+//  their kernel-argument layout and with them their code)
+template <bool NUC, bool PEN = false, class... P>
+__global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p, SampleArgs a, P... pa_) {
+  const auto& pa = pen_pick(pa_...);
   __shared__ float red[4][16];
   __shared__ SampleSmem sm;
   const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1141,6 +1276,18 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
       }
       x[LPF_OFF[s] + q] = v;
     }
+  int np = 0;
+  if constexpr (PEN) {
+    np = pen_count(pa, i);
+    if (np > 0) pen_stage<1024>(pa, i, np);              // (np is uniform over the workgroup)
+  }
+  // a listed token's log-prob -> its score (in: the element is a token of the row)
+  auto pen = [&](float l, int idx, bool in) {
+    if constexpr (PEN) {
+      if (np > 0 && in && pen_bit(idx)) return pen_score(pa, np, idx, l);
+    }
+    return l;
+  };
   float mx[4], sm_[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -1205,10 +1352,10 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
       // head: v - lse_h (the argmax kernels' `x - lse_h`); tails: v + off
       const float l0 = s == 0 ? v.x - lse_h : v.x + off[s], l1 = s == 0 ? v.y - lse_h : v.y + off[s];
       const float l2 = s == 0 ? v.z - lse_h : v.z + off[s], l3 = s == 0 ? v.w - lse_h : v.w + off[s];
-      key[e0] = j < lim[s] ? lp_key(l0) : 0u;
-      key[e0 + 1] = j + 1 < lim[s] ? lp_key(l1) : 0u;
-      key[e0 + 2] = j + 2 < lim[s] ? lp_key(l2) : 0u;
-      key[e0 + 3] = j + 3 < lim[s] ? lp_key(l3) : 0u;
+      key[e0] = j < lim[s] ? lp_key(pen(l0, base[s] + j, j < lim[s])) : 0u;
+      key[e0 + 1] = j + 1 < lim[s] ? lp_key(pen(l1, base[s] + j + 1, j + 1 < lim[s])) : 0u;
+      key[e0 + 2] = j + 2 < lim[s] ? lp_key(pen(l2, base[s] + j + 2, j + 2 < lim[s])) : 0u;
+      key[e0 + 3] = j + 3 < lim[s] ? lp_key(pen(l3, base[s] + j + 3, j + 3 < lim[s])) : 0u;
       tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
     }
   auto each = [&](auto f) {
@@ -1220,16 +1367,17 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
         for (int e = 0; e < 4; ++e) f(key[(LPF_OFF[s] + q) * 4 + e], base[s] + (q * 1024 + tid) * 4 + e);
   };
   auto each_mem = [&](auto f) {                               // (the same keys: the same operations on the same logits)
-    for (int j = tid; j < p.c0; j += 1024) f(lp_key(rowp[0][j] - lse_h), j);
+    for (int j = tid; j < p.c0; j += 1024) f(lp_key(pen(rowp[0][j] - lse_h, j, true)), j);
     for (int s = 1; s < nseg; ++s)
-      for (int j = tid; j < n[s]; j += 1024) f(lp_key(rowp[s][j] + off[s]), base[s] + j);
+      for (int j = tid; j < n[s]; j += 1024) f(lp_key(pen(rowp[s][j] + off[s], base[s] + j, true)), base[s] + j);
   };
   sample_row<NUC>(each, each_mem, tmax, i, a, sm);
 }
 // Any row: the log-probs with the arithmetic of logprob_argmax_kernel (the three-pass form; its full-row output is what the
 // tests take top-k of), read from memory in every pass of the select.
-template <bool NUC>
-__global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs p, SampleArgs a) {
+template <bool NUC, bool PEN = false, class... P>
+__global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs p, SampleArgs a, P... pa_) {
+  const auto& pa = pen_pick(pa_...);
   __shared__ float red[16];
   __shared__ SampleSmem sm;
   const int i = blockIdx.x, tid = threadIdx.x;
@@ -1257,18 +1405,36 @@ __global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs
     s2 = block_sum(s2, red);
     off[c] = (hrow[p.c0 + c] - lse_h) - (m2 + __logf(s2));
   }
-  auto each = [&](auto f) {
-    for (int j = tid; j < p.c0; j += 1024) f(lp_key(hrow[j] - lse_h), j);
-    int base = p.c0;
-    for (int c = 0; c < p.n_tails; ++c) {
-      const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
-      for (int j = tid; j < p.tail_n[c]; j += 1024) f(lp_key(trow[j] + off[c]), base + j);
-      base += p.tail_n[c];
-    }
-  };
-  uint32_t tmax = 0;
-  each([&](uint32_t key, int) { tmax = max(tmax, key); });
-  sample_row<NUC>(each, each, tmax, i, a, sm);
+  if constexpr (!PEN) {                                       // (the unpenalised kernel: the code it always was)
+    auto each = [&](auto f) {
+      for (int j = tid; j < p.c0; j += 1024) f(lp_key(hrow[j] - lse_h), j);
+      int base = p.c0;
+      for (int c = 0; c < p.n_tails; ++c) {
+        const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+        for (int j = tid; j < p.tail_n[c]; j += 1024) f(lp_key(trow[j] + off[c]), base + j);
+        base += p.tail_n[c];
+      }
+    };
+    uint32_t tmax = 0;
+    each([&](uint32_t key, int) { tmax = max(tmax, key); });
+    sample_row<NUC>(each, each, tmax, i, a, sm);
+  } else {
+    const int np = pen_count(pa, i);
+    if (np > 0) pen_stage<1024>(pa, i, np);                   // (np is uniform over the workgroup)
+    auto pen = [&](float l, int idx) { return np > 0 && pen_bit(idx) ? pen_score(pa, np, idx, l) : l; };
+    auto each = [&](auto f) {
+      for (int j = tid; j < p.c0; j += 1024) f(lp_key(pen(hrow[j] - lse_h, j)), j);
+      int base = p.c0;
+      for (int c = 0; c < p.n_tails; ++c) {
+        const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+        for (int j = tid; j < p.tail_n[c]; j += 1024) f(lp_key(pen(trow[j] + off[c], base + j)), base + j);
+        base += p.tail_n[c];
+      }
+    };
+    uint32_t tmax = 0;
+    each([&](uint32_t key, int) { tmax = max(tmax, key); });
+    sample_row<NUC>(each, each, tmax, i, a, sm);
+  }
 }
 extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
@@ -1302,6 +1468,47 @@ extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int
   }
   hipLaunchKernelGGL(logprob_sample_stream_kernel<false>, dim3(rows), dim3(1024), 0, stream, p, a);
   return tell_check_launch("logprob_sample");
+}
+
+// tell_adaptive_logprob_sample over penalised scores (include/tell_hip.h): the arguments of tell_adaptive_logprob_sample
+// plus the penalty list of tell_adaptive_logprob_topk_penalised.
+extern "C" int tell_adaptive_logprob_sample_penalised(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
+                                                      long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
+                                                      long ld2, int n2, int rows, int k, float inv_temp, const uint32_t* seed_dev,
+                                                      const int* row_ids, int step, const int* step_dev, const int* pen_tok,
+                                                      const int* pen_cnt, long ld_pen, const int* n_pen, float theta,
+                                                      const float* sub, int n_sub, int* tokens, float* lps, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_sample_penalised: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample_penalised: 1 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_sample_penalised: inv_temp > 0");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample_penalised: seed_dev, tokens and lps are required");
+  PenArgs pa;
+  const int rc = pen_args(pa, c0, n_tails, n0, n1, n2, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
+  if (rc != TELL_OK) return rc;
+  TELL_REQUIRE(pa.vocab >= k, "logprob_sample_penalised: k <= vocab");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr; a.typ_c = nullptr;
+  const size_t lds = pen_lds(pa);
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    hipLaunchKernelGGL((logprob_sample_regs_kernel<false, true>), dim3(rows), dim3(1024), lds, stream, p, a, pa);
+    return tell_check_launch("logprob_sample_penalised (registers)");
+  }
+  hipLaunchKernelGGL((logprob_sample_stream_kernel<false, true>), dim3(rows), dim3(1024), lds, stream, p, a, pa);
+  return tell_check_launch("logprob_sample_penalised");
 }
 
 // steps 2-5 of the sampling semantics on given candidates (sorted best first): one thread per row

@@ -1871,6 +1871,64 @@ extern "C" int tell_decode_ban_list(const long* hist, long ld_hist, int L, const
   return tell_check_launch("decode_ban_list");
 }
 
+// ------------------------------------------------------------------ repetition penalties: the token counts of every row
+// Step i of a row with history h[0 .. i]: the distinct tokens of h[0 .. i] in order of first occurrence, each with the number
+// of positions that hold it; a finished row lists nothing.  One wave per row: the history goes to LDS, lane l owns positions
+// l, l + 64, ..; a position that is its token's first occurrence appends (token, count), a round's hits in lane order.
+__global__ __launch_bounds__(64) void decode_token_counts_kernel(const long* __restrict__ hist, long ld_hist, int L,
+                                                                 const uint8_t* __restrict__ finished, int step_host,
+                                                                 const int* step_dev, int* __restrict__ pen_tok,
+                                                                 int* __restrict__ pen_cnt, long ld_pen,
+                                                                 int* __restrict__ n_pen) {
+  __shared__ int hs[256];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  int step = step_dev ? *step_dev + 1 : step_host;
+  step = step < 0 ? 0 : (step > L - 1 ? L - 1 : step);
+  if (finished && finished[row]) {
+    if (lane == 0) n_pen[row] = 0;
+    return;
+  }
+  const long* h = hist + (long)row * ld_hist;
+  const int n = step + 1;                                  // (<= L <= 256)
+  for (int p = lane; p < n; p += 64) hs[p] = (int)h[p];
+  __syncthreads();
+  int* ot = pen_tok + (long)row * ld_pen;
+  int* oc = pen_cnt + (long)row * ld_pen;
+  int count = 0;
+  for (int p0 = 0; p0 < n; p0 += 64) {
+    const int p = p0 + lane;
+    bool first = p < n;
+    int t = 0, c = 0;
+    if (p < n) {
+      t = hs[p];
+      for (int q = 0; q < n; ++q) {
+        const bool same = hs[q] == t;
+        c += same ? 1 : 0;
+        if (same && q < p) first = false;
+      }
+    }
+    const unsigned long long hits = __ballot(first);
+    if (first) {
+      const int o = count + __popcll(hits & ((1ull << lane) - 1ull));      // (o < number of distinct tokens <= n <= ld_pen)
+      ot[o] = t;
+      oc[o] = c;
+    }
+    count += __popcll(hits);
+  }
+  if (lane == 0) n_pen[row] = count;
+}
+// hist / finished / step / step_dev as tell_decode_ban_list; pen_tok, pen_cnt int32 [rows, ld_pen >= L], n_pen int32 [rows].
+extern "C" int tell_decode_token_counts(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
+                                        const int* step_dev, int* pen_tok, int* pen_cnt, long ld_pen, int* n_pen,
+                                        hipStream_t stream) {
+  TELL_REQUIRE(rows > 0 && L >= 1 && L <= 256 && ld_hist >= L, "decode_token_counts: history [rows, L <= 256]");
+  TELL_REQUIRE(step_dev || (step >= 0 && step < L), "decode_token_counts: 0 <= step < L");
+  TELL_REQUIRE(hist && pen_tok && pen_cnt && n_pen && ld_pen >= L, "decode_token_counts: pen_tok / pen_cnt [rows, ld_pen >= L], n_pen [rows]");
+  hipLaunchKernelGGL(decode_token_counts_kernel, dim3(rows), dim3(64), 0, stream, hist, ld_hist, L, finished, step, step_dev,
+                     pen_tok, pen_cnt, ld_pen, n_pen);
+  return tell_check_launch("decode_token_counts");
+}
+
 // Rows of the DynamicConv input buffers follow their hypotheses (dynamic.py:338-342 reorder_incremental_state):
 // buf[p][r][:] <- buf[p][rows[r]][:] for every plane p of up to 8 buffers [planes, M, C] bf16, in place - rows[r] stays
 // inside r's group of K consecutive rows (a sample's hypotheses), so a workgroup that owns (plane, group) reads its K

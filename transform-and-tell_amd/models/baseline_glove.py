@@ -9,7 +9,8 @@ import math
 import torch
 
 from .. import ops
-from .transformer import CaptionModel, Model, check_beam_options, check_sampling, draw_seed, set_sampling
+from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_penalties, check_sampling, draw_seed,
+                          set_sampling)
 
 
 def _refuse_search_options(model, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, n_best=1):
@@ -31,9 +32,16 @@ class BaselineGloveModel(Model):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
                  weigh_bert=False, initializer=None, resnet=None, sampling_topp=None, beam_len_penalty=0.0,
-                 no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
+                 no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None, repetition_penalty=1.0,
+                 presence_penalty=0.0, frequency_penalty=0.0):
         super().__init__(vocab)
         _refuse_search_options(self, beam_len_penalty, no_repeat_ngram_size, min_len)
+        pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen != (1.0, 0.0, 0.0):
+            raise ValueError('%s: %s decodes with an LSTM decoder; the penalties cover the cached DynamicConv generator only'
+                             % (' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, pen, (1.0, 0.0, 0.0)) if v != d),
+                                type(self).__name__))
+        self.repetition_penalty, self.presence_penalty, self.frequency_penalty = pen
         for name, v in (('sampling_minp', sampling_minp), ('sampling_typical', sampling_typical)):
             if v is not None:
                 raise ValueError('%s=%r: %s has a decode step with its own decision launch (LSTM decoder); min-p and typical '
@@ -175,7 +183,8 @@ class TransformerGloveModel(CaptionModel):
     def __init__(self, vocab, decoder, criterion, evaluate_mode=False, attention_dim=1024, hidden_size=1024, dropout=0.1,
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
                  use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None,
-                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -189,6 +198,9 @@ class TransformerGloveModel(CaptionModel):
             beam_len_penalty, no_repeat_ngram_size, min_len)
         self._check_options()
         self._check_truncation()
+        self.repetition_penalty, self.presence_penalty, self.frequency_penalty = check_penalties(
+            repetition_penalty, presence_penalty, frequency_penalty)
+        self._check_penalties()
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0

@@ -53,14 +53,16 @@ class PointerModelBase(CaptionModel):
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
                  model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
-                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         if sampling_topk != 1 and sampling_topp is None and sampling_minp is None and sampling_typical is None:       # (with sampling_topp: the generated token is a nucleus draw)
             raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
         super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
                          model_name, namespace, index, padding_value, use_context, sampling_topk, sampling_temp,
                          weigh_bert, initializer, resnet, roberta, n_bert_layers, sampling_topp,
                          beam_len_penalty, no_repeat_ngram_size, min_len,   # (refused unless at their defaults: SEARCH_OPTIONS)
-                         sampling_minp, sampling_typical)                   # (... and so are these: _check_truncation)
+                         sampling_minp, sampling_typical,                   # (... and so are these: _check_truncation)
+                         repetition_penalty, presence_penalty, frequency_penalty)       # (... and these: _check_penalties)
         if weigh_bert:
             self.bert_weight_2 = nn.Parameter(torch.rand(n_bert_layers))      # :61-62
         self.batch_history = defaultdict(float)        # summed on the device (0-d tensors); floats once get_metrics reads

@@ -7,6 +7,15 @@ import torch
 
 from .. import decode, graphs, ops
 
+
+def sub_table(alpha, beta, L):
+    """The subtrahend table of the penalised pick kernels: fp32 [L + 1], sub[0] = 0, sub[c] = float32(float64(alpha) +
+    float64(beta) * c) - built on the host like the length-penalty table (inv_norm_table)."""
+    import numpy as np
+    t = np.zeros(int(L) + 1, dtype=np.float32)
+    t[1:] = (np.float64(alpha) + np.float64(beta) * np.arange(1, int(L) + 1, dtype=np.float64)).astype(np.float32)
+    return torch.from_numpy(t)
+
 # decode steps per graph replay once a generation loop is past its first all-finished test (DecodeStepper.multi)
 MULTI_STEP_GRAPHS = os.environ.get('TELL_MULTI_STEP_GRAPHS', '1') != '0'
 
@@ -40,15 +49,27 @@ class DecodeStepper:
     for the greedy decode).  opts: the caller's whole option tuple; it joins the signature when given (a captured
     bookkeeping launch differs with it), the default captures are keyed and recorded exactly as before.
 
+    pen = (theta, alpha, beta) (repetition / presence / frequency penalties): the head's last launch
+    becomes two - tell_decode_token_counts over the caller's histories (step.pen_source(hist, finished), like ban_source) with
+    the step index from the host or from the device counter, then the pick over penalised scores:
+    tell_adaptive_logprob_topk_penalised (k = 1 for the greedy decode) or, with sample = (k, T),
+    tell_adaptive_logprob_sample_penalised.  The list buffers and the `sub` table live in the cache entry, next to the graphs
+    that pin them.  ('penalty', theta, alpha, beta) joins the signature only when set; it does not combine with `ban`, with
+    attention maps or with a truncation rule.
+
     prefix=True (caption completion): the stepper owns a forcing table - int64 [samples, gen_len] + int32 [samples], static,
     filled per caption batch by step.set_prefix(tokens, plen) - and every head ends in tell_adaptive_logprob_forced with the
     step index from the host or from the device counter.  ('prefix',) joins the signature: its own captured graph, one for
     every prefix width; without it nothing is allocated, launched or keyed differently."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False):
+                 prefix=False, pen=None):
         if ban is not None and (sample is not None or attention):
             raise ValueError('no_repeat_ngram_size / min_len do not combine with sampling or attention maps')
+        if pen is not None and (ban is not None or attention or (sample is not None and len(sample) != 2)):
+            raise ValueError('repetition_penalty / presence_penalty / frequency_penalty do not combine with no_repeat_ngram_size '
+                             '/ min_len, attention maps or sampling_topp / sampling_minp / sampling_typical')
+        self.pen = None if pen is None else (float(pen[0]), float(pen[1]), float(pen[2]))
         dec = self.dec = model.decoder
         self.index, self.pad = model.index, int(model.padding_idx)
         self.B, self.gen_len, self.topk, self.n_hyp, self.lane = B, int(gen_len), topk, max(int(topk), 1), int(lane)
@@ -61,7 +82,7 @@ class DecodeStepper:
             self.h, self.state, self.ctx, self.kv = None, {}, contexts, kv
             self.seed = torch.zeros(1, dtype=torch.int32, device=dev)
             self.pfx = self._make_prefix(dev) if prefix else {}
-            self.ban_src = {}
+            self.ban_src, self.pen_src = {}, {}
             self.attn = self._make_sink(kv, dev) if attention else None
             self.cur = self.counter_out = self.back = None
             return
@@ -70,6 +91,7 @@ class DecodeStepper:
         self.state, self.ctx, self.kv = h['state'], h['ctx'], h['kv']
         # (the captured launches hold these buffers' addresses: from the entry, never freshly allocated)
         self.pfx, self.ban_src, self.attn = h.get('pfx', {}), h['ban_src'], h.get('attn')
+        self.pen_src = h.setdefault('pen_src', {}) if self.pen is not None else {}
         self.seed, self.cur = h['seed'], h['cur']
         self.c_cur, self.c_next = h['counter'][0:1], h['counter'][1:2]
         # where a bookkeeping launch leaves the next step's offset: the word the embedder's kernel reads (in-graph
@@ -104,6 +126,8 @@ class DecodeStepper:
             sig = sig + (('search', tuple(ban or ()), tuple(opts or ())),)
         if prefix:                                                # (... and every one without a forced prefix)
             sig = sig + (('prefix',),)
+        if self.pen is not None:                                  # (... and every one without penalties)
+            sig = sig + (('penalty',) + self.pen,)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -208,6 +232,24 @@ class DecodeStepper:
             ban_src['ban'] = torch.zeros(B, hist.shape[1] + 1, dtype=torch.int32, device=hist.device)
             ban_src['n_ban'] = torch.zeros(B, dtype=torch.int32, device=hist.device)
 
+    def pen_source(self, hist, fin):
+        """The histories the penalty lists are counted from (before every eager step; once when the buffers are static).  The
+        list buffers and the `sub` table (fp32 [L + 1]: sub[0] = 0, sub[c] = float32(alpha + beta * c) formed in fp64) are kept
+        while they fit: captured launches hold their addresses."""
+        B, src = self.B, self.pen_src
+        if self.pen is None:
+            raise ValueError('pen_source: the stepper was built without pen=(theta, alpha, beta)')
+        if hist.dtype != torch.long or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1 or \
+                hist.shape[1] > 256 or fin.dtype != torch.uint8 or fin.numel() != B or not fin.is_contiguous():
+            raise ValueError('pen_source: hist int64 [%d, L <= 256] and finished uint8 [%d] expected' % (B, B))
+        src['hist'], src['fin'] = hist, fin
+        L = hist.shape[1]
+        if 'tok' not in src or src['tok'].shape[1] < L or src['tok'].device != hist.device or src['sub'].numel() != L + 1:
+            src['tok'] = torch.zeros(B, L, dtype=torch.int32, device=hist.device)
+            src['cnt'] = torch.zeros(B, L, dtype=torch.int32, device=hist.device)
+            src['n_pen'] = torch.zeros(B, dtype=torch.int32, device=hist.device)
+            src['sub'] = sub_table(self.pen[1], self.pen[2], L).to(hist.device)
+
     def book(self, kind, make):
         """The caller's static bookkeeping buffers of this signature (made once: a captured bookkeeping launch pins them)."""
         if kind not in self.h['book']:
@@ -232,7 +274,8 @@ class DecodeStepper:
     # ---- one step -------------------------------------------------------------------
     def _head(self, x, sidx):
         """The head over the decoder's output x at step index sidx (the host's int, or the device counter of a captured
-        step): arg-max, top-k, a draw, or the banned top-k; with a forcing table every one of them ends in the forced pick."""
+        step): arg-max, top-k, a draw, the banned top-k, or - after the counts launch - the penalised top-k / draw; with a
+        forcing table every one of them ends in the forced pick."""
         soft, pfx = self.dec.adaptive_softmax, self.pfx
         force = (pfx['tab'], pfx['plen'], None, self.n_hyp, sidx, self.pad) if pfx else None
         if self.ban is not None:
@@ -244,6 +287,19 @@ class DecodeStepper:
                      src['ban'], src['ban'].stride(0), src['n_ban'])
             tok, lp = soft.topk(x, self.n_hyp, ban=(src['ban'], src['n_ban']), force=force)
             return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
+        pen = None
+        if self.pen is not None:
+            src = self.pen_src
+            hist = src['hist']
+            step_dev = sidx if torch.is_tensor(sidx) else None
+            ops.call('tell_decode_token_counts', hist, hist.stride(0), hist.shape[1], src['fin'], self.B,
+                     0 if step_dev is not None else int(sidx), step_dev, src['tok'], src['cnt'], src['tok'].stride(0),
+                     src['n_pen'])
+            pen = (self.pen[0], src['sub'], src['tok'], src['cnt'], src['n_pen'])
+            if self.sample is None:
+                tok, lp = soft.topk(x, self.n_hyp, force=force, pen=pen)
+                return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
+            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, pen=pen)
         if self.sample is not None:
             topp = self.sample[2] if len(self.sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
             rule = self.sample[3] if len(self.sample) > 3 else None      # 'minp' / 'typical': topp is m / tau

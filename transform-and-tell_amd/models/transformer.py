@@ -127,6 +127,22 @@ def check_beam_options(beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, 
     return float(a), int(n), int(m)
 
 
+PENALTY_KEYS = ('repetition_penalty', 'presence_penalty', 'frequency_penalty')
+
+
+def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """The soft repetition controls of the cached generators: `repetition_penalty` theta, finite and
+    >= 1; `presence_penalty` alpha and `frequency_penalty` beta, finite and >= 0.  A token that the caption already holds
+    c >= 1 times scores min(lp, 0) * theta - (alpha + beta * c) instead of its log-prob lp.  -> (theta, alpha, beta);
+    ValueError naming the option otherwise."""
+    out = []
+    for name, v, lo in zip(PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty), (1.0, 0.0, 0.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) < float('inf'):
+            raise ValueError('%s must be a finite number >= %g (got %r)' % (name, lo, v))
+        out.append(float(v))
+    return tuple(out)
+
+
 def check_prefix(prefix, batch_size, vocab_size, gen_len=DEFAULT_GEN_LEN, pad=1, eos=2):
     """The forced caption prefix of the cached generators: int64 [B, P], the caption tokens AFTER <s>,
     right-padded with `pad`; plen[r] = the number of leading non-pad tokens (0: the row decodes freely).  </s> may only be
@@ -305,7 +321,8 @@ class CaptionModel(Model):
                  dropout=0.1, vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta',
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
                  initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
-                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None):
+                 beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -324,6 +341,9 @@ class CaptionModel(Model):
             beam_len_penalty, no_repeat_ngram_size, min_len)
         self._check_options()
         self._check_truncation()
+        self.repetition_penalty, self.presence_penalty, self.frequency_penalty = check_penalties(
+            repetition_penalty, presence_penalty, frequency_penalty)
+        self._check_penalties()
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -406,6 +426,34 @@ class CaptionModel(Model):
             raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
                              'search options cover the cached DynamicConv generator only' % (what, type(self).__name__))
         return opts
+
+    def _penalties(self):
+        """-> (theta, alpha, beta) of the model's attributes, checked; None when all three are at their defaults."""
+        pen = check_penalties(getattr(self, 'repetition_penalty', 1.0), getattr(self, 'presence_penalty', 0.0),
+                              getattr(self, 'frequency_penalty', 0.0))
+        return None if pen == (1.0, 0.0, 0.0) else pen
+
+    def _check_penalties(self, attention=False):
+        """What the penalties combine with: the arg-max, beam and top-k sampling decodes of the cached
+        DynamicConv generator - no truncation rule, no ban options, no attention maps, not the LSTM decoders nor the copy
+        models.  -> (theta, alpha, beta) or None."""
+        pen = self._penalties()
+        if pen is None:
+            return None
+        what = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, pen, (1.0, 0.0, 0.0)) if v != d)
+        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
+            if getattr(self, name, None) is not None:
+                raise ValueError('%s and %s=%r do not combine: the penalties cover the arg-max, beam and top-k sampling decodes'
+                                 % (what, name, getattr(self, name)))
+        for name in ('no_repeat_ngram_size', 'min_len'):
+            if getattr(self, name, 0):
+                raise ValueError('%s and %s=%r do not combine: one list per pick launch' % (what, name, getattr(self, name)))
+        if attention:
+            raise ValueError('%s and attention=True do not combine: attention maps are exported without penalties' % what)
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
+                             'penalties cover the cached DynamicConv generator only' % (what, type(self).__name__))
+        return pen
 
     def _check_prefix(self, prefix, batch_size, gen_len=DEFAULT_GEN_LEN, eos=2):
         """generate(prefix=...): check_prefix against this model; the cached DynamicConv generators only - the LSTM decoders
@@ -685,6 +733,10 @@ class CaptionModel(Model):
         report the model's log-prob of it; 'gen_ids' is <s>, the prefix, the generated rest, 'log_probs' has one entry per
         step (forced steps: the teacher-forced log-probs), 'prefix_len' [B] is plen.  None: exactly the launches of before.
         'scores' [B]: the score of every caption (sum of its log-probs; beam search with `beam_len_penalty` alpha: * len ** -alpha).
+        With `repetition_penalty` / `presence_penalty` / `frequency_penalty` set every pick is taken over
+        penalised scores s = min(lp, 0) * theta - (alpha + beta * count) for the tokens the caption already holds, and
+        'log_probs' / 'scores' (and their n-best forms) then hold THOSE SCORES, not log-probs - the convention of the
+        generators that introduced these penalties; forced prefix steps still report the model's own log-prob.
         n_best = n (2..beam_size): also 'gen_ids_nbest' [B, n, L], 'log_probs_nbest' [B, n, L - 1], 'scores_nbest' [B, n] - the
         n best hypotheses of the beam, best first ('gen_ids' / 'log_probs' stay hypothesis 0).
         attention=True (greedy / top-k / nucleus, DynamicConv decoders): 'attns' is a dict name -> fp32 device tensor
@@ -761,6 +813,7 @@ class CaptionModel(Model):
                 return
         self._check_beam(beam_size)
         self._check_options(beam_size, attention, n_best)
+        self._check_penalties(attention)
         it = iter(batches)
         main = torch.cuda.current_stream()
         lane_streams = [streams.get('decode_lane_%d' % i) for i in range(lanes)]
@@ -873,6 +926,8 @@ class CaptionModel(Model):
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
                   prefix=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
+        if self._check_penalties(attention) is not None:      # (the penalties live in the cached generators, like `opts`)
+            opts = opts or (0.0, 0, 0)
         if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
             self._check_prefix(prefix[0], caption_ids.shape[0], gen_len, eos)
         if attention:
@@ -925,7 +980,9 @@ class CaptionModel(Model):
         per step); the third result is then an AttnMaps (maps {name: [B, steps, n_layers, S + 2] fp32}, steps [B]) instead of [].
         prefix = (tokens int64 [B, P], plen int32 [B]) of check_prefix: the stepper's forcing table is filled before the first step
         and the head of every step ends in one more launch (tell_adaptive_logprob_forced); the bookkeeping is untouched - it
-        books a forced token exactly as a picked one."""
+        books a forced token exactly as a picked one.
+        With penalties set (_penalties()): the head counts every row's tokens (step.pen_source over `ids`) and picks - arg-max or
+        top-k draw - over the penalised scores, which is what `log_probs` then holds."""
         dec = self.decoder
         B = caption_ids.shape[0]
         dev = caption_ids.device
@@ -934,8 +991,9 @@ class CaptionModel(Model):
         opts = self._check_options(1, attention, 1, gen_len)
         # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
         ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
+        pen = self._check_penalties(attention)
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
-                                    prefix=prefix is not None)
+                                    prefix=prefix is not None, **({'pen': pen} if pen is not None else {}))
         if prefix is not None:
             step.set_prefix(*prefix)
         if sampling is not None:
@@ -955,6 +1013,8 @@ class CaptionModel(Model):
             done_step.fill_(gen_len)
             if ban is not None:
                 step.ban_source(ids, fin8)
+            if pen is not None:
+                step.pen_source(ids, fin8)
         else:
             ids = torch.full((B, gen_len + 1), self.padding_idx, dtype=torch.long, device=dev)
             lps = torch.zeros(B, gen_len, dtype=torch.float32, device=dev)
@@ -977,6 +1037,8 @@ class CaptionModel(Model):
         for i in range(0 if fused else gen_len):
             if ban is not None:
                 step.ban_source(ids, finished.to(torch.uint8))
+            if pen is not None:
+                step.pen_source(ids, finished.to(torch.uint8))
             tok, lp = step(i, cur)
             yield i
             tok = tok.long().view(B)
@@ -1002,11 +1064,11 @@ class CaptionModel(Model):
         return lps[:, :steps], ids[:, :steps + 1], attns
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False):
+                        prefix=False, pen=None):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
-                             opts=opts, prefix=prefix)
+                             opts=opts, prefix=prefix, pen=pen)
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
@@ -1025,7 +1087,9 @@ class CaptionModel(Model):
         n_best = n > 1, .nbest = (ids [B,n,steps+1], log_probs [B,n,steps], scores [B,n]).
         prefix = (tokens, plen) of check_prefix: during a sample's forced steps every hypothesis' candidate list is the forced
         token and K - 1 fillers (-inf, pad), so only slot 0 stays live - as at step 0 - and the beam opens at the first free
-        step; the bookkeeping is untouched."""
+        step; the bookkeeping is untouched.
+        With penalties set (_penalties()): every hypothesis' K best are taken over its penalised scores (step.pen_source over
+        `seqs`), and `cum`, the log_probs and the scores accumulate those scores."""
         dec = self.decoder
         B, K = caption_ids.shape[0], int(beam_size)
         dev = caption_ids.device
@@ -1038,8 +1102,10 @@ class CaptionModel(Model):
         # sample as K query positions of that sample (modules/attention.py), nothing is replicated per beam
         ctx = {k_: v_ for k_, v_ in contexts.items() if torch.is_tensor(v_)}
         kv = dec.project_contexts(contexts)
+        pen = self._check_penalties()
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
-                                    opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None)
+                                    opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None,
+                                    **({'pen': pen} if pen is not None else {}))
         if prefix is not None:
             step.set_prefix(*prefix)
         cur = rep(caption_ids[:, 0:1], 0)
@@ -1083,6 +1149,8 @@ class CaptionModel(Model):
 
             if ban is not None:
                 step.ban_source(seqs.view(B * K, gen_len + 1), fin8.view(B * K))
+            if pen is not None:
+                step.pen_source(seqs.view(B * K, gen_len + 1), fin8.view(B * K))
 
             def book(out, i, step_dev):
                 tk, lp = out
@@ -1106,6 +1174,8 @@ class CaptionModel(Model):
             # each hypothesis contributes its own K best tokens (the best K of K x V always lie among them)
             if ban is not None:
                 step.ban_source(seqs.view(B * K, -1).contiguous(), finished.to(torch.uint8).view(B * K).contiguous())
+            if pen is not None:
+                step.pen_source(seqs.view(B * K, -1).contiguous(), finished.to(torch.uint8).view(B * K).contiguous())
             tk, lp = step(i, cur)
             tk, lp = tk.view(B, K, K).long(), lp.view(B, K, K) / self.sampling_temp
             # a finished hypothesis has ONE continuation: pad, at no cost

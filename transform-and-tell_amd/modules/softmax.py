@@ -74,31 +74,40 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k, ban=None, force=None):
+    def topk(self, X, k, ban=None, force=None, pen=None):
         """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
         ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
-        (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans)."""
+        (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans).
+        pen = (theta, sub fp32 [n_sub], pen_tok int32 [B * T, ld], pen_cnt alike, n_pen int32 [B * T]): the k best PENALISED
+        scores s = min(lp, 0) * theta - sub[count] of the listed tokens, lp of every other (DESIGN.md section 20,
+        tell_adaptive_logprob_topk_penalised); the second result then holds scores, not log-probs."""
         B, T, E = X.shape
+        kw = {'pen': pen} if pen is not None else {}
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force)
+                                            self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force, **kw)
         return tok.view(B, T, k), lp.view(B, T, k)
 
-    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None):
+    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None, pen=None):
         """One top-k draw with temperature per position (transformer_faces_objects.py:443-470: lprobs.topk(k), / temp,
         multinomial), fused like `greedy`: -> (token [B, T], log-prob [B, T] WITHOUT the temperature).  seed_dev: int32 [1]
         device word holding the seed; step: host step index or the int32 [1] device counter of a captured step (step - 1);
         row_ids: int32 [B * T] original batch rows (compacted batches), default the row index
         (include/tell_hip.h tell_adaptive_logprob_sample).  topp = p: the nucleus draw instead (k = 0: no top-k cut;
         tell_adaptive_logprob_nucleus) - the same launches up to the last one.  rule = 'minp' / 'typical': topp is that
-        rule's parameter (m / tau; k = 0; tell_adaptive_logprob_minp / tell_adaptive_logprob_typical)."""
+        rule's parameter (m / tau; k = 0; tell_adaptive_logprob_minp / tell_adaptive_logprob_typical).
+        pen (as in `topk`; the top-k draw only): the draw runs over the penalised scores and the second result is the drawn
+        token's score (tell_adaptive_logprob_sample_penalised)."""
+        if pen is not None and (topp is not None or rule is not None):
+            raise ValueError('sample: penalties go with the top-k draw, not with sampling_topp / sampling_minp / sampling_typical')
         B, T, E = X.shape
+        kw = {'pen': pen} if pen is not None else {}
         sample = (int(k), 1.0 / float(temp), seed_dev, row_ids, step)
         if topp is not None:
             sample = sample + (float(topp),)
         if rule is not None:
             sample = sample + (rule,)
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), sample=sample, force=force)
+                                            self.head.class_proj.weight, self._tails(), sample=sample, force=force, **kw)
         return tok.view(B, T), lp.view(B, T)
 
     def greedy(self, X, force=None):

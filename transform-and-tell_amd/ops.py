@@ -1744,15 +1744,30 @@ def adaptive_loss(x, target, cutoffs, pad_idx, emb0, class_proj, tails):
     return AdaptiveLossFn.apply(x, target, tuple(cutoffs), pad_idx, emb0, class_proj, *tails)
 
 
-def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
+def _pen_args(pen, N):
+    """pen = (theta, sub fp32 [n_sub] device, pen_tok int32 [N, ld], pen_cnt int32 [N, ld], n_pen int32 [N]) -> the list
+    arguments of the penalised entry points, checked."""
+    theta, sub, pen_tok, pen_cnt, n_pen = pen
+    if pen_tok.dtype != torch.int32 or pen_cnt.dtype != torch.int32 or n_pen.dtype != torch.int32 or pen_tok.dim() != 2 or \
+            pen_tok.shape != pen_cnt.shape or pen_tok.stride() != pen_cnt.stride() or pen_tok.stride(1) != 1 or \
+            pen_tok.shape[0] != N or n_pen.numel() != N or not n_pen.is_contiguous() or sub.dtype != torch.float32 or \
+            sub.dim() != 1 or not sub.is_contiguous() or sub.numel() < 1:
+        raise ValueError('penalties: pen_tok / pen_cnt int32 [%d, ld], n_pen int32 [%d] and sub fp32 [n_sub] expected' % (N, N))
+    return pen_tok, pen_cnt, pen_tok.stride(0), n_pen, float(theta), sub, sub.numel()
+
+
+def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None):
     """The sampling head's last launch (tell_adaptive_logprob_sample) over the fp32 logits of the head and the tails.
     sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
     int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
     counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None).
     A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut); a seventh names another
     rule for the sixth: 'minp' (m: tell_adaptive_logprob_minp, log(m) formed here in fp64) or 'typical' (tau:
-    tell_adaptive_logprob_typical) - both over the whole row, k = 0."""
+    tell_adaptive_logprob_typical) - both over the whole row, k = 0.  pen (see _pen_args; the top-k draw only): the draw runs
+    over the penalised scores (tell_adaptive_logprob_sample_penalised) and the second result is the token's score."""
     k, inv_temp, seed_dev, row_ids, step = sample[:5]
+    if pen is not None and len(sample) > 5:
+        raise ValueError('logprob_sample: penalties go with the top-k draw, not with a truncation rule')
     step_dev = step if torch.is_tensor(step) else None
     token = torch.empty(N, dtype=torch.int32, device=head.device)
     token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
@@ -1772,18 +1787,29 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample):
              lds[2], ns[2], N, int(k), float(inv_temp), float(sample[5]), seed_dev, row_ids,
              0 if step_dev is not None else int(step), step_dev, token, token_lp, None, None)
         return token, token_lp, None
+    if pen is not None:
+        call('tell_adaptive_logprob_sample_penalised', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
+             tl[2], lds[2], ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step),
+             step_dev, *_pen_args(pen, N), token, token_lp)
+        return token, token_lp, None
     call('tell_adaptive_logprob_sample', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
          ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token,
          token_lp)
     return token, token_lp, None
 
 
-def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None):
+def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None):
     """The top-k head's last launch: tell_adaptive_logprob_topk, or - ban = (ban int32 [N, ld_ban], n_ban int32 [N]) -
-    tell_adaptive_logprob_topk_banned.  -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
+    tell_adaptive_logprob_topk_banned, or - pen (see _pen_args) - tell_adaptive_logprob_topk_penalised, whose second result
+    holds the penalised scores.  -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
     tokens = torch.empty(N, k, dtype=torch.int32, device=head.device)
     lps = torch.empty(N, k, dtype=torch.float32, device=head.device)
-    if ban is None:
+    if pen is not None:
+        if ban is not None:
+            raise ValueError('logprob_topk: a ban list and penalties do not combine')
+        call('tell_adaptive_logprob_topk_penalised', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
+             tl[2], lds[2], ns[2], N, int(k), *_pen_args(pen, N), tokens, lps)
+    elif ban is None:
         call('tell_adaptive_logprob_topk', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
              lds[2], ns[2], N, int(k), tokens, lps)
     else:
@@ -1814,12 +1840,16 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
     return picked
 
 
-def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None):
+def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None,
+                       pen=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
     draw per row instead of the arg-max
-    (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced)."""
+    (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced);
+    pen (see _pen_args; with topk = k >= 1 or a top-k draw): the pick runs over the penalised scores."""
+    if pen is not None and (want_full or (not topk and sample is None)):
+        raise ValueError('adaptive_log_probs: penalties go with topk = k >= 1 or a top-k draw')
     if force is not None and want_full:
         raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
     N, E = x2.shape
@@ -1831,6 +1861,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
+        if pen is not None:      # (a call without penalties is the call it was: stand-ins for head_step keep working)
+            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen)
         return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
@@ -1849,9 +1881,9 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     def forced(picked):
         return picked if force is None else logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
     if sample is not None and not want_full:
-        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample))
+        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample, pen=pen))
     if topk:
-        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban))
+        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban, pen=pen))
     if ban is not None:
         raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
     full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
