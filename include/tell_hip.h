@@ -302,6 +302,28 @@ int tell_decode_token_counts(const long* hist, long ld_hist, int L, const uint8_
  * input buffers kept in time order (the layer-by-layer fp32 step); the rings of tell_dynconv_step are never moved. */
 int tell_reorder_rows(int n, void* const* bufs, const int* planes, const long* rows, int M, int C, int K,
                       tell_stream_t stream);
+/* The n sampled hypotheses of every image (generate(n_samples=n)): duplicates flagged, scored and
+ * ranked in one launch behind the decode loop, one workgroup per image.  Hypothesis j of image b is row r = b * n + j of
+ * ids int64 [B * n, ld_ids >= steps + 1] (column 0 = <s>), lps fp32 [B * n, ld_lps >= steps] and done_step int64 [B * n]
+ * (the bookkeeping buffers of tell_greedy_update); 1 <= n <= 16, 1 <= steps <= 256.
+ *   len[r]   = min(max(done_step[r], 0), steps): the steps the row took part in, its </s> included;
+ *   score[r] = (lps[r][0] + .. + lps[r][len - 1]) * inv_norm[len]: ONE fp32 accumulator, added in ascending order, then one
+ *              fp32 multiply (inv_norm fp32 [>= steps + 1], the table of tell_beam_update_norm; NULL: no multiply) - a
+ *              sequential fp32 loop on the host gives the same bits;
+ *   dup[b][j] = 1 when some j' < j of the image has the same len and the same tokens ids[..][1 .. len] (what lies behind
+ *              a row's </s> is not compared);
+ *   cons[b][i] (rule 2, or whenever cons is given): with big(i) the MULTISET of token-id bigrams of the generated tokens
+ *              ids[r][1 .. len] without a final `eos`, u(i, j) = 2 |big(i) n big(j)| / (|big(i)| + |big(j)|) (counts clipped
+ *              to the smaller one; 0 when the denominator is 0; the quotient of two exact fp32 integers), cons = the sum
+ *              of u(i, j) over j != i - duplicates included - in ascending j, divided by n - 1; 0 for n = 1.
+ *   order[b][.]: the hypotheses of the image, first rank first.  rule 0 (draw): the identity.  rule 1 (score): every
+ *              non-duplicate before every duplicate, then score descending, then the lower j.  rule 2 (consensus):
+ *              non-duplicates first, then cons descending, then score descending, then the lower j.  A NaN key ranks as -inf.
+ * out: order int32, score fp32, dup uint8 [B, n]; cons fp32 [B, n] (may be NULL unless rule = 2); len int32 [B, n] (may be
+ * NULL).  `pad` is not read: a row is cut at len.  No atomics, no scratch in global memory; at most 16 x 256 tokens in LDS. */
+int tell_sample_rank(const long* ids, long ld_ids, const float* lps, long ld_lps, const long* done_step,
+                     const float* inv_norm, int B, int n, int steps, int pad, int eos, int rule, int* order, float* score,
+                     uint8_t* dup, float* cons, int* len, tell_stream_t stream);
 
 /* ---- LayerNorm: y = LN(res + dropout(x)), decoder_faces_objects.py:263-266,367-372 */
 int tell_layernorm_fwd(const void* x, long ld_x, const void* res, long ld_r, const float* gamma,

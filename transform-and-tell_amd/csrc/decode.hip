@@ -1968,3 +1968,146 @@ extern "C" int tell_reorder_rows(int n, void* const* bufs, const int* planes, co
   hipLaunchKernelGGL(reorder_rows_kernel, dim3(a.plane0[n], M / K), dim3(128), 0, stream, a, rows, M, C, K);
   return tell_check_launch("reorder_rows");
 }
+
+// ------------------------------------------------------------------ n sampled captions per image: duplicates, scores, rank
+// tell_sample_rank (include/tell_hip.h): one wave per image, behind the decode loop.  Lane j < n owns hypothesis j wherever a
+// result is one number per hypothesis (len, the sequential score sum, cons, the rank); the token comparisons and the bigram
+// counts are striped over the 64 lanes.  LDS: the tokens [16][256], per bigram position its count inside its own hypothesis
+// (0 unless it is the bigram's first occurrence) [16][256], u [16][16].
+constexpr int SR_N = 16, SR_L = 256;
+__global__ __launch_bounds__(64) void sample_rank_kernel(const long* __restrict__ ids, long ld_ids,
+                                                         const float* __restrict__ lps, long ld_lps,
+                                                         const long* __restrict__ done_step,
+                                                         const float* __restrict__ inv_norm, int n, int steps, int eos,
+                                                         int rule, int* __restrict__ order, float* __restrict__ score,
+                                                         uint8_t* __restrict__ dup, float* __restrict__ cons,
+                                                         int* __restrict__ len_out) {
+  __shared__ int tok[SR_N][SR_L];
+  __shared__ int own[SR_N][SR_L];
+  __shared__ float u[SR_N][SR_N];
+  __shared__ int len_s[SR_N], nbig[SR_N], dup_s[SR_N];
+  __shared__ float score_s[SR_N], key_s[SR_N];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long r0 = (long)b * n;
+  if (lane < n) {
+    const long d = done_step[r0 + lane];
+    const int len = d < 0 ? 0 : (d > steps ? steps : (int)d);
+    const float* lp = lps + (r0 + lane) * ld_lps;
+    float s = 0.f;
+    for (int p = 0; p < len; ++p) s += lp[p];
+    if (inv_norm) s = s * inv_norm[len];
+    len_s[lane] = len;
+    score_s[lane] = s;
+    score[r0 + lane] = s;
+    if (len_out) len_out[r0 + lane] = len;
+  }
+  __syncthreads();
+  for (int j = 0; j < n; ++j) {
+    const long* h = ids + (r0 + j) * ld_ids + 1;
+    for (int p = lane; p < len_s[j]; p += 64) tok[j][p] = (int)h[p];
+  }
+  __syncthreads();
+  // duplicates: same length, same tokens as an earlier draw
+  for (int j = 0; j < n; ++j) {
+    const int len = len_s[j];
+    int is_dup = 0;
+    for (int e = 0; e < j && !is_dup; ++e) {
+      if (len_s[e] != len) continue;
+      bool differ = false;
+      for (int p = lane; p < len; p += 64) differ = differ || tok[j][p] != tok[e][p];
+      if (__ballot(differ) == 0ull) is_dup = 1;
+    }
+    if (lane == 0) dup_s[j] = is_dup;
+  }
+  if (cons) {
+    // bigrams of a hypothesis: positions 0 .. nbig - 1 of its tokens without the final eos
+    for (int j = 0; j < n; ++j) {
+      const int len = len_s[j];
+      const int m = len - ((len > 0 && tok[j][len - 1] == eos) ? 1 : 0);
+      const int nb = m > 1 ? m - 1 : 0;
+      if (lane == 0) nbig[j] = nb;
+      for (int p = lane; p < nb; p += 64) {
+        const int t0 = tok[j][p], t1 = tok[j][p + 1];
+        int c = 0;
+        bool first = true;
+        for (int q = 0; q < nb; ++q) {
+          const bool same = tok[j][q] == t0 && tok[j][q + 1] == t1;
+          c += same ? 1 : 0;
+          if (same && q < p) first = false;
+        }
+        own[j][p] = first ? c : 0;
+      }
+    }
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+      for (int j = i + 1; j < n; ++j) {
+        const int nbi = nbig[i], nbj = nbig[j];
+        int acc = 0;
+        for (int p = lane; p < nbi; p += 64) {
+          const int ci = own[i][p];
+          if (ci == 0) continue;
+          const int t0 = tok[i][p], t1 = tok[i][p + 1];
+          int cj = 0;
+          for (int q = 0; q < nbj; ++q) cj += (tok[j][q] == t0 && tok[j][q + 1] == t1) ? 1 : 0;
+          acc += ci < cj ? ci : cj;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) {
+          const int den = nbi + nbj;
+          const float v = den > 0 ? (float)(2 * acc) / (float)den : 0.f;
+          u[i][j] = v;
+          u[j][i] = v;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (lane < n) {
+    float c = 0.f;
+    if (cons) {
+      for (int j = 0; j < n; ++j)
+        if (j != lane) c += u[lane][j];
+      c = n > 1 ? c / (float)(n - 1) : 0.f;
+      cons[r0 + lane] = c;
+    }
+    float key = rule == 2 ? c : score_s[lane];
+    if (key != key) key = -INFINITY;
+    key_s[lane] = key;
+    dup[r0 + lane] = (uint8_t)dup_s[lane];
+  }
+  __syncthreads();
+  if (lane < n) {
+    int rank = lane;
+    if (rule != 0) {
+      rank = 0;
+      const int dj = dup_s[lane];
+      const float kj = key_s[lane], sj = score_s[lane];
+      for (int e = 0; e < n; ++e) {
+        if (e == lane) continue;
+        const int de = dup_s[e];
+        const float ke = key_s[e], se = score_s[e];
+        bool before;                                        // e ranks before this hypothesis
+        if (de != dj) before = de < dj;
+        else if (ke > kj) before = true;
+        else if (ke < kj) before = false;
+        else if (rule == 2 && se > sj) before = true;
+        else if (rule == 2 && se < sj) before = false;
+        else before = e < lane;
+        rank += before ? 1 : 0;
+      }
+    }
+    order[r0 + rank] = lane;
+  }
+}
+extern "C" int tell_sample_rank(const long* ids, long ld_ids, const float* lps, long ld_lps, const long* done_step,
+                                const float* inv_norm, int B, int n, int steps, int pad, int eos, int rule, int* order,
+                                float* score, uint8_t* dup, float* cons, int* len, hipStream_t stream) {
+  (void)pad;
+  TELL_REQUIRE(B > 0 && n >= 1 && n <= SR_N && steps >= 1 && steps <= SR_L, "sample_rank: 1 <= n <= 16, 1 <= steps <= 256");
+  TELL_REQUIRE(ids && lps && done_step && ld_ids >= steps + 1 && ld_lps >= steps, "sample_rank: ids [B n, > steps], lps [B n, >= steps]");
+  TELL_REQUIRE(order && score && dup && rule >= 0 && rule <= 2 && (cons || rule != 2), "sample_rank: rule 0 .. 2; cons with rule 2");
+  hipLaunchKernelGGL(sample_rank_kernel, dim3(B), dim3(64), 0, stream, ids, ld_ids, lps, ld_lps, done_step, inv_norm, n, steps,
+                     eos, rule, order, score, dup, cons, len);
+  return tell_check_launch("sample_rank");
+}

@@ -106,8 +106,14 @@ class BaselineGloveModel(Model):
         self.n_batches += 1
         return out
 
-    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None):
+    def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None,
+                 n_samples=1, rank_by='score', rank_len_penalty=0.0):
         _refuse_search_options(self, n_best=n_best)
+        from .transformer import check_n_samples
+        if check_n_samples(n_samples, rank_by, rank_len_penalty)[0] > 1:
+            raise ValueError('n_samples=%d: %s decodes with an LSTM decoder, whose step has its own decision launch; several '
+                             'samples per image cover the cached DynamicConv generator only (DESIGN.md section 21)'
+                             % (n_samples, type(self).__name__))
         if prefix is not None:
             raise ValueError('prefix: %s decodes with an LSTM decoder, whose step has its own decision launch; a forced '
                              'prefix is out of scope there (DESIGN.md section 17)' % type(self).__name__)
@@ -226,16 +232,18 @@ class TransformerGloveModel(CaptionModel):
         return out
 
     def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1,
-                 prefix=None):
+                 prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0):
         if attention:
             self._check_attention(beam_size)
         self._check_options(beam_size, attention, n_best)
+        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
-                                                   **({'prefix': pfx} if pfx is not None else {}))
+                                                   **({'prefix': pfx} if pfx is not None else {}),
+                                                   **({'samples': ns} if ns is not None else {}))
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
             out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)

@@ -170,13 +170,15 @@ class PointerModelBase(CaptionModel):
 
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
+                 rank_by='score', rank_len_penalty=0.0):
         if attention:
             self._check_attention(beam_size)
         if prefix is not None:
             self._check_prefix(prefix, 0)                             # (refused: the copy decision is out of scope)
         self._check_beam(beam_size)
         self._check_options(beam_size, attention, n_best)
+        self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)   # (n > 1 refused, like the prefix)
         self._require_masks(context)
         enc = encoded if encoded is not None else self.encode(context, image)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, None, enc)

@@ -60,10 +60,18 @@ class DecodeStepper:
     prefix=True (caption completion): the stepper owns a forcing table - int64 [samples, gen_len] + int32 [samples], static,
     filled per caption batch by step.set_prefix(tokens, plen) - and every head ends in tell_adaptive_logprob_forced with the
     step index from the host or from the device counter.  ('prefix',) joins the signature: its own captured graph, one for
-    every prefix width; without it nothing is allocated, launched or keyed differently."""
+    every prefix width; without it nothing is allocated, launched or keyed differently.
+
+    hyp = n > 1 (generate(n_samples=n); without topk): the B rows are n sampled hypotheses of each of
+    B / n samples, row = sample * n + j, over contexts and K/V of width B / n - what beam search hands in with topk = K, but no
+    row ever moves: the DynamicConv rings get no ancestor table, the forcing table has B / n rows (beams = n in the forced
+    launch).  ('hyp', n) joins the signature only then."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False, pen=None):
+                 prefix=False, pen=None, hyp=1):
+        if int(hyp) > 1 and (topk or attention or sample is None or B % int(hyp)):
+            raise ValueError('hyp = %d hypotheses per sample: a sampling step without beam search or attention maps, over a '
+                             'multiple of %d rows' % (int(hyp), int(hyp)))
         if ban is not None and (sample is not None or attention):
             raise ValueError('no_repeat_ngram_size / min_len do not combine with sampling or attention maps')
         if pen is not None and (ban is not None or attention or (sample is not None and len(sample) != 2)):
@@ -73,6 +81,7 @@ class DecodeStepper:
         dec = self.dec = model.decoder
         self.index, self.pad = model.index, int(model.padding_idx)
         self.B, self.gen_len, self.topk, self.n_hyp, self.lane = B, int(gen_len), topk, max(int(topk), 1), int(lane)
+        self.per_sample = max(self.n_hyp, int(hyp))               # rows that share one sample's contexts and prefix
         self.sample, self.ban = sample, ban
         names = [n for layer_kv in kv[:1] for n in layer_kv]
         self.static = bool(graphs.ENABLED and not model.training and torch.is_tensor(kv[0][names[0]][0]) and
@@ -101,8 +110,8 @@ class DecodeStepper:
 
     # ---- the cache entry ------------------------------------------------------------
     def _make_prefix(self, device):
-        return {'tab': torch.full((self.B // self.n_hyp, self.gen_len), self.pad, dtype=torch.long, device=device),
-                'plen': torch.zeros(self.B // self.n_hyp, dtype=torch.int32, device=device)}
+        return {'tab': torch.full((self.B // self.per_sample, self.gen_len), self.pad, dtype=torch.long, device=device),
+                'plen': torch.zeros(self.B // self.per_sample, dtype=torch.int32, device=device)}
 
     def _make_sink(self, kv, device):
         return decode.AttnSink([{n: torch.zeros(self.gen_len, self.B, int(pair[0].shape[0]) + 2, dtype=torch.float32,
@@ -128,6 +137,8 @@ class DecodeStepper:
             sig = sig + (('prefix',),)
         if self.pen is not None:                                  # (... and every one without penalties)
             sig = sig + (('penalty',) + self.pen,)
+        if self.per_sample > self.n_hyp:                          # (... and every one with one draw per sample)
+            sig = sig + (('hyp', self.per_sample),)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -277,7 +288,7 @@ class DecodeStepper:
         step): arg-max, top-k, a draw, the banned top-k, or - after the counts launch - the penalised top-k / draw; with a
         forcing table every one of them ends in the forced pick."""
         soft, pfx = self.dec.adaptive_softmax, self.pfx
-        force = (pfx['tab'], pfx['plen'], None, self.n_hyp, sidx, self.pad) if pfx else None
+        force = (pfx['tab'], pfx['plen'], None, self.per_sample, sidx, self.pad) if pfx else None
         if self.ban is not None:
             ban, src = self.ban, self.ban_src
             hist = src['hist']

@@ -192,12 +192,91 @@ def inv_norm_table(alpha, L):
     return torch.from_numpy(t)
 
 
+MAX_N_SAMPLES = 16              # tell_sample_rank's hypotheses per image
+RANK_BY = ('draw', 'score', 'consensus')
+
+
+def check_n_samples(n_samples=1, rank_by='score', rank_len_penalty=0.0):
+    """generate(n_samples=, rank_by=, rank_len_penalty=): n an integer in 1..16, the rank rule one of
+    'draw' / 'score' / 'consensus', alpha a finite number >= 0 (score = sum of log-probs * len ** -alpha, as beam_len_penalty).
+    -> (n, rule, alpha); ValueError otherwise."""
+    n = n_samples
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_N_SAMPLES:
+        raise ValueError('n_samples must be an integer in 1..%d (got %r)' % (MAX_N_SAMPLES, n))
+    if not isinstance(rank_by, str) or rank_by not in RANK_BY:
+        raise ValueError('rank_by must be one of %s (got %r)' % (', '.join(repr(r) for r in RANK_BY), rank_by))
+    a = rank_len_penalty
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) < float('inf'):
+        raise ValueError('rank_len_penalty must be a finite number >= 0 (got %r)' % (a,))
+    return n, rank_by, float(a)
+
+
+def sample_rank_definition(ids, lps, done_step, n, steps, eos, rule, inv_norm=None):
+    """The contract of tell_sample_rank (include/tell_hip.h) in numpy on the host - what the kernel is tested against and what
+    ranks hypotheses that live on the CPU.  ids [B * n, > steps], lps [B * n, >= steps], done_step [B * n]; rule 'draw' /
+    'score' / 'consensus' (or 0 / 1 / 2); inv_norm fp32 [>= steps + 1] or None.
+    -> dict of [B, n] arrays: len int32, score fp32 (sequential fp32 sum, one fp32 multiply), dup uint8, cons fp32, order int32."""
+    import functools
+    from collections import Counter
+    import numpy as np
+    ids, done = np.asarray(ids), np.asarray(done_step).reshape(-1)
+    lps = np.asarray(lps, dtype=np.float32)
+    rule = RANK_BY.index(rule) if isinstance(rule, str) else int(rule)
+    n, steps = int(n), int(steps)
+    R = ids.shape[0]
+    B = R // n
+    ln = np.clip(done, 0, steps).astype(np.int32)
+    score = np.zeros(R, dtype=np.float32)
+    with np.errstate(all='ignore'):
+        for r in range(R):
+            acc = np.float32(0.0)
+            for p in range(int(ln[r])):
+                acc = np.float32(acc + lps[r, p])
+            if inv_norm is not None:
+                acc = np.float32(acc * np.float32(inv_norm[int(ln[r])]))
+            score[r] = acc
+    dup, cons, order = np.zeros(R, dtype=np.uint8), np.zeros(R, dtype=np.float32), np.zeros(R, dtype=np.int32)
+    for b in range(B):
+        toks = [tuple(int(t) for t in ids[b * n + j, 1:1 + int(ln[b * n + j])]) for j in range(n)]
+        big = []
+        for j, t in enumerate(toks):
+            dup[b * n + j] = any(toks[e] == t for e in range(j))
+            g = t[:-1] if t and t[-1] == int(eos) else t
+            big.append(Counter(zip(g, g[1:])))
+        for i in range(n):
+            acc = np.float32(0.0)
+            for j in range(n):
+                if j == i:
+                    continue
+                den = sum(big[i].values()) + sum(big[j].values())
+                inter = sum((big[i] & big[j]).values())
+                acc = np.float32(acc + (np.float32(2 * inter) / np.float32(den) if den else np.float32(0.0)))
+            cons[b * n + i] = np.float32(acc / np.float32(n - 1)) if n > 1 else np.float32(0.0)
+        sc = score[b * n:(b + 1) * n]
+        key = (cons if rule == 2 else score)[b * n:(b + 1) * n].copy()
+        key[np.isnan(key)] = -np.inf
+        dp = dup[b * n:(b + 1) * n]
+
+        def cmp(e, j):                              # < 0: e ranks before j
+            if dp[e] != dp[j]:
+                return -1 if dp[e] < dp[j] else 1
+            if key[e] > key[j] or key[e] < key[j]:
+                return -1 if key[e] > key[j] else 1
+            if rule == 2 and (sc[e] > sc[j] or sc[e] < sc[j]):
+                return -1 if sc[e] > sc[j] else 1
+            return -1 if e < j else 1
+        order[b * n:(b + 1) * n] = list(range(n)) if rule == 0 else sorted(range(n), key=functools.cmp_to_key(cmp))
+    return {k_: v_.reshape(B, n) for k_, v_ in (('len', ln), ('score', score), ('dup', dup), ('cons', cons), ('order', order))}
+
+
 class DecodeInfo(list):
     """Third result of the cached generators without attention maps: the empty list it always was, carrying what
     `generate` reports beside the best hypothesis - scores [B] (beam: the normalised score of hypothesis 0) and, with
-    n_best > 1, nbest = (ids [B, n, L], log_probs [B, n, L - 1], scores [B, n]), best first."""
+    n_best > 1, nbest = (ids [B, n, L], log_probs [B, n, L - 1], scores [B, n]), best first; with n_samples > 1, samples =
+    the '*_samples' / 'sample_index' / 'duplicate' entries of the output dict, in rank order."""
     scores = None
     nbest = None
+    samples = None
 
 
 def nucleus_definition(lp, temp, topp, topk=0, u=None):
@@ -466,6 +545,31 @@ class CaptionModel(Model):
                              'the cached DynamicConv generator only' % type(self).__name__)
         return check_prefix(prefix, batch_size, self.decoder.adaptive_softmax.vocab_size, gen_len, self.padding_idx, eos)
 
+    def _check_n_samples(self, n_samples=1, rank_by='score', rank_len_penalty=0.0, beam_size=1, attention=False,
+                         forward=False):
+        """generate(n_samples=n): check_n_samples, and for n > 1 what it combines with - a sampling
+        decode of the cached DynamicConv generator, one seed per call; no beam search (n_best is the beam's own form), no
+        attention maps, not forward=True, not the arg-max decode, not the LSTM decoders nor the copy models.
+        -> (n, rule, alpha), or None for n = 1."""
+        n, rule, alpha = check_n_samples(n_samples, rank_by, rank_len_penalty)
+        if n == 1:
+            return None
+        if int(beam_size) > 1:
+            raise ValueError('n_samples=%d and beam search (beam_size %d) do not combine: n_best is the beam\'s own form'
+                             % (n, int(beam_size)))
+        if attention:
+            raise ValueError('n_samples=%d and attention=True do not combine: attention maps are exported for one hypothesis '
+                             'per sample' % n)
+        if forward:
+            raise ValueError('n_samples goes with generate, not with forward=True')
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('n_samples=%d: %s has a decode step with its own decision launch (LSTM decoders, copy models); '
+                             'several samples per image cover the cached DynamicConv generator only' % (n, type(self).__name__))
+        if self._sampling() is None:
+            raise ValueError('n_samples=%d needs a sampling model (sampling_topk > 1, sampling_topp, sampling_minp or '
+                             'sampling_typical): the arg-max decode (sampling_topk 1) would give %d identical captions' % (n, n))
+        return n, rule, alpha
+
     def _check_attention(self, beam_size=1):
         """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
         sample (greedy, top-k, nucleus)."""
@@ -490,6 +594,8 @@ class CaptionModel(Model):
             out['scores'] = info.scores if info is not None and info.scores is not None else out['log_probs'].sum(-1)
             if info is not None and info.nbest is not None:
                 out['gen_ids_nbest'], out['log_probs_nbest'], out['scores_nbest'] = info.nbest
+            if info is not None and info.samples is not None:
+                out.update(info.samples)
         return out
 
     def reset_graphs(self):
@@ -725,8 +831,18 @@ class CaptionModel(Model):
         return ' '.join(str(int(i)) for i in ids if int(i) != 2)
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None):
+                 attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
+                 rank_by='score', rank_len_penalty=0.0):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        n_samples = n (2..16; a sampling model): n draws per image from ONE pass of the encoders and ONE
+        cached context - row b * n + j of the decode step is draw j of image b, keyed (seed, b * n + j, step): under the same
+        torch.manual_seed the draws of the batch with every image repeated n times.  Adds 'gen_ids_samples' [B, n, L],
+        'log_probs_samples' [B, n, L - 1], 'scores_samples' [B, n] in rank order, 'sample_index' [B, n] (the draw in every rank
+        slot) and 'duplicate' [B, n] bool (an earlier draw of the image has the same tokens); 'gen_ids' / 'log_probs' /
+        'scores' are the first rank.  rank_by: 'draw' (draw order, duplicates flagged only), 'score' (sum of the recorded
+        log-probs * len ** -rank_len_penalty, best first) or 'consensus' (mean bigram overlap with the other draws); with the
+        last two every duplicate ranks behind every non-duplicate (tell_sample_rank).  A prefix row is shared by the n
+        hypotheses of its image.  n_samples = 1: exactly the call of before.
         prefix (caption completion): int64 [B, P], the tokens every caption starts with after <s>,
         right-padded with padding_idx (`check_prefix`; `encode_prefix` builds it from strings).  Row r's first plen[r] steps take
         the prefix token instead of the model's pick - inside the decode step, every mode of the cached generators - and
@@ -749,11 +865,13 @@ class CaptionModel(Model):
         if attention:
             self._check_attention(beam_size)
         self._check_options(beam_size, attention, n_best)
+        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         # (prefix=None reads nothing of the batch here: the default path is the path of before)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
+                                                   **({'samples': ns} if ns is not None else {}),
                                                    prefix=pfx)
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
@@ -791,14 +909,17 @@ class CaptionModel(Model):
                 and next(self.parameters()).is_cuda)
 
     @torch.no_grad()
-    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1):
+    def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1, n_samples=1,
+                       rank_by='score', rank_len_penalty=0.0):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own DecodeStepper - captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
         chain fits beside the first.  The host alternates the lanes' graph replays (one replay per lane and token).  The
         encoders of a group of batches run first (eval mode: no randomness, results identical to `generate`).
         Yields (batch, output) in order.  forward=True: the outputs of `forward` in evaluate mode (loss + captions + per-sample
-        BLEU bookkeeping: what commands/evaluate.py consumes) instead of `generate`'s; beam_size then is `eval_beam_size`."""
+        BLEU bookkeeping: what commands/evaluate.py consumes) instead of `generate`'s; beam_size then is `eval_beam_size`.
+        n_samples / rank_by / rank_len_penalty: as `generate` - every lane decodes the n hypotheses of its batch's images."""
+        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
         if attention:
             if forward:
                 raise ValueError('attention=True goes with generate, not with forward=True')
@@ -845,7 +966,8 @@ class CaptionModel(Model):
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
                     g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx)
                          if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx))
+                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx,
+                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {})))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -924,7 +1046,7 @@ class CaptionModel(Model):
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
-                  prefix=None):
+                  prefix=None, samples=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
         if self._check_penalties(attention) is not None:      # (the penalties live in the cached generators, like `opts`)
             opts = opts or (0.0, 0, 0)
@@ -946,6 +1068,8 @@ class CaptionModel(Model):
         self._check_beam(beam_size)
         if beam_size > 1:
             return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix)
+        if samples is not None:
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples)
         if self.fast_generation or opts is not None or prefix is not None:  # (the search options live in the cached generator)
             return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
@@ -960,13 +1084,15 @@ class CaptionModel(Model):
             return done.value
 
     @torch.no_grad()
-    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None):
+    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None,
+                         samples=None):
         # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
-                                              **({'prefix': prefix} if prefix is not None else {})))
+                                              **({'prefix': prefix} if prefix is not None else {}),
+                                              **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {})))
 
     def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
-                      prefix=None):
+                      prefix=None, n=1, rank=('score', 0.0)):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -982,9 +1108,16 @@ class CaptionModel(Model):
         and the head of every step ends in one more launch (tell_adaptive_logprob_forced); the bookkeeping is untouched - it
         books a forced token exactly as a picked one.
         With penalties set (_penalties()): the head counts every row's tokens (step.pen_source over `ids`) and picks - arg-max or
-        top-k draw - over the penalised scores, which is what `log_probs` then holds."""
+        top-k draw - over the penalised scores, which is what `log_probs` then holds.
+        n > 1 (a sampling model; generate(n_samples=n)): R = B * n rows are resident, hypothesis j of image b in row b * n + j -
+        cur, ids, lps, done_step and fin8 are R rows tall, the contexts, masks, projected K/V and the prefix stay at width B (as
+        _beam_steps hands them to the stepper), one seed, row r draws with (seed, r, step).  Behind the loop one launch
+        (tell_sample_rank, rank = (rule, alpha)) scores, de-duplicates and ranks the n hypotheses of every image: the results
+        are the first rank's, the third a DecodeInfo with .scores and .samples."""
         dec = self.decoder
-        B = caption_ids.shape[0]
+        n = int(n)
+        images = caption_ids.shape[0]
+        B = images * n                                           # decode rows
         dev = caption_ids.device
         kv = dec.project_contexts(contexts)
         sampling = self._sampling()
@@ -993,12 +1126,13 @@ class CaptionModel(Model):
         ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
         pen = self._check_penalties(attention)
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
-                                    prefix=prefix is not None, **({'pen': pen} if pen is not None else {}))
+                                    prefix=prefix is not None, **({'pen': pen} if pen is not None else {}),
+                                    **({'hyp': n} if n > 1 else {}))
         if prefix is not None:
             step.set_prefix(*prefix)
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
-        cur = caption_ids[:, 0:1].contiguous()
+        cur = caption_ids[:, 0:1].contiguous() if n == 1 else caption_ids[:, 0:1].repeat_interleave(n, dim=0).contiguous()
         finished = cur[:, 0] == eos
         fused = caption_ids.is_cuda and step.static              # one bookkeeping launch per token (tell_greedy_update)
         if fused:
@@ -1053,6 +1187,8 @@ class CaptionModel(Model):
                 break
         steps = int(done_step.max())                                          # one sync at the end
         steps = max(steps, 1)
+        if n > 1:
+            return self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank)
         attns = []
         if attention:
             # slot i of a layer's buffer = step i (the token at ids[:, i + 1]); copied out: the buffers belong to the stepper
@@ -1063,12 +1199,36 @@ class CaptionModel(Model):
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
         return lps[:, :steps], ids[:, :steps + 1], attns
 
+    def _rank_samples(self, ids, lps, done_step, B, n, steps, gen_len, eos, rank):
+        """The end of _greedy_steps with n > 1 hypotheses per image: ids [B * n, gen_len + 1], lps [B * n, gen_len], done_step
+        [B * n] of the decode loop -> (log_probs [B, steps], ids [B, steps + 1] of the first rank, DecodeInfo).  One launch
+        (tell_sample_rank; hypotheses on the CPU: its host definition), then the gathers by its order."""
+        rule, alpha = rank
+        inv_norm = inv_norm_table(alpha, gen_len).to(ids.device) if alpha else None
+        if ids.is_cuda:
+            order, score, dup = ops.sample_rank(ids, lps, done_step, B, n, steps, self.padding_idx, eos, rule, inv_norm=inv_norm)[:3]
+        else:
+            d = sample_rank_definition(ids.numpy(), lps.numpy(), done_step.numpy(), n, steps, eos, rule,
+                                       None if inv_norm is None else inv_norm.numpy())
+            order, score, dup = (torch.from_numpy(d[k_]) for k_ in ('order', 'score', 'dup'))
+        order = order.long()
+
+        def ranked(t):                                            # [B * n, W] -> [B, n, W] in rank order (a new tensor)
+            t = t.reshape(B, n, -1)
+            return t.gather(1, order.unsqueeze(-1).expand(-1, -1, t.shape[-1]))
+        info = DecodeInfo()
+        info.samples = {'gen_ids_samples': ranked(ids[:, :steps + 1]), 'log_probs_samples': ranked(lps[:, :steps]),
+                        'scores_samples': score.gather(1, order), 'sample_index': order,
+                        'duplicate': dup.gather(1, order).bool()}
+        info.scores = info.samples['scores_samples'][:, 0].contiguous()
+        return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
+
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None):
+                        prefix=False, pen=None, hyp=1):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
-                             opts=opts, prefix=prefix, pen=pen)
+                             opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}))
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):

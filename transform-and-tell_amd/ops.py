@@ -2119,3 +2119,32 @@ def entity_logits(x, g, v, b):
     call('tell_entity_logits', x, x.stride(0), x.stride(1), w, b.detach().float().contiguous(), Ba, 1, E, logits,
          hip.dt(x))
     return logits
+
+
+RANK_RULES = {'draw': 0, 'score': 1, 'consensus': 2}
+
+
+def sample_rank(ids, lps, done_step, B, n, steps, pad, eos, rule, inv_norm=None, want_cons=False, want_len=False):
+    """The n sampled hypotheses of every image scored, de-duplicated and ranked (include/tell_hip.h tell_sample_rank): ids int64
+    [B * n, > steps], lps fp32 [B * n, >= steps], done_step int64 [B * n] - the bookkeeping buffers of the greedy generator,
+    hypothesis j of image b in row b * n + j; rule 'draw' / 'score' / 'consensus'; inv_norm fp32 [>= steps + 1] or None.
+    -> (order int32 [B, n], score fp32 [B, n], dup uint8 [B, n], cons fp32 [B, n] or None, len int32 [B, n] or None);
+    cons is computed for rule 'consensus' or want_cons, len with want_len."""
+    rule = RANK_RULES[rule] if isinstance(rule, str) else int(rule)
+    R = int(B) * int(n)
+    if ids.dtype != torch.long or ids.dim() != 2 or ids.shape[0] != R or ids.stride(1) != 1 or ids.shape[1] < steps + 1 or \
+            lps.dtype != torch.float32 or lps.dim() != 2 or lps.shape[0] != R or lps.stride(1) != 1 or lps.shape[1] < steps or \
+            done_step.dtype != torch.long or done_step.numel() != R or not done_step.is_contiguous():
+        raise ValueError('sample_rank: ids int64 [%d, > %d], lps fp32 [%d, >= %d] and done_step int64 [%d] expected'
+                         % (R, steps, R, steps, R))
+    if inv_norm is not None and (inv_norm.dtype != torch.float32 or inv_norm.numel() < steps + 1 or not inv_norm.is_contiguous()):
+        raise ValueError('sample_rank: inv_norm fp32 [>= %d] expected' % (steps + 1))
+    dev = ids.device
+    order = torch.empty(B, n, dtype=torch.int32, device=dev)
+    score = torch.empty(B, n, dtype=torch.float32, device=dev)
+    dup = torch.empty(B, n, dtype=torch.uint8, device=dev)
+    cons = torch.empty(B, n, dtype=torch.float32, device=dev) if (rule == 2 or want_cons) else None
+    length = torch.empty(B, n, dtype=torch.int32, device=dev) if want_len else None
+    call('tell_sample_rank', ids, ids.stride(0), lps, lps.stride(0), done_step, inv_norm, int(B), int(n), int(steps), int(pad),
+         int(eos), rule, order, score, dup, cons, length)
+    return order, score, dup, cons, length
