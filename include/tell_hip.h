@@ -297,6 +297,25 @@ int tell_decode_ban_list(const long* hist, long ld_hist, int L, const uint8_t* f
 int tell_decode_token_counts(const long* hist, long ld_hist, int L, const uint8_t* finished, int rows, int step,
                              const int* step_dev, int* pen_tok, int* pen_cnt, long ld_pen, int* n_pen,
                              tell_stream_t stream);
+/* VOCABULARY MASKS.  A row's mask is a bitmap over the vocabulary, uint32 [words], words = (vocab + 31)
+ * / 32, bit (t & 31) of word t >> 5 set = token t may not be picked.  Under a mask
+ *   - a masked token has score -inf: it is never among the k best and is never drawn;
+ *   - every other log-prob is exactly what the unmasked kernel reports: the log-sum-exps run over the whole row and nothing is
+ *     renormalised;
+ *   - ties: value descending, lower id first;
+ *   - hypothesis row r uses mask row r / per (beam search: per = K; n sampled captions per image: per = n; otherwise 1);
+ *   - the bookkeeping of a finished row and a forced prefix token (tell_adaptive_logprob_forced, which still reports the model's
+ *     own log-prob bit for bit) sit behind the pick and never see the mask.
+ * The mask of image b is  deny[b] | (cls & ~present[b])  with the eos bit always cleared: present[b] is the set of ids in the
+ * row's article ctx[b][0 .. S) (ids equal to `pad`, negative ids and ids >= vocab are ignored), cls the grounded class (tokens
+ * of the class may be generated only if they occur in the article), deny the caller's banned set.
+ * tell_decode_vocab_mask builds it, one workgroup per image: ctx int64 [rows, S] with leading dimension ld_ctx; cls_bits uint32
+ * [words] or NULL (no class); deny8 uint8 [1 or rows, vocab] (non-zero = banned; ld_deny = 0: one row shared by all, else the
+ * leading dimension) or NULL; mask uint32 [rows, ld_mask >= words].  Bits past `vocab` in the last word are written as 0,
+ * nothing is written behind `words`.  vocab <= 2^18. */
+int tell_decode_vocab_mask(const long* ctx, long ld_ctx, int S, int rows, int vocab, const uint32_t* cls_bits,
+                           const uint8_t* deny8, long ld_deny, int eos, int pad, uint32_t* mask, long ld_mask,
+                           tell_stream_t stream);
 /* buf[i][p][r][:] <- buf[i][p][rows[r]][:] in place for n <= 8 bf16 buffers [planes[i], M, 1024] (HOST arrays); rows[r]
  * must lie inside r's group of K consecutive rows (dynamic.py:338-342 reorder_incremental_state, all layers at once) - for
  * input buffers kept in time order (the layer-by-layer fp32 step); the rings of tell_dynconv_step are never moved. */
@@ -589,6 +608,16 @@ int tell_adaptive_logprob_topk_penalised(const float* head, long ld_head, int c0
                                          int rows, int k, const int* pen_tok, const int* pen_cnt, long ld_pen,
                                          const int* n_pen, float theta, const float* sub, int n_sub, int* tokens, float* lps,
                                          tell_stream_t stream);
+/* tell_adaptive_logprob_topk under a VOCABULARY MASK (definition at tell_decode_vocab_mask): mask uint32 [rows / per, ld_mask >=
+ * words], row r reads mask row r / per (rows % per == 0 is required); bits past the vocabulary are ignored.  ban / ld_ban / n_ban
+ * as tell_adaptive_logprob_topk_banned, ORed into the row's mask (ban == NULL or n_ban == NULL: no list), so
+ * no_repeat_ngram_size / min_len combine with a mask in one launch.  An all-zero mask without a list is
+ * tell_adaptive_logprob_topk bit for bit.  A row with fewer than k allowed tokens ends in (-inf, 0x7fffffff) entries.
+ * k = 1..8; vocab <= 2^18; register and streaming forms as tell_adaptive_logprob_topk (option argmax_regs). */
+int tell_adaptive_logprob_topk_masked(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                      int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                      int rows, int k, const uint32_t* mask, long ld_mask, int per, const int* ban,
+                                      long ld_ban, const int* n_ban, int* tokens, float* lps, tell_stream_t stream);
 int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,
@@ -640,6 +669,15 @@ int tell_adaptive_logprob_sample_penalised(const float* head, long ld_head, int 
                                            const int* row_ids, int step, const int* step_dev, const int* pen_tok,
                                            const int* pen_cnt, long ld_pen, const int* n_pen, float theta, const float* sub,
                                            int n_sub, int* tokens, float* lps, tell_stream_t stream);
+/* tell_adaptive_logprob_sample under a VOCABULARY MASK (mask, ld_mask, per as tell_adaptive_logprob_topk_masked; launch row r
+ * reads mask row r / per whatever row_ids says): the candidates are the k (1..64) best tokens that are not masked, the draw and
+ * the reported log-prob as above.  Every row must keep at least k allowed tokens (the host guarantees 64).  k = 1 is the masked
+ * arg-max bit for bit.  vocab <= 2^18. */
+int tell_adaptive_logprob_sample_masked(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                        int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                        int rows, int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids,
+                                        int step, const int* step_dev, const uint32_t* mask, long ld_mask, int per,
+                                        int* tokens, float* lps, tell_stream_t stream);
 /* steps 2-5 above on given candidates: cand_tokens int32 / cand_lps fp32 [rows, k], each row sorted best first */
 int tell_sample_candidates(const int* cand_tokens, const float* cand_lps, int rows, int k, float inv_temp,
                            const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev, int* tokens,

@@ -426,8 +426,8 @@ struct NoPen {};
 __device__ __forceinline__ NoPen pen_pick() { return NoPen{}; }
 __device__ __forceinline__ const PenArgs& pen_pick(const PenArgs& a) { return a; }
 // the trailing argument of the top-k kernels: the ban list, or with PEN the penalty list
-template <bool PEN> struct ListOf { typedef BanArgs type; };
-template <> struct ListOf<true> { typedef PenArgs type; };
+template <bool PEN, bool MSK = false> struct ListOf { typedef BanArgs type; };
+template <> struct ListOf<true, false> { typedef PenArgs type; };
 #define PEN_MAX_LIST 256
 __device__ __forceinline__ int pen_count(const PenArgs& pa, int row) {
   const int np = pa.n_pen[row];
@@ -471,11 +471,34 @@ __device__ __forceinline__ float pen_score(const PenArgs& pa, int np, int j, flo
 }
 __device__ __forceinline__ float pen_score(const NoPen&, int, int, float lp) { return lp; }
 __device__ __forceinline__ float pen_score(const BanArgs&, int, int, float lp) { return lp; }
+// MSK (tell_adaptive_logprob_topk_masked / _sample_masked, include/tell_hip.h): the BAN bitmap from memory - the workgroup copies
+// row `i / per` of `mask` (uint32 [rows / per, ld_mask], tell_decode_vocab_mask) into ban_bits instead of zeroing it, then ORs
+// the row's optional ban list in (ban == NULL or n_ban == NULL: none).  A token whose bit is set never enters a candidate list
+// (top-k) or gets the key of an element outside the row (the sampler); every other log-prob is the whole row's.
+struct MaskArgs { const unsigned* mask; long ld_mask; int per; const int* ban; long ld_ban; const int* n_ban; int vocab; };
+__device__ __forceinline__ const MaskArgs& pen_pick(const MaskArgs& a) { return a; }
+template <> struct ListOf<false, true> { typedef MaskArgs type; };
+template <class... P> struct IsMask { static constexpr bool value = false; };
+template <> struct IsMask<MaskArgs> { static constexpr bool value = true; };
+template <int THREADS>
+__device__ __forceinline__ void mask_stage(const MaskArgs& ma, int row) {
+  const int words = (ma.vocab + 31) >> 5;
+  const unsigned* m = ma.mask + (long)(row / ma.per) * ma.ld_mask;
+  int nb = 0;                                          // (uniform over the workgroup)
+  if (ma.ban && ma.n_ban) { nb = ma.n_ban[row]; nb = nb < 0 ? 0 : (nb > (int)ma.ld_ban ? (int)ma.ld_ban : nb); }
+  for (int w = threadIdx.x; w < words; w += THREADS) ban_bits[w] = m[w];
+  __syncthreads();
+  for (int e = threadIdx.x; e < nb; e += THREADS) {
+    const int t = ma.ban[(long)row * ma.ld_ban + e];
+    if (t >= 0 && t < ma.vocab) atomicOr(&ban_bits[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+}
 // (the register-resident kernel takes `ba` as a trailing argument that BAN = false never reads: its code stays the kernel's
 //  own, not an inlined body - this is the launch every greedy and beam step ends with)
-template <int K, bool BAN, bool PEN = false>
+template <int K, bool BAN, bool PEN = false, bool MSK = false>
 __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
-                                                            float* __restrict__ lps, typename ListOf<PEN>::type ba) {
+                                                            float* __restrict__ lps, typename ListOf<PEN, MSK>::type ba) {
   __shared__ float red[4][16];
   __shared__ float best_v[16];
   __shared__ int best_i[16];
@@ -510,6 +533,7 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
     }
   if constexpr (BAN) { if (nb > 0) ban_stage<1024>(ba, i, nb); }   // (nb is uniform over the workgroup)
   if constexpr (PEN) { if (nb > 0) pen_stage<1024>(ba, i, nb); }
+  if constexpr (MSK) mask_stage<1024>(ba, i);
   float mx[4], sm[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -560,6 +584,7 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
   auto consider = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
     if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
+    if constexpr (MSK) { if (pen_bit(j)) return; }
     if constexpr (PEN) {
       if (nb > 0 && pen_bit(j)) {
         v = pen_score(ba, nb, j, v);
@@ -634,9 +659,9 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
 // Top-k variant for beam search: per row the k best (log-prob, token) pairs of the adaptive softmax, sorted best
 // first, without materialising [rows, vocab] (a beam of k only ever needs each hypothesis' own k best tokens).
 // Every thread keeps its k best in registers while streaming the row; the block then pops the global best k times.
-template <int K, bool BAN, bool PEN = false>
+template <int K, bool BAN, bool PEN = false, bool MSK = false>
 __device__ __forceinline__ void logprob_topk_body(const LogProbArgs& p, int k, int* __restrict__ tokens,
-                                                  float* __restrict__ lps, const typename ListOf<PEN>::type& ba) {
+                                                  float* __restrict__ lps, const typename ListOf<PEN, MSK>::type& ba) {
   __shared__ float red[4];
   __shared__ float best_v[4];
   __shared__ int best_i[4];
@@ -656,9 +681,11 @@ __device__ __forceinline__ void logprob_topk_body(const LogProbArgs& p, int k, i
     nb = pen_count(ba, i);
     if (nb > 0) pen_stage<256>(ba, i, nb);
   }
+  if constexpr (MSK) mask_stage<256>(ba, i);
   auto push = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
     if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
+    if constexpr (MSK) { if (pen_bit(j)) return; }
     if constexpr (PEN) {
       if (nb > 0 && pen_bit(j)) {
         v = pen_score(ba, nb, j, v);
@@ -734,6 +761,11 @@ template <int K>
 __global__ __launch_bounds__(256) void logprob_topk_penalised_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
                                                                      float* __restrict__ lps, PenArgs pa) {
   logprob_topk_body<K, false, true>(p, k, tokens, lps, pa);
+}
+template <int K>
+__global__ __launch_bounds__(256) void logprob_topk_masked_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
+                                                                  float* __restrict__ lps, MaskArgs ma) {
+  logprob_topk_body<K, false, false, true>(p, k, tokens, lps, ma);
 }
 extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c0, int n_tails,
                                           const float* tail0, long ld0, int n0, const float* tail1, long ld1,
@@ -851,6 +883,53 @@ extern "C" int tell_adaptive_logprob_topk_penalised(const float* head, long ld_h
   if (k <= 4) hipLaunchKernelGGL((logprob_topk_penalised_kernel<4>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, pa);
   else hipLaunchKernelGGL((logprob_topk_penalised_kernel<8>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, pa);
   return tell_check_launch("logprob_topk_penalised");
+}
+
+// tell_adaptive_logprob_topk under a vocabulary mask (include/tell_hip.h): mask uint32 [rows / per, ld_mask >= words], row r
+// reads mask row r / per; ban / n_ban as tell_adaptive_logprob_topk_banned or NULL.
+static int mask_args(MaskArgs& ma, int c0, int n_tails, int n0, int n1, int n2, int rows, const uint32_t* mask, long ld_mask,
+                     int per, const int* ban, long ld_ban, const int* n_ban) {
+  ma.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  TELL_REQUIRE(ma.vocab > 0 && ma.vocab <= (1 << 18), "logprob masked: vocab <= 2^18 (the bitmap: 32 KB of LDS)");
+  TELL_REQUIRE(mask && ld_mask >= (ma.vocab + 31) / 32, "logprob masked: mask uint32 [rows / per, ld_mask >= words]");
+  TELL_REQUIRE(per >= 1 && rows % per == 0, "logprob masked: rows must be a multiple of per >= 1");
+  TELL_REQUIRE(!ban || ld_ban >= 1, "logprob masked: ban [rows, ld_ban >= 1]");
+  ma.mask = mask; ma.ld_mask = ld_mask; ma.per = per; ma.ban = ban; ma.ld_ban = ld_ban; ma.n_ban = n_ban;
+  return TELL_OK;
+}
+extern "C" int tell_adaptive_logprob_topk_masked(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
+                                                 long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
+                                                 long ld2, int n2, int rows, int k, const uint32_t* mask, long ld_mask, int per,
+                                                 const int* ban, long ld_ban, const int* n_ban, int* tokens, float* lps,
+                                                 hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk_masked: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_masked: 1 <= k <= 8");
+  TELL_REQUIRE(tokens && lps, "logprob_topk_masked: tokens and lps [rows, k]");
+  MaskArgs ma;
+  const int rc = mask_args(ma, c0, n_tails, n0, n1, n2, rows, mask, ld_mask, per, ban, ld_ban, n_ban);
+  if (rc != TELL_OK) return rc;
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  const size_t lds = (size_t)((ma.vocab + 31) >> 5) * sizeof(unsigned);
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ma);
+    else hipLaunchKernelGGL((logprob_regs_kernel<8, false, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ma);
+    return tell_check_launch("logprob_topk_masked (registers)");
+  }
+  if (k <= 4) hipLaunchKernelGGL((logprob_topk_masked_kernel<4>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ma);
+  else hipLaunchKernelGGL((logprob_topk_masked_kernel<8>), dim3(rows), dim3(256), lds, stream, p, k, tokens, lps, ma);
+  return tell_check_launch("logprob_topk_masked");
 }
 
 extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails,
@@ -1281,6 +1360,10 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
     np = pen_count(pa, i);
     if (np > 0) pen_stage<1024>(pa, i, np);              // (np is uniform over the workgroup)
   }
+  // MSK (tell_adaptive_logprob_sample_masked): the mask row is staged like the top-k kernels' (mask_stage) and a masked token's
+  // key becomes 0, the key of an element outside the row, where the keys are formed (in: the element is a token of the row)
+  constexpr bool MSK = IsMask<P...>::value;
+  if constexpr (MSK) mask_stage<1024>(pa, i);
   // a listed token's log-prob -> its score (in: the element is a token of the row)
   auto pen = [&](float l, int idx, bool in) {
     if constexpr (PEN) {
@@ -1356,8 +1439,27 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
       key[e0 + 1] = j + 1 < lim[s] ? lp_key(pen(l1, base[s] + j + 1, j + 1 < lim[s])) : 0u;
       key[e0 + 2] = j + 2 < lim[s] ? lp_key(pen(l2, base[s] + j + 2, j + 2 < lim[s])) : 0u;
       key[e0 + 3] = j + 3 < lim[s] ? lp_key(pen(l3, base[s] + j + 3, j + 3 < lim[s])) : 0u;
-      tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
+      if constexpr (!MSK) tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
     }
+  if constexpr (MSK) {                                        // (a pass of its own: the logits are dead by now)
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[s]; ++q) {
+        const int j = (q * 1024 + tid) * 4, e0 = (LPF_OFF[s] + q) * 4;
+        if (j < lim[s]) {                                     // (4 consecutive ids: at most two words of the bitmap)
+          const int t0 = base[s] + j;
+          const unsigned w0 = ban_bits[t0 >> 5], w1 = ban_bits[min(t0 + 3, pa.vocab - 1) >> 5];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int t = t0 + e;
+            const unsigned w = (t >> 5) == (t0 >> 5) ? w0 : w1;
+            if (j + e < lim[s] && ((w >> (t & 31)) & 1u)) key[e0 + e] = 0u;
+          }
+        }
+        tmax = max(tmax, max(max(key[e0], key[e0 + 1]), max(key[e0 + 2], key[e0 + 3])));
+      }
+  }
   auto each = [&](auto f) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -1371,7 +1473,14 @@ __global__ __launch_bounds__(1024) void logprob_sample_regs_kernel(LogProbArgs p
     for (int s = 1; s < nseg; ++s)
       for (int j = tid; j < n[s]; j += 1024) f(lp_key(pen(rowp[s][j] + off[s], base[s] + j, true)), base[s] + j);
   };
-  sample_row<NUC>(each, each_mem, tmax, i, a, sm);
+  if constexpr (MSK) {                                        // (the tie pass over memory: the same keys, masked alike)
+    auto each_mem_masked = [&](auto f) {
+      each_mem([&](uint32_t key_, int idx) { f(pen_bit(idx) ? 0u : key_, idx); });
+    };
+    sample_row<NUC>(each, each_mem_masked, tmax, i, a, sm);
+  } else {
+    sample_row<NUC>(each, each_mem, tmax, i, a, sm);
+  }
 }
 // Any row: the log-probs with the arithmetic of logprob_argmax_kernel (the three-pass form; its full-row output is what the
 // tests take top-k of), read from memory in every pass of the select.
@@ -1405,7 +1514,22 @@ __global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs
     s2 = block_sum(s2, red);
     off[c] = (hrow[p.c0 + c] - lse_h) - (m2 + __logf(s2));
   }
-  if constexpr (!PEN) {                                       // (the unpenalised kernel: the code it always was)
+  if constexpr (IsMask<P...>::value) {                        // masked: a set bit -> the key of an element outside the row
+    mask_stage<1024>(pa, i);
+    auto msk = [&](uint32_t key, int idx) { return pen_bit(idx) ? 0u : key; };
+    auto each = [&](auto f) {
+      for (int j = tid; j < p.c0; j += 1024) f(msk(lp_key(hrow[j] - lse_h), j), j);
+      int base = p.c0;
+      for (int c = 0; c < p.n_tails; ++c) {
+        const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+        for (int j = tid; j < p.tail_n[c]; j += 1024) f(msk(lp_key(trow[j] + off[c]), base + j), base + j);
+        base += p.tail_n[c];
+      }
+    };
+    uint32_t tmax = 0;
+    each([&](uint32_t key, int) { tmax = max(tmax, key); });
+    sample_row<NUC>(each, each, tmax, i, a, sm);
+  } else if constexpr (!PEN) {                                // (the unpenalised kernel: the code it always was)
     auto each = [&](auto f) {
       for (int j = tid; j < p.c0; j += 1024) f(lp_key(hrow[j] - lse_h), j);
       int base = p.c0;
@@ -1509,6 +1633,46 @@ extern "C" int tell_adaptive_logprob_sample_penalised(const float* head, long ld
   }
   hipLaunchKernelGGL((logprob_sample_stream_kernel<false, true>), dim3(rows), dim3(1024), lds, stream, p, a, pa);
   return tell_check_launch("logprob_sample_penalised");
+}
+
+// tell_adaptive_logprob_sample under a vocabulary mask (include/tell_hip.h): the arguments of tell_adaptive_logprob_sample plus
+// the mask of tell_adaptive_logprob_topk_masked (no ban list).
+extern "C" int tell_adaptive_logprob_sample_masked(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
+                                                   long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
+                                                   long ld2, int n2, int rows, int k, float inv_temp, const uint32_t* seed_dev,
+                                                   const int* row_ids, int step, const int* step_dev, const uint32_t* mask,
+                                                   long ld_mask, int per, int* tokens, float* lps, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_sample_masked: up to 3 tails");
+  TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample_masked: 1 <= k <= 64");
+  TELL_REQUIRE(inv_temp > 0.f, "logprob_sample_masked: inv_temp > 0");
+  TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample_masked: seed_dev, tokens and lps are required");
+  MaskArgs ma;
+  const int rc = mask_args(ma, c0, n_tails, n0, n1, n2, rows, mask, ld_mask, per, nullptr, 0, nullptr);
+  if (rc != TELL_OK) return rc;
+  TELL_REQUIRE(ma.vocab >= k, "logprob_sample_masked: k <= vocab");
+  if (rows <= 0) return TELL_OK;
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  SampleArgs a;
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr; a.typ_c = nullptr;
+  const size_t lds = (size_t)((ma.vocab + 31) >> 5) * sizeof(unsigned);
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    hipLaunchKernelGGL((logprob_sample_regs_kernel<false, false>), dim3(rows), dim3(1024), lds, stream, p, a, ma);
+    return tell_check_launch("logprob_sample_masked (registers)");
+  }
+  hipLaunchKernelGGL((logprob_sample_stream_kernel<false, false>), dim3(rows), dim3(1024), lds, stream, p, a, ma);
+  return tell_check_launch("logprob_sample_masked");
 }
 
 // steps 2-5 of the sampling semantics on given candidates (sorted best first): one thread per row

@@ -1929,6 +1929,55 @@ extern "C" int tell_decode_token_counts(const long* hist, long ld_hist, int L, c
   return tell_check_launch("decode_token_counts");
 }
 
+// ------------------------------------------------------------------ vocabulary masks: the bitmap of every image
+// mask[b] = deny[b] | (cls & ~present[b]) with the eos bit and the bits past `vocab` cleared (include/tell_hip.h).  One workgroup
+// per image: present[b], the set of ids in the row's article, is built in LDS - cleared, then one LDS atomic per article token -
+// and combined word by word: a wave reads 64 deny bytes, one per lane, and its ballot is two words of the deny bitmap.
+__global__ __launch_bounds__(256) void decode_vocab_mask_kernel(const long* __restrict__ ctx, long ld_ctx, int S, int vocab,
+                                                                const uint32_t* __restrict__ cls_bits,
+                                                                const uint8_t* __restrict__ deny8, long ld_deny, int eos, int pad,
+                                                                uint32_t* __restrict__ mask, long ld_mask) {
+  extern __shared__ unsigned present[];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int words = (vocab + 31) >> 5;
+  for (int w = tid; w < words; w += 256) present[w] = 0u;
+  __syncthreads();
+  for (int s = tid; s < S; s += 256) {
+    const long t = ctx[(long)b * ld_ctx + s];
+    if (t >= 0 && t < vocab && t != pad) atomicOr(&present[(int)t >> 5], 1u << ((int)t & 31));
+  }
+  __syncthreads();
+  const uint8_t* d = deny8 ? deny8 + (long)b * ld_deny : nullptr;
+  uint32_t* out = mask + (long)b * ld_mask;
+  for (int j0 = wave * 64; j0 < words * 32; j0 += 256) {   // (uniform over the wave: the ballot sees all 64 lanes)
+    const int j = j0 + lane;
+    const bool denied = d != nullptr && j < vocab && d[j] != 0;
+    const unsigned long long bal = __ballot(denied);
+    const int w = (j0 >> 5) + lane;
+    if (lane < 2 && w < words) {
+      unsigned m = lane == 0 ? (unsigned)bal : (unsigned)(bal >> 32);
+      if (cls_bits) m |= cls_bits[w] & ~present[w];
+      if (w == words - 1 && (vocab & 31)) m &= (1u << (vocab & 31)) - 1u;
+      if (eos >= 0 && eos < vocab && (eos >> 5) == w) m &= ~(1u << (eos & 31));
+      out[w] = m;
+    }
+  }
+}
+// ctx int64 [rows, S] with leading dimension ld_ctx; cls_bits uint32 [words] or NULL; deny8 uint8 [1 or rows, vocab] or NULL
+// (ld_deny = 0: one shared row); mask uint32 [rows, ld_mask >= words], words = (vocab + 31) / 32.
+extern "C" int tell_decode_vocab_mask(const long* ctx, long ld_ctx, int S, int rows, int vocab, const uint32_t* cls_bits,
+                                      const uint8_t* deny8, long ld_deny, int eos, int pad, uint32_t* mask, long ld_mask,
+                                      hipStream_t stream) {
+  TELL_REQUIRE(vocab > 0 && vocab <= (1 << 18), "decode_vocab_mask: vocab <= 2^18 (the bitmap: 32 KB of LDS)");
+  TELL_REQUIRE(rows > 0 && S >= 0 && (S == 0 || (ctx && ld_ctx >= S)), "decode_vocab_mask: ctx int64 [rows, S], ld_ctx >= S");
+  TELL_REQUIRE(mask && ld_mask >= (vocab + 31) / 32, "decode_vocab_mask: mask uint32 [rows, ld_mask >= words]");
+  TELL_REQUIRE(!deny8 || ld_deny == 0 || ld_deny >= vocab, "decode_vocab_mask: deny8 uint8 [1 or rows, vocab] (ld_deny = 0: shared)");
+  const size_t lds = (size_t)((vocab + 31) >> 5) * sizeof(unsigned);
+  hipLaunchKernelGGL(decode_vocab_mask_kernel, dim3(rows), dim3(256), lds, stream, ctx, ld_ctx, S, vocab, cls_bits, deny8,
+                     ld_deny, eos, pad, mask, ld_mask);
+  return tell_check_launch("decode_vocab_mask");
+}
+
 // Rows of the DynamicConv input buffers follow their hypotheses (dynamic.py:338-342 reorder_incremental_state):
 // buf[p][r][:] <- buf[p][rows[r]][:] for every plane p of up to 8 buffers [planes, M, C] bf16, in place - rows[r] stays
 // inside r's group of K consecutive rows (a sample's hypotheses), so a workgroup that owns (plane, group) reads its K

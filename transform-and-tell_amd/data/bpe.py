@@ -144,3 +144,26 @@ class RobertaBPE:
             if sym.isdigit():
                 out.append(int(sym))
         return self.bpe.decode(out)
+
+
+def capitalised_tokens(bpe, dictionary=None):
+    """The grounded class of generate(ground=True): bool [len(dictionary)], True for the dictionary
+    entries whose BPE piece, after an optional leading-space marker, starts with an uppercase letter ('ĠParis', 'Paris').
+    The four specials, entries that are no BPE id ('madeupword0000') and ids the encoder does not know are never in it.
+    The class is PER TOKEN, not per word: a name's continuation pieces ('aris' of 'P' + 'aris') are lower-case pieces, stay
+    outside it and are unconstrained.  bpe: a RobertaBPE, or a ByteBPE with its FairseqDictionary as `dictionary`."""
+    import torch
+    if dictionary is None:
+        bpe, dictionary = bpe.bpe, bpe.source_dictionary
+    out = torch.zeros(len(dictionary), dtype=torch.bool)
+    for i, sym in enumerate(dictionary.symbols):
+        if i < 4 or not sym.isdigit() or int(sym) not in bpe.decoder:
+            continue
+        piece = bpe.decoder[int(sym)]
+        if not all(c in bpe.byte_decoder for c in piece):
+            continue
+        text = bytearray(bpe.byte_decoder[c] for c in piece).decode('utf-8', errors='ignore')
+        if text.startswith(' '):
+            text = text[1:]
+        out[i] = bool(text[:1].isupper())
+    return out

@@ -208,7 +208,7 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None, mask=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
@@ -217,7 +217,11 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     the top-k draw instead of the arg-max (ops.logprob_sample); ban = (ban, n_ban) with topk: the last launch is
     tell_adaptive_logprob_topk_banned (ops.logprob_topk); force (caption completion): one more launch behind that pick,
     tell_adaptive_logprob_forced over the same logits (ops.logprob_forced) - without it the launches are what they were.
-    pen (ops._pen_args; with topk or sample): the last launch is tell_adaptive_logprob_topk_penalised / _sample_penalised."""
+    pen (ops._pen_args; with topk or sample): the last launch is tell_adaptive_logprob_topk_penalised / _sample_penalised.
+    mask (ops._mask_args; with topk - a ban list may join it - or a top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked."""
+    if mask is not None and ((not topk and sample is None) or pen is not None):
+        raise ValueError('head_step: a vocabulary mask goes with topk = k >= 1 or a top-k draw, without penalties')
+    mk = {'mask': mask} if mask is not None else {}
     if pen is not None and not topk and sample is None:
         raise ValueError('head_step: penalties go with topk = k >= 1 or a top-k draw')
     if ban is not None and (not topk or sample is not None):
@@ -266,9 +270,9 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         def forced(picked):
             return picked if force is None else ops.logprob_forced(logits, LD, c0, n_tails, tl, lds, ns, N, picked, force)
         if sample is not None:
-            return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample, pen=pen))
+            return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
         if topk:
-            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen))
+            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk))
         token = torch.empty(N, dtype=torch.int32, device=dev)
         token_lp = torch.empty(N, dtype=torch.float32, device=dev)
         call('tell_adaptive_logprob_argmax', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
@@ -308,9 +312,9 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     def forced(picked):
         return picked if force is None else ops.logprob_forced(head, ld, c0, n_tails, tl, lds, ns, N, picked, force)
     if sample is not None:
-        return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample, pen=pen))
+        return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
     if topk:
-        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen))
+        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk))
     token = torch.empty(N, dtype=torch.int32, device=dev)
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
     call('tell_adaptive_logprob_argmax', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],

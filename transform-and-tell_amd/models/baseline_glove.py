@@ -9,8 +9,19 @@ import math
 import torch
 
 from .. import ops
-from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_penalties, check_sampling, draw_seed,
-                          set_sampling)
+from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_mask_keys, check_penalties,
+                          check_sampling, draw_seed, set_sampling)
+
+
+def _refuse_mask_options(model, suppress_tokens=(), ground_names=False, banned=None, ground=None):
+    """BaselineGloveModel decodes with an LSTM decoder: the vocabulary masks are out of scope there."""
+    st, gn = check_mask_keys(suppress_tokens, ground_names)
+    used = [n for n, on in (('banned', banned is not None), ('ground', ground is not None and ground is not False),
+                            ('suppress_tokens', bool(st)), ('ground_names', gn)) if on]
+    if used:
+        raise ValueError('%s: %s decodes with an LSTM decoder, whose step has its own decision launch; vocabulary masks cover '
+                         'the cached DynamicConv generator only' % (' / '.join(used), type(model).__name__))
+    return st, gn
 
 
 def _refuse_search_options(model, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, n_best=1):
@@ -33,9 +44,10 @@ class BaselineGloveModel(Model):
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
                  weigh_bert=False, initializer=None, resnet=None, sampling_topp=None, beam_len_penalty=0.0,
                  no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None, repetition_penalty=1.0,
-                 presence_penalty=0.0, frequency_penalty=0.0):
+                 presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False):
         super().__init__(vocab)
         _refuse_search_options(self, beam_len_penalty, no_repeat_ngram_size, min_len)
+        self.suppress_tokens, self.ground_names = _refuse_mask_options(self, suppress_tokens, ground_names)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if pen != (1.0, 0.0, 0.0):
             raise ValueError('%s: %s decodes with an LSTM decoder; the penalties cover the cached DynamicConv generator only'
@@ -107,8 +119,9 @@ class BaselineGloveModel(Model):
         return out
 
     def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None,
-                 n_samples=1, rank_by='score', rank_len_penalty=0.0):
+                 n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
         _refuse_search_options(self, n_best=n_best)
+        _refuse_mask_options(self, banned=banned, ground=ground)
         from .transformer import check_n_samples
         if check_n_samples(n_samples, rank_by, rank_len_penalty)[0] > 1:
             raise ValueError('n_samples=%d: %s decodes with an LSTM decoder, whose step has its own decision launch; several '
@@ -190,7 +203,7 @@ class TransformerGloveModel(CaptionModel):
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
                  use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -207,11 +220,26 @@ class TransformerGloveModel(CaptionModel):
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = check_penalties(
             repetition_penalty, presence_penalty, frequency_penalty)
         self._check_penalties()
+        self.suppress_tokens, self.ground_names = check_mask_keys(suppress_tokens, ground_names)
+        self._check_mask_options()
+        self._check_grounding()
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0
 
     EVAL_ATTENTION = False       # its own forward(): evaluate mode generates without maps (no article pieces to merge either)
+
+    def _check_grounding(self, ground=None):
+        """The article of this model is a matrix of GloVe vectors: its batches carry no article token ids, so there is nothing
+        to ground a class in - `banned` and `suppress_tokens` apply, `ground` / `ground_names` are refused."""
+        if (ground is not None and ground is not False) or getattr(self, 'ground_names', False):
+            raise ValueError('%s: %s reads GloVe article vectors; its batches hold no article token ids to ground a class in'
+                             % ('ground' if ground is not None and ground is not False else 'ground_names', type(self).__name__))
+
+    def _glove_mask(self, caption, banned=None, attention=False):
+        """_vocab_mask for a batch without article ids: the banned set alone (an empty article)."""
+        ids = caption[self.index]
+        return self._vocab_mask({self.index: ids.new_zeros(ids.shape[0], 0)}, banned, None, attention)
     _vectors = staticmethod(BaselineGloveModel._vectors)
     _glove_forward = BaselineGloveModel._forward
 
@@ -225,16 +253,19 @@ class TransformerGloveModel(CaptionModel):
         loss = (loss_sum / math.log(2) / sample_size.to(torch.float32)).reshape(())
         out = {'loss': loss, 'sample_size': sample_size.reshape(())}
         if not self.training and self.evaluate_mode:
-            _, gen_ids, _ = self._generate(caption_ids, contexts)
+            vm = self._glove_mask(caption)
+            _, gen_ids, _ = self._generate(caption_ids, contexts, **({'vmask': vm} if vm is not None else {}))
             out['gen_ids'] = gen_ids.cpu().numpy()
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
         return out
 
     def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1,
-                 prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0):
+                 prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
         if attention:
             self._check_attention(beam_size)
+        self._check_grounding(ground)
+        vm = self._glove_mask(caption, banned, attention)
         self._check_options(beam_size, attention, n_best)
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
@@ -243,7 +274,8 @@ class TransformerGloveModel(CaptionModel):
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
                                                    **({'prefix': pfx} if pfx is not None else {}),
-                                                   **({'samples': ns} if ns is not None else {}))
+                                                   **({'samples': ns} if ns is not None else {}),
+                                                   **({'vmask': vm} if vm is not None else {}))
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
             out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)

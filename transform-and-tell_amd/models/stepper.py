@@ -65,10 +65,17 @@ class DecodeStepper:
     hyp = n > 1 (generate(n_samples=n); without topk): the B rows are n sampled hypotheses of each of
     B / n samples, row = sample * n + j, over contexts and K/V of width B / n - what beam search hands in with topk = K, but no
     row ever moves: the DynamicConv rings get no ancestor table, the forcing table has B / n rows (beams = n in the forced
-    launch).  ('hyp', n) joins the signature only then."""
+    launch).  ('hyp', n) joins the signature only then.
+
+    mask=True (vocabulary masks): the stepper owns one bitmap per sample - int32 [B / per_sample, words],
+    static in the cache entry (h['vmask']), filled per caption batch by step.set_mask(ctx_ids, cls_bits, deny8, eos)
+    (tell_decode_vocab_mask, outside the captured step) - and the head's pick becomes the masked one:
+    tell_adaptive_logprob_topk_masked (k = 1 for the greedy decode; with `ban`, behind tell_decode_ban_list and with its list) or,
+    with sample = (k, T), tell_adaptive_logprob_sample_masked.  ('mask',) joins the signature only when set; it does not combine
+    with `pen`, with attention maps or with a truncation rule."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False, pen=None, hyp=1):
+                 prefix=False, pen=None, hyp=1, mask=False):
         if int(hyp) > 1 and (topk or attention or sample is None or B % int(hyp)):
             raise ValueError('hyp = %d hypotheses per sample: a sampling step without beam search or attention maps, over a '
                              'multiple of %d rows' % (int(hyp), int(hyp)))
@@ -77,6 +84,11 @@ class DecodeStepper:
         if pen is not None and (ban is not None or attention or (sample is not None and len(sample) != 2)):
             raise ValueError('repetition_penalty / presence_penalty / frequency_penalty do not combine with no_repeat_ngram_size '
                              '/ min_len, attention maps or sampling_topp / sampling_minp / sampling_typical')
+        if mask and (pen is not None or attention or (sample is not None and len(sample) != 2)):
+            raise ValueError('banned / ground / suppress_tokens / ground_names (a vocabulary mask) do not combine with '
+                             'repetition_penalty / presence_penalty / frequency_penalty, attention maps or sampling_topp / '
+                             'sampling_minp / sampling_typical')
+        self.mask, self.vmask = bool(mask), None
         self.pen = None if pen is None else (float(pen[0]), float(pen[1]), float(pen[2]))
         dec = self.dec = model.decoder
         self.index, self.pad = model.index, int(model.padding_idx)
@@ -101,6 +113,7 @@ class DecodeStepper:
         # (the captured launches hold these buffers' addresses: from the entry, never freshly allocated)
         self.pfx, self.ban_src, self.attn = h.get('pfx', {}), h['ban_src'], h.get('attn')
         self.pen_src = h.setdefault('pen_src', {}) if self.pen is not None else {}
+        self.vmask = h.get('vmask')
         self.seed, self.cur = h['seed'], h['cur']
         self.c_cur, self.c_next = h['counter'][0:1], h['counter'][1:2]
         # where a bookkeeping launch leaves the next step's offset: the word the embedder's kernel reads (in-graph
@@ -112,6 +125,10 @@ class DecodeStepper:
     def _make_prefix(self, device):
         return {'tab': torch.full((self.B // self.per_sample, self.gen_len), self.pad, dtype=torch.long, device=device),
                 'plen': torch.zeros(self.B // self.per_sample, dtype=torch.int32, device=device)}
+
+    def _make_mask(self, device):
+        words = (int(self.dec.adaptive_softmax.vocab_size) + 31) // 32
+        return torch.zeros(self.B // self.per_sample, words, dtype=torch.int32, device=device)
 
     def _make_sink(self, kv, device):
         return decode.AttnSink([{n: torch.zeros(self.gen_len, self.B, int(pair[0].shape[0]) + 2, dtype=torch.float32,
@@ -139,6 +156,8 @@ class DecodeStepper:
             sig = sig + (('penalty',) + self.pen,)
         if self.per_sample > self.n_hyp:                          # (... and every one with one draw per sample)
             sig = sig + (('hyp', self.per_sample),)
+        if self.mask:                                             # (... and every one without a vocabulary mask)
+            sig = sig + (('mask',),)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -202,6 +221,8 @@ class DecodeStepper:
                        decode.embed_usable(dec.embedder, h['cur'], h['state']))
         if prefix:
             h['pfx'] = self._make_prefix(dev)
+        if self.mask:
+            h['vmask'] = self._make_mask(dev)
         return h
 
     def _fill(self, kv, contexts):
@@ -231,6 +252,23 @@ class DecodeStepper:
         pfx['tab'].fill_(self.pad)
         pfx['tab'][:, :tokens.shape[1]].copy_(tokens)
         pfx['plen'].copy_(plen.to(torch.int32))
+
+    def set_mask(self, ctx_ids, cls_bits=None, deny8=None, eos=2):
+        """This caption batch's vocabulary masks (one launch, tell_decode_vocab_mask: deny | (cls & ~present) without eos) into
+        the stepper's bitmap - the static one of the cache entry, which the captured picks read, or a fresh tensor when the
+        step is issued launch by launch.  ctx_ids int64 [samples, S]: every sample's article ids; cls_bits int32 [words]
+        (ops.pack_mask_bits) or None; deny8 uint8 [1 or samples, vocab] or None."""
+        if not self.mask:
+            raise ValueError('set_mask: the stepper was built without mask=True')
+        n = self.B // self.per_sample
+        if ctx_ids.dim() != 2 or ctx_ids.shape[0] != n:
+            raise ValueError('set_mask: ctx_ids int64 [%d, S] expected' % n)
+        dev = next(self.dec.parameters()).device
+        if not self.static:
+            self.vmask = self._make_mask(dev)
+        ctx_ids = ctx_ids.to(dev)
+        ops.vocab_mask(ctx_ids if ctx_ids.stride(1) == 1 else ctx_ids.contiguous(), self.dec.adaptive_softmax.vocab_size,
+                       cls_bits, deny8, eos, self.pad, out=self.vmask)
 
     def ban_source(self, hist, fin):
         """The histories the ban lists are built from (before every eager step; once when the buffers are static)."""
@@ -289,6 +327,22 @@ class DecodeStepper:
         forcing table every one of them ends in the forced pick."""
         soft, pfx = self.dec.adaptive_softmax, self.pfx
         force = (pfx['tab'], pfx['plen'], None, self.per_sample, sidx, self.pad) if pfx else None
+        if self.mask:
+            if self.vmask is None:
+                raise ValueError('a stepper with mask=True needs set_mask(...) before its first step')
+            mask, ban = (self.vmask, self.per_sample), None
+            if self.ban is not None:                                  # the ban list first; the masked pick ORs it in
+                src = self.ban_src
+                hist = src['hist']
+                step_dev = sidx if torch.is_tensor(sidx) else None
+                ops.call('tell_decode_ban_list', hist, hist.stride(0), hist.shape[1], src['fin'], self.B,
+                         0 if step_dev is not None else int(sidx), step_dev, int(self.ban[0]), int(self.ban[1]),
+                         int(self.ban[2]), src['ban'], src['ban'].stride(0), src['n_ban'])
+                ban = (src['ban'], src['n_ban'])
+            if self.sample is not None:
+                return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, mask=mask)
+            tok, lp = soft.topk(x, self.n_hyp, ban=ban, force=force, mask=mask)
+            return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
         if self.ban is not None:
             ban, src = self.ban, self.ban_src
             hist = src['hist']

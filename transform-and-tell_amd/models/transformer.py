@@ -143,6 +143,69 @@ def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_pena
     return tuple(out)
 
 
+MIN_ALLOWED_TOKENS = MAX_SAMPLING_TOPK       # every row of a vocabulary mask keeps that many tokens: a pick has k real candidates
+
+
+def check_mask_keys(suppress_tokens=(), ground_names=False):
+    """The constructor / config keys of the vocabulary masks: `suppress_tokens`, a list of token ids
+    that no caption may contain (folded into the banned set), and `ground_names`, a bool (generate(ground=True)).
+    -> (tuple of ids, bool); ValueError naming the key otherwise."""
+    st = suppress_tokens
+    if st is None:
+        st = ()
+    if isinstance(st, (str, bytes)) or not isinstance(st, (list, tuple)) or \
+            any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in st):
+        raise ValueError('suppress_tokens must be a list of token ids >= 0 (got %r)' % (suppress_tokens,))
+    if not isinstance(ground_names, bool):
+        raise ValueError('ground_names must be a bool (got %r)' % (ground_names,))
+    return tuple(sorted(set(int(t) for t in st))), ground_names
+
+
+def check_vocab_mask(banned, ground, vocab_size, batch_size, eos=2, suppress=()):
+    """generate(banned=, ground=) (DESIGN.md section 22).  banned: bool [V] or [B, V], True = the token may not be generated;
+    ground: bool [V], the grounded class - its tokens may be generated only if they occur in the row's own article; `suppress`:
+    ids folded into the banned set (the model's `suppress_tokens`).  </s> may not be banned (it is never in the class: the mask
+    kernel clears it), and every row must keep at least 64 allowed tokens - the sampler's largest k, so every pick has k real
+    candidates; for `ground` that is counted on the class's complement, for `banned` it is one reduction and one sync per call.
+    -> (deny bool [1 or B, V] or None, cls bool [V] or None); ValueError naming the option otherwise."""
+    V, B = int(vocab_size), int(batch_size)
+    cls = deny = None
+    if ground is not None:
+        if not torch.is_tensor(ground) or ground.dtype != torch.bool or tuple(ground.shape) != (V,):
+            raise ValueError('ground must be a bool tensor [%d] (the grounded class) or True (got %s)' % (
+                V, '%s %s' % (ground.dtype, tuple(ground.shape)) if torch.is_tensor(ground) else repr(ground)))
+        cls = ground.clone()
+        if 0 <= int(eos) < V:
+            cls[int(eos)] = False
+        if V - int(cls.sum()) < MIN_ALLOWED_TOKENS:
+            raise ValueError('ground: the class leaves %d tokens outside it, at least %d must stay allowed'
+                             % (V - int(cls.sum()), MIN_ALLOWED_TOKENS))
+    if banned is not None:
+        if not torch.is_tensor(banned) or banned.dtype != torch.bool or banned.dim() not in (1, 2) or \
+                banned.shape[-1] != V or (banned.dim() == 2 and banned.shape[0] != B):
+            raise ValueError('banned must be a bool tensor [%d] or [%d, %d] (got %s)' % (
+                V, B, V, '%s %s' % (banned.dtype, tuple(banned.shape)) if torch.is_tensor(banned) else repr(banned)))
+        deny = banned.view(1, V) if banned.dim() == 1 else banned
+        if 0 <= int(eos) < V and bool(deny[:, int(eos)].any()):
+            raise ValueError('banned: </s> (%d) may not be banned - a caption could never end' % int(eos))
+    sup = [int(t) for t in suppress]
+    if sup:
+        if max(sup) >= V:
+            raise ValueError('suppress_tokens: token ids must lie in 0..%d (got %d)' % (V - 1, max(sup)))
+        if int(eos) in sup:
+            raise ValueError('suppress_tokens: </s> (%d) may not be suppressed - a caption could never end' % int(eos))
+        dev = deny.device if deny is not None else (cls.device if cls is not None else 'cpu')
+        deny = deny.clone() if deny is not None else torch.zeros(1, V, dtype=torch.bool, device=dev)
+        deny[:, torch.tensor(sup, dtype=torch.long, device=deny.device)] = True
+    if deny is not None:
+        gone = deny if cls is None else (deny | cls.to(deny.device).view(1, V))
+        left = V - int(gone.sum(1).max())                    # (the one reduction and sync of the non-default path)
+        if left < MIN_ALLOWED_TOKENS:
+            raise ValueError('%s: a row keeps %d allowed tokens, at least %d must stay allowed'
+                             % ('banned' if banned is not None else 'suppress_tokens', left, MIN_ALLOWED_TOKENS))
+    return deny, cls
+
+
 def check_prefix(prefix, batch_size, vocab_size, gen_len=DEFAULT_GEN_LEN, pad=1, eos=2):
     """The forced caption prefix of the cached generators: int64 [B, P], the caption tokens AFTER <s>,
     right-padded with `pad`; plen[r] = the number of leading non-pad tokens (0: the row decodes freely).  </s> may only be
@@ -401,7 +464,8 @@ class CaptionModel(Model):
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
                  initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(),
+                 ground_names=False):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -423,6 +487,8 @@ class CaptionModel(Model):
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = check_penalties(
             repetition_penalty, presence_penalty, frequency_penalty)
         self._check_penalties()
+        self.suppress_tokens, self.ground_names = check_mask_keys(suppress_tokens, ground_names)
+        self._check_mask_options()
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -533,6 +599,79 @@ class CaptionModel(Model):
             raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
                              'penalties cover the cached DynamicConv generator only' % (what, type(self).__name__))
         return pen
+
+    def _mask_options(self, banned=None, ground=None):
+        """-> the names of the vocabulary-mask options in force ('banned', 'ground', 'suppress_tokens', 'ground_names'), the
+        call's arguments and the model's attributes alike; empty: nothing set."""
+        st, gn = check_mask_keys(getattr(self, 'suppress_tokens', ()), getattr(self, 'ground_names', False))
+        used = []
+        if banned is not None:
+            used.append('banned')
+        if ground is not None and ground is not False:
+            used.append('ground')
+        if st:
+            used.append('suppress_tokens')
+        if gn and 'ground' not in used:
+            used.append('ground_names')
+        return used
+
+    def _check_mask_options(self, banned=None, ground=None, attention=False):
+        """What a vocabulary mask combines with: the arg-max, beam and top-k sampling decodes of the
+        cached DynamicConv generator, with or without the search options, n_samples and a prefix - no truncation rule, no
+        penalties, no attention maps, not the LSTM decoders nor the copy models.  -> the option names in force (may be empty)."""
+        used = self._mask_options(banned, ground)
+        if not used:
+            return used
+        what = ' / '.join(used)
+        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
+            if getattr(self, name, None) is not None:
+                raise ValueError('%s and %s=%r do not combine: a vocabulary mask covers the arg-max, beam and top-k sampling '
+                                 'decodes' % (what, name, getattr(self, name)))
+        if self._penalties() is not None:
+            pen = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, self._penalties(), (1.0, 0.0, 0.0)) if v != d)
+            raise ValueError('%s and %s do not combine: the penalties\' bitmap means "listed", not "banned"' % (what, pen))
+        if attention:
+            raise ValueError('%s and attention=True do not combine: attention maps are exported without a vocabulary mask' % what)
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); vocabulary '
+                             'masks cover the cached DynamicConv generator only' % (what, type(self).__name__))
+        return used
+
+    def name_tokens(self):
+        """The grounded class of generate(ground=True): data.bpe.capitalised_tokens over the installed roberta-base vocabulary -
+        bool [vocab], the BPE pieces that start a capitalised word (per token, not per word: continuation pieces are
+        unconstrained).  Cached; FileNotFoundError when the vocabulary files are absent."""
+        cls = self.__dict__.get('_name_tokens')
+        if cls is None:
+            from ..data.bpe import RobertaBPE, capitalised_tokens
+            from ..data.indexers import bpe_directory
+            cls = capitalised_tokens(RobertaBPE(bpe_directory()))
+            V = int(self.decoder.adaptive_softmax.vocab_size)
+            full = torch.zeros(V, dtype=torch.bool)
+            full[:min(V, cls.numel())] = cls[:V]
+            cls = self.__dict__['_name_tokens'] = full
+        return cls
+
+    def _vocab_mask(self, context, banned=None, ground=None, attention=False, eos=2):
+        """The vocabulary mask of one caption batch, from generate's arguments and the model's `suppress_tokens` /
+        `ground_names`: -> None when nothing is set (the default path reads nothing of the batch), else (ctx_ids int64 [B, S] -
+        the article ids context[self.index] -, cls_bits int32 [words] or None, deny8 uint8 [1 or B, V] or None), what
+        DecodeStepper.set_mask takes.  check_vocab_mask and _check_mask_options apply."""
+        used = self._check_mask_options(banned, ground, attention)
+        if not used:
+            return None
+        ctx_ids = context[self.index]
+        if ground is True or (ground is None and 'ground_names' in used):
+            ground = self.name_tokens()
+        if ground is False:
+            ground = None
+        V = int(self.decoder.adaptive_softmax.vocab_size)
+        deny, cls = check_vocab_mask(banned, ground, V, ctx_ids.shape[0], eos,
+                                     suppress=getattr(self, 'suppress_tokens', ()) or ())
+        dev = ctx_ids.device
+        cls_bits = None if cls is None else ops.pack_mask_bits(cls).to(dev)
+        deny8 = None if deny is None else deny.to(device=dev, dtype=torch.uint8).contiguous()
+        return ctx_ids, cls_bits, deny8
 
     def _check_prefix(self, prefix, batch_size, gen_len=DEFAULT_GEN_LEN, eos=2):
         """generate(prefix=...): check_prefix against this model; the cached DynamicConv generators only - the LSTM decoders
@@ -770,8 +909,10 @@ class CaptionModel(Model):
         output_dict, caption_ids, contexts = self._forward_loss(context, image, caption, face_embeds, obj_embeds, encoded)
         if not self.training and self.evaluate_mode:                       # :92-116
             # (eval_attention: commands/evaluate.py's opt-in - the captions come with their attention maps)
+            vm = self._vocab_mask(context, attention=bool(getattr(self, 'eval_attention', False)))
             _, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=getattr(self, 'eval_beam_size', 1),
-                                               **({'attention': True} if getattr(self, 'eval_attention', False) else {}))
+                                               **({'attention': True} if getattr(self, 'eval_attention', False) else {}),
+                                               **({'vmask': vm} if vm is not None else {}))
             self._forward_generated(output_dict, gen_ids, attns, metadata)
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
@@ -832,8 +973,16 @@ class CaptionModel(Model):
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        banned / ground (vocabulary masks): banned - bool [V] or [B, V] - lists tokens no caption (of
+        that row) may contain; ground - bool [V], or True for `name_tokens()`, the BPE pieces that start a capitalised word -
+        is a class of tokens that may be generated only if they occur in the row's own article context[index] (the class is per
+        token, not per word: continuation pieces are unconstrained).  The model's `suppress_tokens` joins `banned`,
+        `ground_names` means ground=True.  A masked token is never picked - greedy, beam search (with its search options and
+        n_best) and top-k sampling (with n_samples), with or without a prefix; every reported log-prob is the model's own
+        (nothing is renormalised), </s> is always allowed, a forced prefix token still wins.  None / None with the model's keys
+        at their defaults: exactly the call of before.
         n_samples = n (2..16; a sampling model): n draws per image from ONE pass of the encoders and ONE
         cached context - row b * n + j of the decode step is draw j of image b, keyed (seed, b * n + j, step): under the same
         torch.manual_seed the draws of the batch with every image repeated n times.  Adds 'gen_ids_samples' [B, n, L],
@@ -868,10 +1017,12 @@ class CaptionModel(Model):
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         # (prefix=None reads nothing of the batch here: the default path is the path of before)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
+        vm = self._vocab_mask(context, banned, ground, attention)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
                                                    **({'samples': ns} if ns is not None else {}),
+                                                   **({'vmask': vm} if vm is not None else {}),
                                                    prefix=pfx)
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
@@ -910,7 +1061,7 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1, n_samples=1,
-                       rank_by='score', rank_len_penalty=0.0):
+                       rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own DecodeStepper - captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
@@ -918,7 +1069,11 @@ class CaptionModel(Model):
         encoders of a group of batches run first (eval mode: no randomness, results identical to `generate`).
         Yields (batch, output) in order.  forward=True: the outputs of `forward` in evaluate mode (loss + captions + per-sample
         BLEU bookkeeping: what commands/evaluate.py consumes) instead of `generate`'s; beam_size then is `eval_beam_size`.
-        n_samples / rank_by / rank_len_penalty: as `generate` - every lane decodes the n hypotheses of its batch's images."""
+        n_samples / rank_by / rank_len_penalty: as `generate` - every lane decodes the n hypotheses of its batch's images.
+        banned (bool [V]) / ground (bool [V] or True): the shared forms of `generate`'s vocabulary masks, applied to every batch
+        (each row grounded in its own article)."""
+        if banned is not None and (not torch.is_tensor(banned) or banned.dim() != 1):
+            raise ValueError('generate_lanes takes the shared form of banned: a bool tensor [V]')
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
         if attention:
             if forward:
@@ -960,14 +1115,16 @@ class CaptionModel(Model):
                     raise ValueError('prefix goes with generate, not with forward=True')
                 pfx = self._check_prefix(b.get('prefix'), caption_ids.shape[0])
                 plens.append(pfx[1] if pfx is not None else None)
+                vm = self._vocab_mask(b['context'], banned, ground, attention)
+                vkw = {'vmask': vm} if vm is not None else {}
                 ev = torch.cuda.Event()
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx)
+                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx, **vkw)
                          if beam_size > 1 else
                          self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx,
-                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {})))
+                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {}), **vkw))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -1046,12 +1203,21 @@ class CaptionModel(Model):
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
-                  prefix=None, samples=None):
+                  prefix=None, samples=None, vmask=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
         if self._check_penalties(attention) is not None:      # (the penalties live in the cached generators, like `opts`)
             opts = opts or (0.0, 0, 0)
         if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
             self._check_prefix(prefix[0], caption_ids.shape[0], gen_len, eos)
+        if vmask is not None:                 # (ctx_ids, cls_bits, deny8) of _vocab_mask: lives in the cached generators
+            self._check_mask_options(True, None, attention)
+            if not hasattr(self.decoder, 'project_contexts'):
+                raise ValueError('vocabulary masks cover the cached DynamicConv generator only')
+            self._check_beam(beam_size)
+            vkw = {'vmask': vmask}
+            if beam_size > 1:
+                return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix, **vkw)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **vkw)
         if attention:
             # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
             # flow with the legacy need_attn export, which stays what it is)
@@ -1085,14 +1251,15 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None,
-                         samples=None):
+                         samples=None, vmask=None):
         # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
                                               **({'prefix': prefix} if prefix is not None else {}),
-                                              **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {})))
+                                              **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {}),
+                                              **({'vmask': vmask} if vmask is not None else {})))
 
     def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
-                      prefix=None, n=1, rank=('score', 0.0)):
+                      prefix=None, n=1, rank=('score', 0.0), vmask=None):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -1113,7 +1280,9 @@ class CaptionModel(Model):
         cur, ids, lps, done_step and fin8 are R rows tall, the contexts, masks, projected K/V and the prefix stay at width B (as
         _beam_steps hands them to the stepper), one seed, row r draws with (seed, r, step).  Behind the loop one launch
         (tell_sample_rank, rank = (rule, alpha)) scores, de-duplicates and ranks the n hypotheses of every image: the results
-        are the first rank's, the third a DecodeInfo with .scores and .samples."""
+        are the first rank's, the third a DecodeInfo with .scores and .samples.
+        vmask = (ctx_ids, cls_bits, deny8) of _vocab_mask: the stepper's bitmap - one row per image - is built before the first
+        step (step.set_mask) and every pick is the masked one; the bookkeeping is untouched."""
         dec = self.decoder
         n = int(n)
         images = caption_ids.shape[0]
@@ -1127,9 +1296,11 @@ class CaptionModel(Model):
         pen = self._check_penalties(attention)
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
                                     prefix=prefix is not None, **({'pen': pen} if pen is not None else {}),
-                                    **({'hyp': n} if n > 1 else {}))
+                                    **({'hyp': n} if n > 1 else {}), **({'mask': True} if vmask is not None else {}))
         if prefix is not None:
             step.set_prefix(*prefix)
+        if vmask is not None:
+            step.set_mask(*vmask, eos=int(eos))
         if sampling is not None:
             step.seed.fill_(draw_seed() if seed is None else int(seed))
         cur = caption_ids[:, 0:1].contiguous() if n == 1 else caption_ids[:, 0:1].repeat_interleave(n, dim=0).contiguous()
@@ -1224,17 +1395,21 @@ class CaptionModel(Model):
         return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None, hyp=1):
+                        prefix=False, pen=None, hyp=1, mask=False):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
-                             opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}))
+                             opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}),
+                             **({'mask': True} if mask else {}))
 
     @torch.no_grad()
-    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
-        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best, prefix=prefix))
+    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
+                       vmask=None):
+        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best, prefix=prefix,
+                                            **({'vmask': vmask} if vmask is not None else {})))
 
-    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None):
+    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
+                    vmask=None):
         """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
         only samples top-1, transformer_faces_objects.py:443-464).  B*K rows (row = b*K + j) stay resident; the
         projected K/V of the static contexts are computed once per caption and replicated per beam; the DynamicConv
@@ -1249,7 +1424,9 @@ class CaptionModel(Model):
         token and K - 1 fillers (-inf, pad), so only slot 0 stays live - as at step 0 - and the beam opens at the first free
         step; the bookkeeping is untouched.
         With penalties set (_penalties()): every hypothesis' K best are taken over its penalised scores (step.pen_source over
-        `seqs`), and `cum`, the log_probs and the scores accumulate those scores."""
+        `seqs`), and `cum`, the log_probs and the scores accumulate those scores.
+        vmask = (ctx_ids, cls_bits, deny8) of _vocab_mask: the K hypotheses of a sample share its row of the stepper's bitmap
+        (step.set_mask) and every hypothesis' K best are taken under it - with a ban list, in the same launch."""
         dec = self.decoder
         B, K = caption_ids.shape[0], int(beam_size)
         dev = caption_ids.device
@@ -1265,9 +1442,11 @@ class CaptionModel(Model):
         pen = self._check_penalties()
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
                                     opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None,
-                                    **({'pen': pen} if pen is not None else {}))
+                                    **({'pen': pen} if pen is not None else {}), **({'mask': True} if vmask is not None else {}))
         if prefix is not None:
             step.set_prefix(*prefix)
+        if vmask is not None:
+            step.set_mask(*vmask, eos=int(eos))
         cur = rep(caption_ids[:, 0:1], 0)
         finished = (cur[:, 0] == eos).view(B, K)
         fused = caption_ids.is_cuda and step.static and K <= 8 and gen_len + 1 <= 256

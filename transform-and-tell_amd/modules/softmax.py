@@ -74,20 +74,24 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k, ban=None, force=None, pen=None):
+    def topk(self, X, k, ban=None, force=None, pen=None, mask=None):
         """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
         ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
         (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans).
         pen = (theta, sub fp32 [n_sub], pen_tok int32 [B * T, ld], pen_cnt alike, n_pen int32 [B * T]): the k best PENALISED
         scores s = min(lp, 0) * theta - sub[count] of the listed tokens, lp of every other (DESIGN.md section 20,
-        tell_adaptive_logprob_topk_penalised); the second result then holds scores, not log-probs."""
+        tell_adaptive_logprob_topk_penalised); the second result then holds scores, not log-probs.
+        mask = (bits int32 [B * T / per, words], per): position r never lists a token whose bit is set in bits[r // per]; every
+        log-prob is the unmasked one (tell_adaptive_logprob_topk_masked; a ban list may join it)."""
         B, T, E = X.shape
         kw = {'pen': pen} if pen is not None else {}
+        if mask is not None:
+            kw['mask'] = mask
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
                                             self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force, **kw)
         return tok.view(B, T, k), lp.view(B, T, k)
 
-    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None, pen=None):
+    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None, pen=None, mask=None):
         """One top-k draw with temperature per position (transformer_faces_objects.py:443-470: lprobs.topk(k), / temp,
         multinomial), fused like `greedy`: -> (token [B, T], log-prob [B, T] WITHOUT the temperature).  seed_dev: int32 [1]
         device word holding the seed; step: host step index or the int32 [1] device counter of a captured step (step - 1);
@@ -96,11 +100,18 @@ class AdaptiveSoftmax(nn.Module):
         tell_adaptive_logprob_nucleus) - the same launches up to the last one.  rule = 'minp' / 'typical': topp is that
         rule's parameter (m / tau; k = 0; tell_adaptive_logprob_minp / tell_adaptive_logprob_typical).
         pen (as in `topk`; the top-k draw only): the draw runs over the penalised scores and the second result is the drawn
-        token's score (tell_adaptive_logprob_sample_penalised)."""
+        token's score (tell_adaptive_logprob_sample_penalised).
+        mask (as in `topk`; the top-k draw only): the candidates are the k best tokens that are not masked
+        (tell_adaptive_logprob_sample_masked)."""
         if pen is not None and (topp is not None or rule is not None):
             raise ValueError('sample: penalties go with the top-k draw, not with sampling_topp / sampling_minp / sampling_typical')
+        if mask is not None and (topp is not None or rule is not None or pen is not None):
+            raise ValueError('sample: a vocabulary mask goes with the top-k draw, not with sampling_topp / sampling_minp / '
+                             'sampling_typical or the penalties')
         B, T, E = X.shape
         kw = {'pen': pen} if pen is not None else {}
+        if mask is not None:
+            kw['mask'] = mask
         sample = (int(k), 1.0 / float(temp), seed_dev, row_ids, step)
         if topp is not None:
             sample = sample + (float(topp),)
@@ -110,12 +121,16 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), sample=sample, force=force, **kw)
         return tok.view(B, T), lp.view(B, T)
 
-    def greedy(self, X, force=None):
+    def greedy(self, X, force=None, mask=None):
         """Fused arg-max over the full vocabulary (get_log_prob + topk(1),
         transformer_faces_objects.py:443-464) without materialising [N, vocab].
         force (here, in `topk` and in `sample`): the forcing table of a caption completion (ops.logprob_forced) - rows with
-        prefix left take the prefix token and its log-prob instead of the pick."""
+        prefix left take the prefix token and its log-prob instead of the pick.
+        mask (as in `topk`): the arg-max over the tokens that are not masked - `topk` with k = 1."""
         B, T, E = X.shape
+        if mask is not None:
+            tok, lp = self.topk(X, 1, force=force, mask=mask)
+            return tok.view(B, T), lp.view(B, T)
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
                                             self.head.class_proj.weight, self._tails(), force=force)
         return tok.view(B, T), lp.view(B, T)

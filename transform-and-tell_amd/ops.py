@@ -1756,7 +1756,58 @@ def _pen_args(pen, N):
     return pen_tok, pen_cnt, pen_tok.stride(0), n_pen, float(theta), sub, sub.numel()
 
 
-def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None):
+def _mask_args(mask, N, vocab):
+    """mask = (bits int32 [N / per, ld >= words] on the device - the uint32 bitmaps of tell_decode_vocab_mask -, per): row r
+    of the launch reads bits[r // per] -> the mask arguments of the masked entry points, checked."""
+    bits, per = mask
+    per = int(per)
+    words = (int(vocab) + 31) // 32
+    if bits.dtype != torch.int32 or bits.dim() != 2 or bits.stride(1) != 1 or bits.shape[1] < words or per < 1 or \
+            N % per or bits.shape[0] != N // per:
+        raise ValueError('mask: (bits int32 [%d / per, >= %d words], per) with per dividing the %d rows expected' % (N, words, N))
+    return bits, bits.stride(0), per
+
+
+def pack_mask_bits(flags):
+    """bool [V] or [R, V] -> int32 [words] / [R, words], words = (V + 31) // 32: bit (t & 31) of word t >> 5 = flags[t] (the
+    layout of tell_decode_vocab_mask; the tail bits of the last word are 0).  Built on the host."""
+    import numpy as np
+    f = flags.detach().cpu().numpy().astype(bool)
+    V = f.shape[-1]
+    words = (V + 31) // 32
+    padded = np.zeros(f.shape[:-1] + (words * 32,), dtype=np.uint8)
+    padded[..., :V] = f
+    packed = np.packbits(padded, axis=-1, bitorder='little').view('<u4').astype(np.uint32).view(np.int32)
+    return torch.from_numpy(np.ascontiguousarray(packed)).to(flags.device)
+
+
+def vocab_mask(ctx_ids, vocab, cls_bits=None, deny8=None, eos=2, pad=1, out=None):
+    """tell_decode_vocab_mask: the mask of every image, deny | (cls & ~present) without eos (include/tell_hip.h).  ctx_ids int64
+    [B, S] (stride(1) == 1); cls_bits int32 [words] (pack_mask_bits) or None; deny8 uint8 [V], [1, V] or [B, V] or None.
+    -> out (int32 [B, >= words]; made when None)."""
+    B, S = ctx_ids.shape
+    words = (int(vocab) + 31) // 32
+    if ctx_ids.dtype != torch.long or ctx_ids.dim() != 2 or (S and ctx_ids.stride(1) != 1):
+        raise ValueError('vocab_mask: ctx_ids int64 [B, S] with unit stride along S expected')
+    if cls_bits is not None and (cls_bits.dtype != torch.int32 or cls_bits.numel() < words or not cls_bits.is_contiguous()):
+        raise ValueError('vocab_mask: cls_bits int32 [%d] expected' % words)
+    ld_deny = 0
+    if deny8 is not None:
+        deny8 = deny8.view(1, -1) if deny8.dim() == 1 else deny8
+        if deny8.dtype != torch.uint8 or deny8.dim() != 2 or deny8.shape[1] != int(vocab) or deny8.stride(1) != 1 or \
+                deny8.shape[0] not in (1, B):
+            raise ValueError('vocab_mask: deny8 uint8 [1 or %d, %d] expected' % (B, int(vocab)))
+        ld_deny = deny8.stride(0) if deny8.shape[0] > 1 else 0
+    if out is None:
+        out = torch.empty(B, words, dtype=torch.int32, device=ctx_ids.device)
+    if out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < words or out.stride(1) != 1:
+        raise ValueError('vocab_mask: out int32 [%d, >= %d] expected' % (B, words))
+    call('tell_decode_vocab_mask', ctx_ids, ctx_ids.stride(0) if S else 0, S, B, int(vocab), cls_bits, deny8, ld_deny, int(eos),
+         int(pad), out, out.stride(0))
+    return out
+
+
+def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None, mask=None):
     """The sampling head's last launch (tell_adaptive_logprob_sample) over the fp32 logits of the head and the tails.
     sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
     int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
@@ -1764,10 +1815,13 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None)
     A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut); a seventh names another
     rule for the sixth: 'minp' (m: tell_adaptive_logprob_minp, log(m) formed here in fp64) or 'typical' (tau:
     tell_adaptive_logprob_typical) - both over the whole row, k = 0.  pen (see _pen_args; the top-k draw only): the draw runs
-    over the penalised scores (tell_adaptive_logprob_sample_penalised) and the second result is the token's score."""
+    over the penalised scores (tell_adaptive_logprob_sample_penalised) and the second result is the token's score.
+    mask (see _mask_args; the top-k draw only): masked tokens are never candidates (tell_adaptive_logprob_sample_masked)."""
     k, inv_temp, seed_dev, row_ids, step = sample[:5]
     if pen is not None and len(sample) > 5:
         raise ValueError('logprob_sample: penalties go with the top-k draw, not with a truncation rule')
+    if mask is not None and (len(sample) > 5 or pen is not None):
+        raise ValueError('logprob_sample: a vocabulary mask goes with the top-k draw, not with a truncation rule or penalties')
     step_dev = step if torch.is_tensor(step) else None
     token = torch.empty(N, dtype=torch.int32, device=head.device)
     token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
@@ -1792,19 +1846,35 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None)
              tl[2], lds[2], ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step),
              step_dev, *_pen_args(pen, N), token, token_lp)
         return token, token_lp, None
+    if mask is not None:
+        call('tell_adaptive_logprob_sample_masked', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
+             tl[2], lds[2], ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step),
+             step_dev, *_mask_args(mask, N, c0 + sum(ns[:n_tails])), token, token_lp)
+        return token, token_lp, None
     call('tell_adaptive_logprob_sample', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
          ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token,
          token_lp)
     return token, token_lp, None
 
 
-def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None):
+def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None, mask=None):
     """The top-k head's last launch: tell_adaptive_logprob_topk, or - ban = (ban int32 [N, ld_ban], n_ban int32 [N]) -
     tell_adaptive_logprob_topk_banned, or - pen (see _pen_args) - tell_adaptive_logprob_topk_penalised, whose second result
-    holds the penalised scores.  -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
+    holds the penalised scores, or - mask (see _mask_args), with or without a ban list - tell_adaptive_logprob_topk_masked.
+    -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
     tokens = torch.empty(N, k, dtype=torch.int32, device=head.device)
     lps = torch.empty(N, k, dtype=torch.float32, device=head.device)
-    if pen is not None:
+    if mask is not None:
+        if pen is not None:
+            raise ValueError('logprob_topk: a vocabulary mask and penalties do not combine')
+        bans, n_ban = ban if ban is not None else (None, None)
+        if ban is not None and (bans.shape[0] != N or n_ban.shape[0] != N or bans.dtype != torch.int32 or
+                                n_ban.dtype != torch.int32):
+            raise ValueError('logprob_topk: ban int32 [%d, ld] and n_ban int32 [%d] expected' % (N, N))
+        call('tell_adaptive_logprob_topk_masked', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
+             tl[2], lds[2], ns[2], N, int(k), *_mask_args(mask, N, c0 + sum(ns[:n_tails])), bans,
+             bans.stride(0) if ban is not None else 0, n_ban, tokens, lps)
+    elif pen is not None:
         if ban is not None:
             raise ValueError('logprob_topk: a ban list and penalties do not combine')
         call('tell_adaptive_logprob_topk_penalised', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
@@ -1841,15 +1911,18 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
 
 
 def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None,
-                       pen=None):
+                       pen=None, mask=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
     draw per row instead of the arg-max
     (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced);
-    pen (see _pen_args; with topk = k >= 1 or a top-k draw): the pick runs over the penalised scores."""
+    pen (see _pen_args; with topk = k >= 1 or a top-k draw): the pick runs over the penalised scores;
+    mask (see _mask_args; with topk = k >= 1 or a top-k draw): masked tokens are never picked."""
     if pen is not None and (want_full or (not topk and sample is None)):
         raise ValueError('adaptive_log_probs: penalties go with topk = k >= 1 or a top-k draw')
+    if mask is not None and (want_full or (not topk and sample is None)):
+        raise ValueError('adaptive_log_probs: a vocabulary mask goes with topk = k >= 1 or a top-k draw')
     if force is not None and want_full:
         raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
     N, E = x2.shape
@@ -1861,6 +1934,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
+        if mask is not None:     # (a call without a mask is the call it was: stand-ins for head_step keep working)
+            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask)
         if pen is not None:      # (a call without penalties is the call it was: stand-ins for head_step keep working)
             return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen)
         return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force)
@@ -1881,9 +1956,11 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     def forced(picked):
         return picked if force is None else logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
     if sample is not None and not want_full:
-        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample, pen=pen))
+        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample, pen=pen,
+                                     **({'mask': mask} if mask is not None else {})))
     if topk:
-        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban, pen=pen))
+        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban, pen=pen,
+                                   **({'mask': mask} if mask is not None else {})))
     if ban is not None:
         raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
     full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
