@@ -286,7 +286,7 @@ extern "C" int tell_dynconv_bwd(const void* x, const void* dy, const float* taps
   TELL_REQUIRE(p >= 0.f && p < 1.f, "dynconv: p must be in [0,1)");
   uint32_t thr = p > 0.f ? tell_drop_threshold(p) : 0u;
   float ik = 1.f / (1.f - p);
-  if (dc_lds_ok(x, dy, T, R, K, dtype) && T <= 64 && (H * R) % 8 == 0 && ((uintptr_t)dx & 15) == 0) {   // <= 48 KB of LDS
+  if (dc_lds_ok(x, dy, T, R, K, dtype) && T <= 64 && (H * R) % 8 == 0 && ((uintptr_t)dx & 15) == 0) {   // <= 49 408 B of LDS (T = 64, K = 32): no attribute needed
     const size_t smem = ((size_t)T * (2 * DC_R + 1) + (size_t)2 * T * K) * sizeof(float);
     if (dtype == TELL_BF16) hipLaunchKernelGGL((dynconv_bwd_lds_kernel<uint16_t>), dim3(B * H), dim3(256), smem, stream, (const uint16_t*)x, (const uint16_t*)dy, taps, (uint16_t*)dx, dx_accumulate, (uint16_t*)dlogits, T, B, H, K, thr, ik, seed, salt, g_tell_rng_step);
     else hipLaunchKernelGGL((dynconv_bwd_lds_kernel<float>), dim3(B * H), dim3(256), smem, stream, (const float*)x, (const float*)dy, taps, (float*)dx, dx_accumulate, (float*)dlogits, T, B, H, K, thr, ik, seed, salt, g_tell_rng_step);
