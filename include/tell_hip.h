@@ -618,6 +618,22 @@ int tell_adaptive_logprob_topk_masked(const float* head, long ld_head, int c0, i
                                       int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
                                       int rows, int k, const uint32_t* mask, long ld_mask, int per, const int* ban,
                                       long ld_ban, const int* n_ban, int* tokens, float* lps, tell_stream_t stream);
+/* CONTEXT GUIDANCE: the pick of a decode step whose batch holds every caption twice.  `rows` conditional
+ * rows r = 0 .. rows - 1; the partner of row r - the same caption decoded with some contexts dropped - is row r + pair_offset
+ * of the same logit buffers (pair_offset >= rows).  With lp_c, lp_u the full log-probs of the two rows as
+ * tell_adaptive_logprob_argmax computes them, and gamma = *gamma_dev (a device float, read by the kernel: a captured step
+ * serves every gamma):
+ *     d = lp_c - lp_u;  t = (gamma - 1) * d;  s = lp_c + t     three fp32 operations rounded one by one, never an FMA
+ *     L = log sum_v exp(s(v)) over the whole vocabulary (max-shifted, fp32);  g = s - L
+ * The result is the k best tokens of the pair ranked by s, value descending, lower id first on ties, reported with g (a
+ * normalised log-prob), written to tokens / lps [.., k] at row r AND at row r + pair_offset.  gamma = 1, or u == c, makes s
+ * equal lp_c bit for bit: the tokens are then those of tell_adaptive_logprob_topk.  s_rows: optional fp32 [rows, ld_s >= vocab],
+ * the full s of every pair (NULL: not written).  k = 1..8 (k = 1: the guided arg-max); register and streaming forms as
+ * tell_adaptive_logprob_topk (option argmax_regs). */
+int tell_adaptive_logprob_topk_guided(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                      int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                      int rows, long pair_offset, int k, const float* gamma_dev, float* s_rows, long ld_s,
+                                      int* tokens, float* lps, tell_stream_t stream);
 int tell_adaptive_logprob_argmax(const float* head, long ld_head, int c0, int n_tails, const float* tail0,
                                  long ld0, int n0, const float* tail1, long ld1, int n1, const float* tail2,
                                  long ld2, int n2, int rows, float* log_probs, long ld_lp, int* token,

@@ -46,12 +46,14 @@ def build_decoder(kind='faces_objects', vocab_size=50265, dim=1024, heads=16, ff
 def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=25, sampling_topk=1, sampling_temp=1.0,
                 sampling_topp=None, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None,
                 sampling_typical=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(),
-                ground_names=False, **decoder_kw):
+                ground_names=False, guidance_scale=1.0, guidance_drop=('image',), **decoder_kw):
     search = dict(beam_len_penalty=beam_len_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_len=min_len,
                   sampling_minp=sampling_minp, sampling_typical=sampling_typical, repetition_penalty=repetition_penalty,
                   presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
     if suppress_tokens or ground_names is not False:         # (the defaults add nothing to the constructor call)
         search.update(suppress_tokens=suppress_tokens, ground_names=ground_names)
+    if guidance_scale != 1.0 or tuple(guidance_drop) != ('image',):
+        search.update(guidance_scale=guidance_scale, guidance_drop=guidance_drop)
     if kind in ('pointer', 'pointer_2'):                     # expt/*/a1-a3: transformer_pointer(_2) on the faces decoder
         from .models.pointer import TransformerPointer2Model, TransformerPointerModel
         dec = build_decoder('faces_parallel', **decoder_kw)

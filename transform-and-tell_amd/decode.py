@@ -208,7 +208,7 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None, mask=None):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None, mask=None, guide=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
@@ -218,7 +218,13 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     tell_adaptive_logprob_topk_banned (ops.logprob_topk); force (caption completion): one more launch behind that pick,
     tell_adaptive_logprob_forced over the same logits (ops.logprob_forced) - without it the launches are what they were.
     pen (ops._pen_args; with topk or sample): the last launch is tell_adaptive_logprob_topk_penalised / _sample_penalised.
-    mask (ops._mask_args; with topk - a ban list may join it - or a top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked."""
+    mask (ops._mask_args; with topk - a ban list may join it - or a top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked.
+    guide = (pair_offset, gamma_dev) (context guidance; with topk alone): the last launch is
+    tell_adaptive_logprob_topk_guided over the N / 2 pairs of rows (r, r + pair_offset)."""
+    if guide is not None and (not topk or sample is not None or ban is not None or force is not None or pen is not None or
+                              mask is not None):
+        raise ValueError('head_step: guidance goes with topk = k >= 1 alone')
+    mk_g = {'guide': guide} if guide is not None else {}
     if mask is not None and ((not topk and sample is None) or pen is not None):
         raise ValueError('head_step: a vocabulary mask goes with topk = k >= 1 or a top-k draw, without penalties')
     mk = {'mask': mask} if mask is not None else {}
@@ -272,7 +278,7 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         if sample is not None:
             return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
         if topk:
-            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk))
+            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk, **mk_g))
         token = torch.empty(N, dtype=torch.int32, device=dev)
         token_lp = torch.empty(N, dtype=torch.float32, device=dev)
         call('tell_adaptive_logprob_argmax', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
@@ -314,7 +320,7 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     if sample is not None:
         return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
     if topk:
-        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk))
+        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk, **mk_g))
     token = torch.empty(N, dtype=torch.int32, device=dev)
     token_lp = torch.empty(N, dtype=torch.float32, device=dev)
     call('tell_adaptive_logprob_argmax', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],

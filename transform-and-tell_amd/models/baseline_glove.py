@@ -9,8 +9,8 @@ import math
 import torch
 
 from .. import ops
-from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_mask_keys, check_penalties,
-                          check_sampling, draw_seed, set_sampling)
+from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_guidance, check_mask_keys,
+                          check_penalties, check_sampling, draw_seed, set_sampling)
 
 
 def _refuse_mask_options(model, suppress_tokens=(), ground_names=False, banned=None, ground=None):
@@ -22,6 +22,15 @@ def _refuse_mask_options(model, suppress_tokens=(), ground_names=False, banned=N
         raise ValueError('%s: %s decodes with an LSTM decoder, whose step has its own decision launch; vocabulary masks cover '
                          'the cached DynamicConv generator only' % (' / '.join(used), type(model).__name__))
     return st, gn
+
+
+def _refuse_guidance(model, guidance_scale=1.0, guidance_drop=('image',)):
+    """BaselineGloveModel decodes with an LSTM decoder: context guidance is out of scope there."""
+    gamma, drop = check_guidance(guidance_scale, guidance_drop)
+    if gamma != 1.0:
+        raise ValueError('guidance=%r: %s decodes with an LSTM decoder, whose step has its own decision launch; context guidance '
+                         'covers the cached DynamicConv generator only' % (gamma, type(model).__name__))
+    return gamma, drop
 
 
 def _refuse_search_options(model, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, n_best=1):
@@ -44,10 +53,12 @@ class BaselineGloveModel(Model):
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, max_caption_len=50,
                  weigh_bert=False, initializer=None, resnet=None, sampling_topp=None, beam_len_penalty=0.0,
                  no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None, repetition_penalty=1.0,
-                 presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False):
+                 presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False, guidance_scale=1.0,
+                 guidance_drop=('image',)):
         super().__init__(vocab)
         _refuse_search_options(self, beam_len_penalty, no_repeat_ngram_size, min_len)
         self.suppress_tokens, self.ground_names = _refuse_mask_options(self, suppress_tokens, ground_names)
+        self.guidance_scale, self.guidance_drop = _refuse_guidance(self, guidance_scale, guidance_drop)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if pen != (1.0, 0.0, 0.0):
             raise ValueError('%s: %s decodes with an LSTM decoder; the penalties cover the cached DynamicConv generator only'
@@ -119,9 +130,12 @@ class BaselineGloveModel(Model):
         return out
 
     def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None,
-                 n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
+                 n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None,
+                 guidance_drop=None):
         _refuse_search_options(self, n_best=n_best)
         _refuse_mask_options(self, banned=banned, ground=ground)
+        _refuse_guidance(self, getattr(self, 'guidance_scale', 1.0) if guidance is None else guidance,
+                         getattr(self, 'guidance_drop', ('image',)) if guidance_drop is None else guidance_drop)
         from .transformer import check_n_samples
         if check_n_samples(n_samples, rank_by, rank_len_penalty)[0] > 1:
             raise ValueError('n_samples=%d: %s decodes with an LSTM decoder, whose step has its own decision launch; several '
@@ -203,7 +217,8 @@ class TransformerGloveModel(CaptionModel):
                  vocab_size=50264, model_name='roberta-base', namespace='bpe', index='roberta', padding_value=1,
                  use_context=True, sampling_topk=1, sampling_temp=1.0, initializer=None, resnet=None, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False,
+                 guidance_scale=1.0, guidance_drop=('image',)):
         Model.__init__(self, vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -223,6 +238,8 @@ class TransformerGloveModel(CaptionModel):
         self.suppress_tokens, self.ground_names = check_mask_keys(suppress_tokens, ground_names)
         self._check_mask_options()
         self._check_grounding()
+        self.guidance_scale, self.guidance_drop = check_guidance(guidance_scale, guidance_drop)
+        self._check_guidance()
         self.weigh_bert = False
         self.max_caption_len = 1 << 30
         self.n_batches = self.n_samples = 0
@@ -254,18 +271,22 @@ class TransformerGloveModel(CaptionModel):
         out = {'loss': loss, 'sample_size': sample_size.reshape(())}
         if not self.training and self.evaluate_mode:
             vm = self._glove_mask(caption)
-            _, gen_ids, _ = self._generate(caption_ids, contexts, **({'vmask': vm} if vm is not None else {}))
+            guide = self._check_guidance()
+            _, gen_ids, _ = self._generate(caption_ids, contexts, **({'vmask': vm} if vm is not None else {}),
+                                           **({'guide': guide} if guide is not None else {}))
             out['gen_ids'] = gen_ids.cpu().numpy()
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
         return out
 
     def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1,
-                 prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
+                 prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None,
+                 guidance_drop=None):
         if attention:
             self._check_attention(beam_size)
         self._check_grounding(ground)
         vm = self._glove_mask(caption, banned, attention)
+        guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
         self._check_options(beam_size, attention, n_best)
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
@@ -275,7 +296,8 @@ class TransformerGloveModel(CaptionModel):
                                                    **({'n_best': n_best} if n_best != 1 else {}),
                                                    **({'prefix': pfx} if pfx is not None else {}),
                                                    **({'samples': ns} if ns is not None else {}),
-                                                   **({'vmask': vm} if vm is not None else {}))
+                                                   **({'vmask': vm} if vm is not None else {}),
+                                                   **({'guide': guide} if guide is not None else {}))
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
             out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)

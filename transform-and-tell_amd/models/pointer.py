@@ -54,7 +54,8 @@ class PointerModelBase(CaptionModel):
                  padding_value=1, use_context=True, sampling_topk=1, sampling_temp=1.0, weigh_bert=False,
                  model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
-                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False):
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False,
+                 guidance_scale=1.0, guidance_drop=('image',)):
         if sampling_topk != 1 and sampling_topp is None and sampling_minp is None and sampling_typical is None:       # (with sampling_topp: the generated token is a nucleus draw)
             raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
         super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
@@ -63,7 +64,8 @@ class PointerModelBase(CaptionModel):
                          beam_len_penalty, no_repeat_ngram_size, min_len,   # (refused unless at their defaults: SEARCH_OPTIONS)
                          sampling_minp, sampling_typical,                   # (... and so are these: _check_truncation)
                          repetition_penalty, presence_penalty, frequency_penalty,       # (... and these: _check_penalties)
-                         suppress_tokens, ground_names)                                 # (... and these: _check_mask_options)
+                         suppress_tokens, ground_names,                                 # (... and these: _check_mask_options)
+                         guidance_scale, guidance_drop)                                 # (... and these: _check_guidance)
         if weigh_bert:
             self.bert_weight_2 = nn.Parameter(torch.rand(n_bert_layers))      # :61-62
         self.batch_history = defaultdict(float)        # summed on the device (0-d tensors); floats once get_metrics reads
@@ -172,10 +174,11 @@ class PointerModelBase(CaptionModel):
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
         if attention:
             self._check_attention(beam_size)
         self._check_mask_options(banned, ground, attention)           # (refused: the copy decision is out of scope)
+        self._check_guidance(guidance, guidance_drop)                 # (gamma != 1 refused: the copy decision is out of scope)
         if prefix is not None:
             self._check_prefix(prefix, 0)                             # (refused: the copy decision is out of scope)
         self._check_beam(beam_size)

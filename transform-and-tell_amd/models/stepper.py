@@ -72,10 +72,29 @@ class DecodeStepper:
     (tell_decode_vocab_mask, outside the captured step) - and the head's pick becomes the masked one:
     tell_adaptive_logprob_topk_masked (k = 1 for the greedy decode; with `ban`, behind tell_decode_ban_list and with its list) or,
     with sample = (k, T), tell_adaptive_logprob_sample_masked.  ('mask',) joins the signature only when set; it does not combine
-    with `pen`, with attention maps or with a truncation rule."""
+    with `pen`, with attention maps or with a truncation rule.
+
+    guide = drop (context guidance; a tuple of context names): the B rows are B / 2 conditional rows and,
+    B / 2 rows further down, their unconditional twins - contexts, K/V and masks of twice the images, the twins' dropped
+    contexts fully masked (transformer.guided_batch) - and the head's pick is the guided one:
+    tell_adaptive_logprob_topk_guided (k = 1 for the greedy decode) with pair_offset = B / 2, which writes the same candidates
+    to both rows of a pair.  gamma lives in a device float of the cache entry (h['gamma'], step.set_guidance(gamma) per caption
+    batch): the captured step reads it, so one graph serves every gamma.  ('guide', drop) joins the signature only when set;
+    it combines with nothing but beam search and its length penalty."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False, pen=None, hyp=1, mask=False):
+                 prefix=False, pen=None, hyp=1, mask=False, guide=None):
+        if guide is not None:
+            for on, what in ((sample is not None, 'sampling (sampling_topk / sampling_topp / sampling_minp / sampling_typical)'),
+                             (ban is not None, 'no_repeat_ngram_size / min_len'),
+                             (pen is not None, 'repetition_penalty / presence_penalty / frequency_penalty'),
+                             (bool(mask), 'banned / ground / suppress_tokens / ground_names (a vocabulary mask)'),
+                             (bool(prefix), 'prefix'), (int(hyp) > 1, 'n_samples'), (bool(attention), 'attention maps')):
+                if on:
+                    raise ValueError('guidance does not combine with %s: the guided pick covers the arg-max and beam decodes' % what)
+            if B % 2:
+                raise ValueError('guidance: an even number of rows (every conditional row and its twin), got %d' % B)
+        self.guide, self.gamma = (None if guide is None else tuple(guide)), None
         if int(hyp) > 1 and (topk or attention or sample is None or B % int(hyp)):
             raise ValueError('hyp = %d hypotheses per sample: a sampling step without beam search or attention maps, over a '
                              'multiple of %d rows' % (int(hyp), int(hyp)))
@@ -102,6 +121,8 @@ class DecodeStepper:
             dev = next(dec.parameters()).device
             self.h, self.state, self.ctx, self.kv = None, {}, contexts, kv
             self.seed = torch.zeros(1, dtype=torch.int32, device=dev)
+            if self.guide is not None:
+                self.gamma = torch.ones(1, dtype=torch.float32, device=dev)
             self.pfx = self._make_prefix(dev) if prefix else {}
             self.ban_src, self.pen_src = {}, {}
             self.attn = self._make_sink(kv, dev) if attention else None
@@ -114,6 +135,7 @@ class DecodeStepper:
         self.pfx, self.ban_src, self.attn = h.get('pfx', {}), h['ban_src'], h.get('attn')
         self.pen_src = h.setdefault('pen_src', {}) if self.pen is not None else {}
         self.vmask = h.get('vmask')
+        self.gamma = h.get('gamma')
         self.seed, self.cur = h['seed'], h['cur']
         self.c_cur, self.c_next = h['counter'][0:1], h['counter'][1:2]
         # where a bookkeeping launch leaves the next step's offset: the word the embedder's kernel reads (in-graph
@@ -158,6 +180,8 @@ class DecodeStepper:
             sig = sig + (('hyp', self.per_sample),)
         if self.mask:                                             # (... and every one without a vocabulary mask)
             sig = sig + (('mask',),)
+        if self.guide is not None:                                # (... and every one without guidance)
+            sig = sig + (('guide', self.guide),)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -223,6 +247,8 @@ class DecodeStepper:
             h['pfx'] = self._make_prefix(dev)
         if self.mask:
             h['vmask'] = self._make_mask(dev)
+        if self.guide is not None:
+            h['gamma'] = torch.ones(1, dtype=torch.float32, device=dev)
         return h
 
     def _fill(self, kv, contexts):
@@ -252,6 +278,12 @@ class DecodeStepper:
         pfx['tab'].fill_(self.pad)
         pfx['tab'][:, :tokens.shape[1]].copy_(tokens)
         pfx['plen'].copy_(plen.to(torch.int32))
+
+    def set_guidance(self, gamma):
+        """This caption batch's guidance scale into the device float the guided pick reads (a captured step included)."""
+        if self.guide is None:
+            raise ValueError('set_guidance: the stepper was built without guide=drop')
+        self.gamma.fill_(float(gamma))
 
     def set_mask(self, ctx_ids, cls_bits=None, deny8=None, eos=2):
         """This caption batch's vocabulary masks (one launch, tell_decode_vocab_mask: deny | (cls & ~present) without eos) into
@@ -327,6 +359,9 @@ class DecodeStepper:
         forcing table every one of them ends in the forced pick."""
         soft, pfx = self.dec.adaptive_softmax, self.pfx
         force = (pfx['tab'], pfx['plen'], None, self.per_sample, sidx, self.pad) if pfx else None
+        if self.guide is not None:                                    # row r and its twin r + B / 2: one pick for both
+            tok, lp = soft.topk(x, self.n_hyp, guide=(self.B // 2, self.gamma))
+            return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
         if self.mask:
             if self.vmask is None:
                 raise ValueError('a stepper with mask=True needs set_mask(...) before its first step')

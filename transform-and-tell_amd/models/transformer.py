@@ -161,6 +161,47 @@ def check_mask_keys(suppress_tokens=(), ground_names=False):
     return tuple(sorted(set(int(t) for t in st))), ground_names
 
 
+GUIDANCE_CONTEXTS = ('image', 'article', 'faces', 'obj')
+
+
+def check_guidance(guidance_scale=1.0, guidance_drop=('image',)):
+    """The keys of context guidance: `guidance_scale` gamma, a finite number >= 0 (1.0: off), and
+    `guidance_drop`, a non-empty list of context names out of image / article / faces / obj - the contexts the unconditional
+    pass decodes without.  -> (gamma, names in the order above)."""
+    g = guidance_scale
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not math.isfinite(g) or g < 0:
+        raise ValueError('guidance_scale must be a finite number >= 0 (got %r)' % (guidance_scale,))
+    d = (guidance_drop,) if isinstance(guidance_drop, str) else guidance_drop
+    if not isinstance(d, (list, tuple)) or not d or any(not isinstance(n, str) for n in d):
+        raise ValueError('guidance_drop must be a non-empty list of context names out of %s (got %r)'
+                         % (' / '.join(GUIDANCE_CONTEXTS), guidance_drop))
+    unknown = [n for n in d if n not in GUIDANCE_CONTEXTS]
+    if unknown:
+        raise ValueError('guidance_drop: unknown context %s (the contexts are %s)'
+                         % (' / '.join(repr(n) for n in unknown), ' / '.join(GUIDANCE_CONTEXTS)))
+    return float(g), tuple(n for n in GUIDANCE_CONTEXTS if n in d)
+
+
+def guided_batch(caption_ids, contexts, drop):
+    """The batch of a guided decode: images B .. 2B - 1 are copies of 0 .. B - 1 whose dropped contexts
+    have an all-masked key-padding mask - they attend to the bias key and the zero key only.  Contexts are [S, B, E] views of
+    [B, S, E] storage and stay that; masks are [B, S].  -> (caption_ids [2B, T], contexts)."""
+    for n in drop:
+        if n not in contexts or n + '_mask' not in contexts:
+            raise ValueError('guidance_drop: the decoder has no context %r (it has %s)'
+                             % (n, ' / '.join(k for k in contexts if not k.endswith('_mask'))))
+    out = {}
+    for k, v in contexts.items():
+        if not torch.is_tensor(v):
+            out[k] = v
+        elif k.endswith('_mask'):
+            twin = torch.ones_like(v) if k[:-5] in drop else v
+            out[k] = torch.cat([v, twin], 0)
+        else:
+            out[k] = torch.cat([v.transpose(0, 1), v.transpose(0, 1)], 0).transpose(0, 1)
+    return torch.cat([caption_ids, caption_ids], 0), out
+
+
 def check_vocab_mask(banned, ground, vocab_size, batch_size, eos=2, suppress=()):
     """generate(banned=, ground=) (DESIGN.md section 22).  banned: bool [V] or [B, V], True = the token may not be generated;
     ground: bool [V], the grounded class - its tokens may be generated only if they occur in the row's own article; `suppress`:
@@ -465,7 +506,7 @@ class CaptionModel(Model):
                  initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(),
-                 ground_names=False):
+                 ground_names=False, guidance_scale=1.0, guidance_drop=('image',)):
         super().__init__(vocab)
         self.decoder, self.criterion = decoder, criterion
         self.index, self.namespace = index, namespace
@@ -489,6 +530,8 @@ class CaptionModel(Model):
         self._check_penalties()
         self.suppress_tokens, self.ground_names = check_mask_keys(suppress_tokens, ground_names)
         self._check_mask_options()
+        self.guidance_scale, self.guidance_drop = check_guidance(guidance_scale, guidance_drop)
+        self._check_guidance()
         self.weigh_bert = weigh_bert
         if weigh_bert:
             self.bert_weight = nn.Parameter(torch.rand(n_bert_layers))      # nn.init.uniform_, :57-59
@@ -636,6 +679,52 @@ class CaptionModel(Model):
             raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); vocabulary '
                              'masks cover the cached DynamicConv generator only' % (what, type(self).__name__))
         return used
+
+    def _check_guidance(self, guidance=None, guidance_drop=None, attention=False, prefix=None, n_samples=1, banned=None,
+                        ground=None):
+        """Context guidance of one call: the arguments, or where they are None the model's
+        `guidance_scale` / `guidance_drop`, checked (check_guidance; every name a context of this decoder).  -> None for
+        gamma = 1.0 (off: the call of before), else (drop, gamma) after what guidance combines with: the arg-max and beam decodes
+        of the cached DynamicConv generator with beam_len_penalty and n_best - no sampling rule, no no_repeat_ngram_size /
+        min_len, no penalties, no vocabulary mask, no prefix, no n_samples, no attention maps, not the LSTM decoders nor the
+        copy models."""
+        gamma, drop = check_guidance(getattr(self, 'guidance_scale', 1.0) if guidance is None else guidance,
+                                     getattr(self, 'guidance_drop', ('image',)) if guidance_drop is None else guidance_drop)
+        layers = getattr(getattr(self, 'decoder', None), 'layers', None)
+        have = getattr(layers[0], 'context_names', None) if layers is not None and len(layers) else None
+        if have is not None and (gamma != 1.0 or guidance_drop is not None):   # (the default drop of a model that is off: unread)
+            for n in drop:
+                if n not in have:
+                    raise ValueError('guidance_drop: the decoder has no context %r (it has %s)' % (n, ' / '.join(have)))
+        if gamma == 1.0:
+            return None
+        what = 'guidance=%r' % gamma
+        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); context '
+                             'guidance covers the cached DynamicConv generator only' % (what, type(self).__name__))
+        if int(getattr(self, 'sampling_topk', 1)) > 1:
+            raise ValueError('%s and sampling_topk=%r do not combine: guidance covers the arg-max and beam decodes'
+                             % (what, self.sampling_topk))
+        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
+            if getattr(self, name, None) is not None:
+                raise ValueError('%s and %s=%r do not combine: guidance covers the arg-max and beam decodes'
+                                 % (what, name, getattr(self, name)))
+        for name in ('no_repeat_ngram_size', 'min_len'):
+            if getattr(self, name, 0):
+                raise ValueError('%s and %s=%r do not combine: the guided pick takes no ban list' % (what, name, getattr(self, name)))
+        if self._penalties() is not None:
+            pen = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, self._penalties(), (1.0, 0.0, 0.0)) if v != d)
+            raise ValueError('%s and %s do not combine: the guided pick takes no penalty list' % (what, pen))
+        used = self._mask_options(banned, ground)
+        if used:
+            raise ValueError('%s and %s do not combine: the guided pick takes no vocabulary mask' % (what, ' / '.join(used)))
+        if prefix is not None:
+            raise ValueError('%s and prefix do not combine: a forced token has no guided log-prob' % what)
+        if isinstance(n_samples, int) and n_samples > 1:
+            raise ValueError('%s and n_samples=%d do not combine: guidance covers the arg-max and beam decodes' % (what, n_samples))
+        if attention:
+            raise ValueError('%s and attention=True do not combine: attention maps are exported without guidance' % what)
+        return drop, gamma
 
     def name_tokens(self):
         """The grounded class of generate(ground=True): data.bpe.capitalised_tokens over the installed roberta-base vocabulary -
@@ -910,9 +999,11 @@ class CaptionModel(Model):
         if not self.training and self.evaluate_mode:                       # :92-116
             # (eval_attention: commands/evaluate.py's opt-in - the captions come with their attention maps)
             vm = self._vocab_mask(context, attention=bool(getattr(self, 'eval_attention', False)))
+            guide = self._check_guidance(attention=bool(getattr(self, 'eval_attention', False)))
             _, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=getattr(self, 'eval_beam_size', 1),
                                                **({'attention': True} if getattr(self, 'eval_attention', False) else {}),
-                                               **({'vmask': vm} if vm is not None else {}))
+                                               **({'vmask': vm} if vm is not None else {}),
+                                               **({'guide': guide} if guide is not None else {}))
             self._forward_generated(output_dict, gen_ids, attns, metadata)
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
@@ -973,8 +1064,15 @@ class CaptionModel(Model):
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        guidance = gamma / guidance_drop = names (context guidance; None: the model's `guidance_scale` /
+        `guidance_drop`): every step is decoded twice in one static batch - with all contexts, and with the contexts in
+        `guidance_drop` (out of image / article / faces / obj) fully masked - and the pick follows
+        s = lp_c + (gamma - 1) * (lp_c - lp_u), reported as the normalised log-prob s - logsumexp(s): gamma > 1 rewards the
+        tokens the dropped contexts made more likely, 0 <= gamma < 1 interpolates towards the decode without them.  Greedy and
+        beam search (with beam_len_penalty and n_best); 'log_probs' / 'scores' then hold the guided log-probs.  gamma = 1.0:
+        exactly the call of before.
         banned / ground (vocabulary masks): banned - bool [V] or [B, V] - lists tokens no caption (of
         that row) may contain; ground - bool [V], or True for `name_tokens()`, the BPE pieces that start a capitalised word -
         is a class of tokens that may be generated only if they occur in the row's own article context[index] (the class is per
@@ -1018,9 +1116,11 @@ class CaptionModel(Model):
         # (prefix=None reads nothing of the batch here: the default path is the path of before)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         vm = self._vocab_mask(context, banned, ground, attention)
+        guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
+                                                   **({'guide': guide} if guide is not None else {}),
                                                    **({'samples': ns} if ns is not None else {}),
                                                    **({'vmask': vm} if vm is not None else {}),
                                                    prefix=pfx)
@@ -1061,7 +1161,7 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1, n_samples=1,
-                       rank_by='score', rank_len_penalty=0.0, banned=None, ground=None):
+                       rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own DecodeStepper - captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
@@ -1071,10 +1171,15 @@ class CaptionModel(Model):
         BLEU bookkeeping: what commands/evaluate.py consumes) instead of `generate`'s; beam_size then is `eval_beam_size`.
         n_samples / rank_by / rank_len_penalty: as `generate` - every lane decodes the n hypotheses of its batch's images.
         banned (bool [V]) / ground (bool [V] or True): the shared forms of `generate`'s vocabulary masks, applied to every batch
-        (each row grounded in its own article)."""
+        (each row grounded in its own article).
+        guidance / guidance_drop: as `generate` - every lane decodes its batch and the batch's unconditional twin."""
         if banned is not None and (not torch.is_tensor(banned) or banned.dim() != 1):
             raise ValueError('generate_lanes takes the shared form of banned: a bool tensor [V]')
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
+        guide = self._check_guidance(guidance, guidance_drop, attention, None, n_samples, banned, ground)
+        if forward and (guidance is not None or guidance_drop is not None):   # (forward=True decodes under the model's keys)
+            raise ValueError('guidance / guidance_drop as arguments go with generate, not with forward=True')
+        gkw = {'guide': guide} if guide is not None else {}
         if attention:
             if forward:
                 raise ValueError('attention=True goes with generate, not with forward=True')
@@ -1114,6 +1219,8 @@ class CaptionModel(Model):
                 if b.get('prefix') is not None and forward:
                     raise ValueError('prefix goes with generate, not with forward=True')
                 pfx = self._check_prefix(b.get('prefix'), caption_ids.shape[0])
+                if guide is not None and pfx is not None:
+                    self._check_guidance(guidance, guidance_drop, prefix=pfx)
                 plens.append(pfx[1] if pfx is not None else None)
                 vm = self._vocab_mask(b['context'], banned, ground, attention)
                 vkw = {'vmask': vm} if vm is not None else {}
@@ -1121,10 +1228,10 @@ class CaptionModel(Model):
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx, **vkw)
+                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx, **vkw, **gkw)
                          if beam_size > 1 else
                          self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx,
-                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {}), **vkw))
+                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {}), **vkw, **gkw))
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -1203,8 +1310,15 @@ class CaptionModel(Model):
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
-                  prefix=None, samples=None, vmask=None):
+                  prefix=None, samples=None, vmask=None, guide=None):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
+        if guide is not None:                 # (drop, gamma) of _check_guidance: lives in the cached generators, like `opts`
+            self._check_guidance(guide[1], guide[0], attention, prefix, samples[0] if samples is not None else 1,
+                                 True if vmask is not None else None)
+            self._check_beam(beam_size)
+            if beam_size > 1:
+                return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, guide=guide)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, guide=guide)
         if self._check_penalties(attention) is not None:      # (the penalties live in the cached generators, like `opts`)
             opts = opts or (0.0, 0, 0)
         if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
@@ -1251,15 +1365,16 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None,
-                         samples=None, vmask=None):
+                         samples=None, vmask=None, guide=None):
         # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
                                               **({'prefix': prefix} if prefix is not None else {}),
                                               **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {}),
-                                              **({'vmask': vmask} if vmask is not None else {})))
+                                              **({'vmask': vmask} if vmask is not None else {}),
+                                              **({'guide': guide} if guide is not None else {})))
 
     def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
-                      prefix=None, n=1, rank=('score', 0.0), vmask=None):
+                      prefix=None, n=1, rank=('score', 0.0), vmask=None, guide=None):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -1282,9 +1397,16 @@ class CaptionModel(Model):
         (tell_sample_rank, rank = (rule, alpha)) scores, de-duplicates and ranks the n hypotheses of every image: the results
         are the first rank's, the third a DecodeInfo with .scores and .samples.
         vmask = (ctx_ids, cls_bits, deny8) of _vocab_mask: the stepper's bitmap - one row per image - is built before the first
-        step (step.set_mask) and every pick is the masked one; the bookkeeping is untouched."""
+        step (step.set_mask) and every pick is the masked one; the bookkeeping is untouched.
+        guide = (drop, gamma) of _check_guidance: the batch is decoded with its unconditional twin behind
+        it (guided_batch: 2 * images rows), every pick is the guided arg-max - one token and one normalised log-prob for both
+        rows of a pair - the bookkeeping runs over all rows unchanged and the results are the first half."""
         dec = self.decoder
         n = int(n)
+        if guide is not None:
+            self._check_guidance(guide[1], guide[0], attention, prefix, n, True if vmask is not None else None)
+            cond = caption_ids.shape[0]
+            caption_ids, contexts = guided_batch(caption_ids, contexts, guide[0])
         images = caption_ids.shape[0]
         B = images * n                                           # decode rows
         dev = caption_ids.device
@@ -1296,7 +1418,10 @@ class CaptionModel(Model):
         pen = self._check_penalties(attention)
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
                                     prefix=prefix is not None, **({'pen': pen} if pen is not None else {}),
-                                    **({'hyp': n} if n > 1 else {}), **({'mask': True} if vmask is not None else {}))
+                                    **({'hyp': n} if n > 1 else {}), **({'mask': True} if vmask is not None else {}),
+                                    **({'guide': guide[0]} if guide is not None else {}))
+        if guide is not None:
+            step.set_guidance(guide[1])
         if prefix is not None:
             step.set_prefix(*prefix)
         if vmask is not None:
@@ -1366,6 +1491,8 @@ class CaptionModel(Model):
             bufs = step.attn.bufs
             attns = AttnMaps({n: torch.stack([lb[n][:steps] for lb in bufs], 0).permute(2, 1, 0, 3).contiguous()
                               for n in bufs[0]}, done_step.clamp(max=steps).clone())
+        if guide is not None:                                                 # (the unconditional twins took the same decisions)
+            return lps[:cond, :steps].clone(), ids[:cond, :steps + 1].clone(), attns
         if fused:                                                             # (the static buffers belong to the stepper)
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
         return lps[:, :steps], ids[:, :steps + 1], attns
@@ -1395,21 +1522,22 @@ class CaptionModel(Model):
         return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None, hyp=1, mask=False):
+                        prefix=False, pen=None, hyp=1, mask=False, guide=None):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
                              opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}),
-                             **({'mask': True} if mask else {}))
+                             **({'mask': True} if mask else {}), **({'guide': guide} if guide is not None else {}))
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
-                       vmask=None):
+                       vmask=None, guide=None):
         return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best, prefix=prefix,
-                                            **({'vmask': vmask} if vmask is not None else {})))
+                                            **({'vmask': vmask} if vmask is not None else {}),
+                                            **({'guide': guide} if guide is not None else {})))
 
     def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
-                    vmask=None):
+                    vmask=None, guide=None):
         """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
         only samples top-1, transformer_faces_objects.py:443-464).  B*K rows (row = b*K + j) stay resident; the
         projected K/V of the static contexts are computed once per caption and replicated per beam; the DynamicConv
@@ -1426,8 +1554,15 @@ class CaptionModel(Model):
         With penalties set (_penalties()): every hypothesis' K best are taken over its penalised scores (step.pen_source over
         `seqs`), and `cum`, the log_probs and the scores accumulate those scores.
         vmask = (ctx_ids, cls_bits, deny8) of _vocab_mask: the K hypotheses of a sample share its row of the stepper's bitmap
-        (step.set_mask) and every hypothesis' K best are taken under it - with a ban list, in the same launch."""
+        (step.set_mask) and every hypothesis' K best are taken under it - with a ban list, in the same launch.
+        guide = (drop, gamma) of _check_guidance: samples B .. 2B - 1 are the unconditional twins
+        (guided_batch), hypothesis row r's partner is row r + B * K; every pair's K candidates come from the guided pick and are
+        the same for both rows, so tell_beam_update takes the same decisions in both halves; the results are the first half."""
         dec = self.decoder
+        if guide is not None:
+            self._check_guidance(guide[1], guide[0], False, prefix, 1, True if vmask is not None else None)
+            cond = caption_ids.shape[0]
+            caption_ids, contexts = guided_batch(caption_ids, contexts, guide[0])
         B, K = caption_ids.shape[0], int(beam_size)
         dev = caption_ids.device
         pad = self.padding_idx
@@ -1442,7 +1577,10 @@ class CaptionModel(Model):
         pen = self._check_penalties()
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
                                     opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None,
-                                    **({'pen': pen} if pen is not None else {}), **({'mask': True} if vmask is not None else {}))
+                                    **({'pen': pen} if pen is not None else {}), **({'mask': True} if vmask is not None else {}),
+                                    **({'guide': guide[0]} if guide is not None else {}))
+        if guide is not None:
+            step.set_guidance(guide[1])
         if prefix is not None:
             step.set_prefix(*prefix)
         if vmask is not None:
@@ -1559,6 +1697,8 @@ class CaptionModel(Model):
         steps = max(min(steps, n_steps), 1)
         info = DecodeInfo()
         scores = cum * inv_norm[hyp_len.long()] if alpha else cum      # (the multiply the ranking used)
+        if guide is not None:                                # (the unconditional twins took the same decisions)
+            seqs, lps, scores, best = seqs[:cond], lps[:cond], scores[:cond], best[:cond]
         info.scores = scores[:, 0].clone()
         if n_best > 1:
             info.nbest = (seqs[:, :n_best, :steps + 1].clone(), lps[:, :n_best, :steps].clone(), scores[:, :n_best].clone())

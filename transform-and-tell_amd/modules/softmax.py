@@ -74,7 +74,7 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k, ban=None, force=None, pen=None, mask=None):
+    def topk(self, X, k, ban=None, force=None, pen=None, mask=None, guide=None):
         """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
         ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
         (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans).
@@ -82,11 +82,16 @@ class AdaptiveSoftmax(nn.Module):
         scores s = min(lp, 0) * theta - sub[count] of the listed tokens, lp of every other (DESIGN.md section 20,
         tell_adaptive_logprob_topk_penalised); the second result then holds scores, not log-probs.
         mask = (bits int32 [B * T / per, words], per): position r never lists a token whose bit is set in bits[r // per]; every
-        log-prob is the unmasked one (tell_adaptive_logprob_topk_masked; a ban list may join it)."""
+        log-prob is the unmasked one (tell_adaptive_logprob_topk_masked; a ban list may join it).
+        guide = (pair_offset, gamma fp32 [1] on the device): position r < pair_offset and its partner r + pair_offset get the
+        same k candidates, ranked by s = lp_c + (gamma - 1) * (lp_c - lp_u) and reported as s - logsumexp(s) (DESIGN.md section 24,
+        tell_adaptive_logprob_topk_guided); on its own - no ban list, penalties, mask or forcing table."""
         B, T, E = X.shape
         kw = {'pen': pen} if pen is not None else {}
         if mask is not None:
             kw['mask'] = mask
+        if guide is not None:
+            kw['guide'] = guide
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
                                             self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force, **kw)
         return tok.view(B, T, k), lp.view(B, T, k)

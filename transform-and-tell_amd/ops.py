@@ -1857,13 +1857,24 @@ def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None,
     return token, token_lp, None
 
 
-def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None, mask=None):
+def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None, mask=None, guide=None):
     """The top-k head's last launch: tell_adaptive_logprob_topk, or - ban = (ban int32 [N, ld_ban], n_ban int32 [N]) -
     tell_adaptive_logprob_topk_banned, or - pen (see _pen_args) - tell_adaptive_logprob_topk_penalised, whose second result
     holds the penalised scores, or - mask (see _mask_args), with or without a ban list - tell_adaptive_logprob_topk_masked.
+    guide = (pair_offset, gamma fp32 [1] on the device) - tell_adaptive_logprob_topk_guided: rows 0 .. N - pair_offset - 1 are
+    conditional, row r's partner is r + pair_offset, both get the pair's k guided candidates.
     -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
     tokens = torch.empty(N, k, dtype=torch.int32, device=head.device)
     lps = torch.empty(N, k, dtype=torch.float32, device=head.device)
+    if guide is not None:
+        off, gamma = int(guide[0]), guide[1]
+        if ban is not None or pen is not None or mask is not None:
+            raise ValueError('logprob_topk: guidance does not combine with a ban list, penalties or a vocabulary mask')
+        if 2 * off != N or gamma.dtype != torch.float32 or gamma.numel() != 1 or gamma.device != head.device:
+            raise ValueError('logprob_topk: guide = (pair_offset = %d / 2, gamma fp32 [1] on the device) expected' % N)
+        call('tell_adaptive_logprob_topk_guided', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
+             lds[2], ns[2], N - off, off, int(k), gamma, None, 0, tokens, lps)
+        return tokens, lps, None
     if mask is not None:
         if pen is not None:
             raise ValueError('logprob_topk: a vocabulary mask and penalties do not combine')
@@ -1911,7 +1922,7 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
 
 
 def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None,
-                       pen=None, mask=None):
+                       pen=None, mask=None, guide=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
@@ -1925,6 +1936,10 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
         raise ValueError('adaptive_log_probs: a vocabulary mask goes with topk = k >= 1 or a top-k draw')
     if force is not None and want_full:
         raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
+    if guide is not None and (want_full or not topk or sample is not None or ban is not None or force is not None or
+                              pen is not None or mask is not None):
+        raise ValueError('adaptive_log_probs: guidance goes with topk = k >= 1 alone (no draw, ban list, forcing table, '
+                         'penalties or vocabulary mask)')
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
@@ -1934,6 +1949,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
+        if guide is not None:    # (a call without guidance is the call it was: stand-ins for head_step keep working)
+            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, guide=guide)
         if mask is not None:     # (a call without a mask is the call it was: stand-ins for head_step keep working)
             return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask)
         if pen is not None:      # (a call without penalties is the call it was: stand-ins for head_step keep working)
@@ -1960,7 +1977,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
                                      **({'mask': mask} if mask is not None else {})))
     if topk:
         return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban, pen=pen,
-                                   **({'mask': mask} if mask is not None else {})))
+                                   **({'mask': mask} if mask is not None else {}),
+                                   **({'guide': guide} if guide is not None else {})))
     if ban is not None:
         raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
     full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
