@@ -128,7 +128,9 @@ int tell_gemm_nt_dropout_residual(const void* A, long lda, const void* B, long l
  * softmax.py:24-40,182-189 (head / tail projections), adaptive.py:73 (band
  * projections) and the convolutions of resnet.py:92-108 (NHWC rows).
  * bias_mode 0 none | 1 bias[n] | 2 bias[m];  act 0 none | 1 relu | 2 gelu(erf) |
- * 3 multiply by (aux[m,n] > 0) (relu backward) | 4 relu(result + aux[m,n]) (residual block);  m_dev: optional device row count. */
+ * 3 multiply by (aux[m,n] > 0) (relu backward) | 4 relu(result + aux[m,n]) (residual block);  m_dev: optional device row count.
+ * aux has the type of C and the ROW STRIDE of C: aux[m,n] is read at aux + m * ldc + n (there is no stride argument of
+ * its own), so an aux next to a strided C must be laid out with the same ldc. */
 int tell_gemm_nt(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                  int in_dtype, int out_dtype, const float* bias, int bias_mode, int act, const void* aux,
                  float alpha, int accumulate, const int* m_dev, tell_stream_t stream);

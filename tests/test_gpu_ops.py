@@ -236,7 +236,9 @@ def test_gemm_dropout_residual_epilogue(M, N, K, p):
                          ids=['pp', 'pp2-multi-round', 'pp2-tile-queue', 'pp2-static'])
 def test_gemm_kernel_variants_behind_switches(env):
     """The GEMM kernels that are not the default choice (the ping-pong family: fallback for K % 128 != 0)
-    stay correct: the switches are read once per process, so each runs tools/probes/gemm_variant_check.py in its own."""
+    stay correct: each runs tools/probes/gemm_variant_check.py in a process of its own, which takes the switches from
+    TELL_<KEY> when the library is loaded.  (The library reads its options per launch: tests/test_gpu_gemm.py switches
+    kernels inside one process and asserts the plan label each time.)"""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     e = dict(os.environ); e.update(env)

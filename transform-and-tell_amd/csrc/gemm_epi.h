@@ -211,6 +211,18 @@ __device__ __forceinline__ void glds_store_tile_act(f32x16 (&acc)[MI][NI], const
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     const int row = LAY ? (i >> 1) * (BM / 2) + wm * 64 + (i & 1) * 32 + (lane & 31) : wm * WM + i * 32 + (lane & 31);
+    // act 4: the residual joins the fp32 value BEFORE the one rounding to bf16, as in gemm_epilogue_act (the edge tiles
+    // of the same output).  Added to the staged bf16 tile it made interior tiles round twice: one bf16 ulp off the edge
+    // tiles' function in one element of nine.  One batch of 8-byte loads per 32-row block, in front of their use.
+    u32x2 ax[NI][4];
+    if constexpr (ACT == 4) {
+      const uint16_t* arow = static_cast<const uint16_t*>(p.aux) + (long)(m0 + row) * p.ldc + n0;
+#pragma unroll
+      for (int j = 0; j < NI; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          ax[j][g] = *reinterpret_cast<const u32x2*>(arow + (LAY ? j * (BN / 2) + wn * 32 : wn * WN + j * 32) + 8 * g + 4 * (lane >> 5));
+    }
 #pragma unroll
     for (int j = 0; j < NI; ++j)
 #pragma unroll
@@ -220,6 +232,12 @@ __device__ __forceinline__ void glds_store_tile_act(f32x16 (&acc)[MI][NI], const
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (acc[i][j][4 * g + e] + b4[j][g][e] + bmr[i]) * p.alpha;
         epi_act4<(ACT == 4 || ACT == 3) ? 0 : ACT>(v);
+        if constexpr (ACT == 4) {
+          v[0] = fmaxf(v[0] + __uint_as_float(ax[j][g][0] << 16), 0.f);
+          v[1] = fmaxf(v[1] + __uint_as_float(ax[j][g][0] & 0xffff0000u), 0.f);
+          v[2] = fmaxf(v[2] + __uint_as_float(ax[j][g][1] << 16), 0.f);
+          v[3] = fmaxf(v[3] + __uint_as_float(ax[j][g][1] & 0xffff0000u), 0.f);
+        }
         int ch = col >> 3;
         if constexpr (SWZ) ch ^= row & (CPRW - 1) & 15;
         u32x2 w = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
@@ -241,15 +259,6 @@ __device__ __forceinline__ void glds_store_tile_act(f32x16 (&acc)[MI][NI], const
         const uint32_t lo = ((r[e] & 0x8000u) == 0 && (r[e] & 0x7fffu) != 0) ? 0x0000ffffu : 0u;
         const uint32_t hi = ((r[e] & 0x80000000u) == 0 && (r[e] & 0x7fff0000u) != 0) ? 0xffff0000u : 0u;
         o[e] &= lo | hi;
-      }
-    }
-    if constexpr (ACT == 4) {                          // relu(tile + residual): the residual arrives as whole 16-byte pieces too
-      const u32x4 r = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(p.aux) + (long)(m0 + row) * p.ldc + n0 + ch * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = fmaxf(__uint_as_float(o[e] << 16) + __uint_as_float(r[e] << 16), 0.f);
-        const float hi = fmaxf(__uint_as_float(o[e] & 0xffff0000u) + __uint_as_float(r[e] & 0xffff0000u), 0.f);
-        o[e] = pack2_bf16(lo, hi);
       }
     }
     *reinterpret_cast<u32x4*>(C + (long)(m0 + row) * p.ldc + n0 + ch * 8) = o;

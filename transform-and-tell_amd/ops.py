@@ -113,6 +113,19 @@ def wgrad_target(p, rows=None):
     return (gw2 if rows is None else gw2[rows[0]:rows[1]]), not grad_stored(p)
 
 
+def _aux_like(aux, out):
+    """The GEMM epilogues read aux[m, n] (act 3 / 4) at m * ldc + n, in the output's type: an aux whose rows are laid out
+    differently from `out` is copied into that layout instead of being indexed wrongly."""
+    if aux is None:
+        return None
+    assert aux.dtype == out.dtype and aux.shape == out.shape, (aux.dtype, out.dtype, aux.shape, out.shape)
+    if aux.stride(1) == 1 and (aux.stride(0) == out.stride(0) or out.shape[0] == 1):
+        return aux
+    same = torch.empty(out.shape[0], out.stride(0), dtype=out.dtype, device=out.device)[:, :out.shape[1]]
+    same.copy_(aux)
+    return same
+
+
 def gemm(a, b, out=None, out_dtype=None, bias=None, bias_mode=0, act=0, aux=None, alpha=1.0,
          accumulate=False, m_dev=None):
     """out[M,N] = act((a[M,K] @ b[N,K]^T + bias) * alpha) (+ out).  K is zero padded to a
@@ -134,6 +147,7 @@ def gemm(a, b, out=None, out_dtype=None, bias=None, bias_mode=0, act=0, aux=None
     if out is None:
         out = torch.empty(M, N, dtype=out_dtype or a.dtype, device=a.device)
     assert out.stride(1) == 1
+    aux = _aux_like(aux, out)
     K = a.shape[1]
     if (_SPLITK and M <= 128 and K >= 2048 and K % 512 == 0 and N % 64 == 0 and a.dtype == torch.bfloat16 and
             bias_mode in (0, 1) and act in (0, 1, 2) and aux is None and not accumulate and m_dev is None and
@@ -319,7 +333,7 @@ def gemm_nn(a, b_kn, b_t=None, out=None, out_dtype=None, alpha=1.0, act=0, aux=N
         if out is None:
             out = torch.empty(M, N, dtype=out_dtype or a.dtype, device=a.device)
         call('tell_gemm_bf16', a, a.stride(0), 0, b_kn, b_kn.stride(0), 1, out, out.stride(0), M, N, K,
-             hip.dt(out), None, 0, act, aux, float(alpha), int(accumulate), m_dev, None, 0.0)
+             hip.dt(out), None, 0, act, _aux_like(aux, out), float(alpha), int(accumulate), m_dev, None, 0.0)
         return out
     bt = b_t() if b_t is not None else transpose(b_kn)[0]
     if bt.shape[1] != a.shape[1]:                       # bring both to one (zero padded) K width
