@@ -914,7 +914,11 @@ int tell_entity_head_bwd(const float* dloss, const float* nvalid, const float* l
 /* Causal entity attention (self_attention.py, downsampled_single_head.py _mask_future_full + scalar_bias.py): query i
  * at position pos0 + i sees keys s < pos0 + i, plus a slot of logit 0 and value 0; no dropout; logits are
  * scale * q.k (q unscaled, dq likewise).  Layout as
- * tell_attn_fwd; D = 64; lse [B,H,Tq].  pos0 = S - 1, Tq = 1 is the generation step over a K/V history of S rows. */
+ * tell_attn_fwd; D = 64; lse [B,H,Tq].  pos0 = S - 1, Tq = 1 is the generation step over a K/V history of S rows.
+ * k and v hold S rows and no row >= S is read: a query with pos0 + i > S sees all S keys (min(pos0 + i, S)), a query
+ * with pos0 + i = 0 sees the zero slot alone (out = 0, lse = 0 exactly).  Every entry point of this section returns a
+ * negative code and launches nothing when it declines its arguments (D, S <= 512, p in [0,1), bias_k, dtype, variant,
+ * a full history); tell_copy_step with Ba = 0 returns 0 and launches nothing. */
 int tell_causal_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int H, int Tq,
                          int S, int D, int pos0, long q_st, long q_sb, long k_ss, long k_sb, long v_ss, long v_sb,
                          long o_st, long o_sb, float scale, int dtype, tell_stream_t stream);

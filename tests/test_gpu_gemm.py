@@ -9,13 +9,12 @@ import pytest
 import torch
 
 import gemm_ref as ref
+from guarded import DEV, SENTINEL, Vec, View          # the guarded views, shared with tests/test_gpu_copy.py
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 F32, BF16 = torch.float32, torch.bfloat16
-SENTINEL = ref.SENTINEL
-PAD = 64                     # elements on each side of a view: keeps the view's 16-byte alignment
+assert SENTINEL == ref.SENTINEL
 
 _GELU = {}
 
@@ -49,37 +48,6 @@ def n_cu():
 
 def r8(n):
     return (n + 7) // 8 * 8
-
-
-class View:
-    """[rows, cols] with row stride ld >= cols inside an allocation filled with SENTINEL (also the columns cols..ld-1 of
-    every row); off: extra elements in front (off = 1 takes a bf16 view 2 bytes off its 8-byte alignment)"""
-
-    def __init__(self, rows, cols, ld, dtype, off=0, fill=None):
-        assert ld >= cols
-        self.rows, self.cols, self.ld, self.lo = rows, cols, ld, PAD + off
-        self.buf = torch.full((self.lo + rows * ld + PAD,), SENTINEL, dtype=dtype, device=DEV)
-        self.t = torch.as_strided(self.buf, (rows, cols), (ld, 1), self.lo)
-        if fill is not None:
-            self.t.copy_(fill)
-
-    def intact(self):
-        gap = torch.as_strided(self.buf, (self.rows, self.ld - self.cols), (self.ld, 1), self.lo + self.cols)
-        return bool((self.buf[:self.lo] == SENTINEL).all()) and bool((gap == SENTINEL).all()) and \
-            bool((self.buf[self.lo + self.rows * self.ld:] == SENTINEL).all())
-
-
-class Vec:
-    """a guarded fp32 vector"""
-
-    def __init__(self, fill):
-        self.n = fill.numel()
-        self.buf = torch.full((self.n + 2 * PAD,), SENTINEL, dtype=F32, device=DEV)
-        self.t = self.buf[PAD:PAD + self.n]
-        self.t.copy_(fill)
-
-    def intact(self):
-        return bool((self.buf[:PAD] == SENTINEL).all()) and bool((self.buf[PAD + self.n:] == SENTINEL).all())
 
 
 def exact(got, want, tag):
