@@ -938,6 +938,34 @@ int tell_copy_step(const void* q, long q_sb, const void* k, long k_ss, long k_sb
                    const float* entity_logits, const long* gen_tok, long* hist, int hist_len, int n_hist, int Ba, int H,
                    int S, int D, long* tok, uint8_t* copied, float* prob, int dtype, tell_stream_t stream);
 
+/* ---- copy mechanism, cached generation (csrc/copy_decode.hip): the tail of a decode step of the copy
+ * models over a batch that keeps its shape.  Both entry points take the step as `step, step_dev`: the step index p is
+ * *step_dev + 1 when step_dev is given (the launch is part of a captured step, as in tell_greedy_update), else `step`.  They
+ * return a negative code and launch nothing when they decline their arguments, synchronise nothing and allocate nothing.
+ *
+ * The one-query causal entity attention of step p over a STATIC history: q, k_new, v_new [B, H*64] (row strides q_sb, kn_sb,
+ * vn_sb) are this step's projections (q unscaled, logits scale * q.k); k_hist, v_hist [L, B, H*64] (strides h_ss, h_sb; the
+ * model dtype).  Row p of both histories is written from k_new / v_new bit for bit, the query sees rows 0 .. p-1 plus a slot
+ * of logit 0 and value 0: out [B, H*64] (row stride o_sb) = tell_causal_attn_fwd(Tq = 1, pos0 = p, S = p), exactly 0 at
+ * p = 0.  D = 64.  Host path: 0 <= step < L or the call is declined; device path: p >= L attends to all L rows and writes no
+ * history row. */
+int tell_entity_attn_step(const void* q, long q_sb, const void* k_new, long kn_sb, const void* v_new, long vn_sb,
+                          void* k_hist, void* v_hist, long h_ss, long h_sb, void* out, long o_sb, int B, int H, int D,
+                          int L, float scale, int step, const int* step_dev, int dtype, tell_stream_t stream);
+/* tell_copy_step for a static batch: row r is batch row r (no row map); a row with finished[r] != 0 (uint8 [B], optional)
+ * reads and writes nothing.  q [B,H*D] (row stride q_sb, scaled); k [S,B,H*D] by strides as in tell_copy_step; bias_k, mask,
+ * proper, ctx_ids as there; entity_logits [B,2]; gen_tok int32 [B] (the head's pick).  The rules are tell_copy_step's, the
+ * history check runs over hist[r, 0 .. p].  Unfinished rows get tok[r] (int32: the copied id or gen_tok[r] - what
+ * tell_greedy_update takes), hist[r, p + 1] (int32 [B, ld_hist >= L + 1]: the copied id, else -1), copied[r, p + 1] (uint8
+ * [B, ld_copied >= L + 1]) and prob[r, p] (fp32 [B, ld_prob >= L]).  Two launches: the per-head probabilities of every
+ * (row, head) into scratch (fp32 [B, H, S]), then one workgroup per row.  S <= 512, D <= 64, bias_k required.  Host path:
+ * 0 <= step < L or the call is declined; device path: p >= L writes nothing. */
+int tell_copy_decide(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k,
+                     const uint8_t* mask, const int8_t* proper, const long* ctx_ids, const float* entity_logits,
+                     const int* gen_tok, const uint8_t* finished, int* hist, long ld_hist, uint8_t* copied,
+                     long ld_copied, float* prob, long ld_prob, int L, int step, const int* step_dev, int B, int H, int S,
+                     int D, float* scratch, int* tok, int dtype, tell_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

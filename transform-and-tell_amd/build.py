@@ -46,7 +46,7 @@ def build_decoder(kind='faces_objects', vocab_size=50265, dim=1024, heads=16, ff
 def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=25, sampling_topk=1, sampling_temp=1.0,
                 sampling_topp=None, beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None,
                 sampling_typical=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(),
-                ground_names=False, guidance_scale=1.0, guidance_drop=('image',), **decoder_kw):
+                ground_names=False, guidance_scale=1.0, guidance_drop=('image',), cached_generation=False, **decoder_kw):
     search = dict(beam_len_penalty=beam_len_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_len=min_len,
                   sampling_minp=sampling_minp, sampling_typical=sampling_typical, repetition_penalty=repetition_penalty,
                   presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
@@ -58,10 +58,15 @@ def build_model(kind, resnet=None, roberta=None, weigh_bert=True, n_bert_layers=
         from .models.pointer import TransformerPointer2Model, TransformerPointerModel
         dec = build_decoder('faces_parallel', **decoder_kw)
         cls = TransformerPointerModel if kind == 'pointer' else TransformerPointer2Model
+        if cached_generation:                                 # (the default adds nothing to the constructor call)
+            search.update(cached_generation=True)
         return cls(None, dec, AdaptiveLoss(padding_idx=1), weigh_bert=weigh_bert,
                    vocab_size=decoder_kw.get('vocab_size', 50265), resnet=resnet, roberta=roberta,
                    n_bert_layers=n_bert_layers, sampling_topk=sampling_topk, sampling_temp=sampling_temp,
                    sampling_topp=sampling_topp, **search)
+    if cached_generation:
+        raise ValueError('cached_generation is a key of the copy models (pointer, pointer_2): the plain caption models always '
+                         'generate through the cached step')
     dec = build_decoder(kind, **decoder_kw)
     cls = {'faces_objects': TransformerFacesObjectModel, 'faces': TransformerFacesModel,
            'faces_parallel': TransformerFacesModel}.get(kind, TransformerFlattenedModel)

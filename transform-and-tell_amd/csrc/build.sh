@@ -8,7 +8,7 @@
 set -e
 cd "$(dirname "$0")"
 if [ -n "$PROBES" ]; then OBJ=_obj_probes; DEF="-DTELL_PROBES"; OUT=${1:-libtell_hip_probes.so}; else OBJ=_obj; DEF=""; OUT=${1:-libtell_hip.so}; fi
-SRCS="api gemm gemm_pp2 gemm_q4 gemm_q4e gemm_s64 elementwise layernorm dynconv attention adaptive guidance optim conv encoders lstm multi decode copy"
+SRCS="api gemm gemm_pp2 gemm_q4 gemm_q4e gemm_s64 elementwise layernorm dynconv attention adaptive guidance optim conv encoders lstm multi decode copy copy_decode"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-unused-value $DEF"
 mkdir -p $OBJ
 pids=""

@@ -10,7 +10,8 @@ is entity_loss + copy_loss in bits; gen_loss is computed and logged only.
 
 Generation (_generate :427-696) is greedy: per step the decoder's token, the entity decision over the step's output
 and its history, and one copy-decision launch (csrc/copy.hip tell_copy_step) with the article keys projected once
-per batch."""
+per batch.  With `cached_generation` / `generate(cached=True)` the same decode runs through the cached, captured step of the
+plain models (_pointer_steps; csrc/copy_decode.hip tell_entity_attn_step and tell_copy_decide)."""
 import logging
 import math
 from collections import defaultdict
@@ -55,7 +56,7 @@ class PointerModelBase(CaptionModel):
                  model_path=None, initializer=None, resnet=None, roberta=None, n_bert_layers=25, sampling_topp=None,
                  beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, sampling_minp=None, sampling_typical=None,
                  repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, suppress_tokens=(), ground_names=False,
-                 guidance_scale=1.0, guidance_drop=('image',)):
+                 guidance_scale=1.0, guidance_drop=('image',), cached_generation=False):
         if sampling_topk != 1 and sampling_topp is None and sampling_minp is None and sampling_typical is None:       # (with sampling_topp: the generated token is a nucleus draw)
             raise ValueError('transformer_pointer generates greedily: sampling_topk must be 1 (got %r)' % (sampling_topk,))
         super().__init__(vocab, decoder, criterion, evaluate_mode, attention_dim, hidden_size, dropout, vocab_size,
@@ -87,6 +88,8 @@ class PointerModelBase(CaptionModel):
                 p.requires_grad_(False)
         self.vocab_size = vocab_size
         self.copy_heads = 16
+        # generate() / forward() in evaluate mode decode through the cached, captured step (_pointer_steps)
+        self.cached_generation = bool(cached_generation)
         if model_path is not None:
             logger.info('Recovering weights from %s.', model_path)
             load_state_dict_with_prefix(self, torch.load(model_path, map_location='cpu'))
@@ -148,7 +151,8 @@ class PointerModelBase(CaptionModel):
             self.batch_history[key] = self.batch_history[key] + torch.where(torch.isnan(v), torch.zeros_like(v), v)
         output_dict = {'loss': loss, 'sample_size': sample_size.reshape(())}
         if not self.training and self.evaluate_mode:
-            gen_ids, _, should_copy, _ = self._generate_pointer(caption_ids, contexts, enc, context)
+            decode = self._generate_pointer_cached if self.cached_generation else self._generate_pointer
+            gen_ids, _, should_copy, _ = decode(caption_ids, contexts, enc, context)
             self._forward_generated(output_dict, gen_ids, [], metadata)
             ids = gen_ids.cpu()
             output_dict['copied_texts'] = [self.detokenize(x[should_copy[i].cpu()]) for i, x in enumerate(ids)]
@@ -174,7 +178,10 @@ class PointerModelBase(CaptionModel):
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None, cached=None):
+        """cached (None: the model's `cached_generation` key): the same greedy / nucleus decode through the cached generator -
+        projected context K/V, a batch that keeps its shape, one captured step per token (_pointer_steps).  Everything refused
+        below is refused on both paths."""
         if attention:
             self._check_attention(beam_size)
         self._check_mask_options(banned, ground, attention)           # (refused: the copy decision is out of scope)
@@ -187,7 +194,9 @@ class PointerModelBase(CaptionModel):
         self._require_masks(context)
         enc = encoded if encoded is not None else self.encode(context, image)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, None, enc)
-        gen_ids, log_probs, should_copy, copy_probs = self._generate_pointer(caption_ids, contexts, enc, context)
+        use_cached = self.cached_generation if cached is None else bool(cached)
+        decode = self._generate_pointer_cached if use_cached else self._generate_pointer
+        gen_ids, log_probs, should_copy, copy_probs = decode(caption_ids, contexts, enc, context)
         ids = gen_ids.cpu()
         return {'gen_ids': gen_ids, 'log_probs': log_probs, 'should_copy': should_copy, 'copy_probs': copy_probs,
                 'generations': [self.detokenize(x[x > 1]) for x in ids],
@@ -262,6 +271,108 @@ class PointerModelBase(CaptionModel):
             if int(keep.sum()) == 0:
                 break
         return torch.cat(paths, -1), torch.cat(log_probs, -1), torch.cat(copies, -1), torch.cat(probs, -1)
+
+    @torch.no_grad()
+    def _generate_pointer_cached(self, caption_ids, contexts, enc, context, gen_len=100, eos=2, check_every=8):
+        return self._drive(self._pointer_steps(caption_ids, contexts, enc, context, gen_len, eos, check_every))
+
+    def _pointer_steps(self, caption_ids, contexts, enc, context, gen_len=100, eos=2, check_every=8):
+        """_generate_pointer on the cached generator - a generator in the style of _greedy_steps (one `yield` per issued step or
+        multi-step replay), same results.  The context K/V are projected once, the batch keeps its shape (finished rows are
+        masked, never compacted), the entity K/V history and the copy bookkeeping are static buffers, and the step's tail -
+        entity projections, tell_entity_attn_step, out_proj + LayerNorm, entity_fc, the copy query, tell_copy_decide and the
+        unchanged tell_greedy_update - is the stepper's `post`: part of the captured single-step and multi-step graphs, with the
+        step index from the device counter.  One host synchronisation per `check_every` steps and one at the end.  When the
+        stepper is not static (graphs disabled) the same launches run one by one over buffers of this call."""
+        dec = self.decoder
+        B = caption_ids.shape[0]
+        dev = caption_ids.device
+        E = self.in_proj_weight.shape[1]
+        H = self.copy_heads
+        kv = dec.project_contexts(contexts)
+        sampling = self._sampling()
+        step = self._decode_stepper(B, kv, contexts, gen_len, sample=sampling, hidden=True)
+        k_src = self._copy_k(self._article_2(enc)).transpose(0, 1)           # [B, S, E], once per batch
+        S, dtype = k_src.shape[1], k_src.dtype
+        ea = self.entity_attn
+        He, scaling = ea.attention.num_heads, ea.attention.attention_module.scaling
+
+        def make_book():
+            return dict(ids=torch.empty(B, gen_len + 1, dtype=torch.long, device=dev),
+                        lps=torch.empty(B, gen_len, dtype=torch.float32, device=dev),
+                        done_step=torch.empty(B, dtype=torch.long, device=dev), fin8=torch.empty(B, dtype=torch.uint8, device=dev))
+
+        def make_copy():
+            return dict(k_article=torch.empty(B, S, E, dtype=dtype, device=dev),
+                        proper=torch.empty(B, S, dtype=torch.int8, device=dev),
+                        ctx_ids=torch.empty(B, S, dtype=torch.long, device=dev),
+                        mask=torch.empty(B, S, dtype=torch.uint8, device=dev),
+                        hist=torch.empty(B, gen_len + 1, dtype=torch.int32, device=dev),
+                        copied=torch.empty(B, gen_len + 1, dtype=torch.uint8, device=dev),
+                        probs=torch.empty(B, gen_len, dtype=torch.float32, device=dev),
+                        k_hist=torch.empty(gen_len, B, E, dtype=dtype, device=dev),
+                        v_hist=torch.empty(gen_len, B, E, dtype=dtype, device=dev),
+                        scratch=torch.empty(B, H, S, dtype=torch.float32, device=dev),
+                        tok=torch.empty(B, dtype=torch.int32, device=dev))
+        bk = step.book('greedy', make_book) if step.static else make_book()
+        cp = step.book('pointer', make_copy) if step.static else make_copy()
+        ids, lps, done_step, fin8 = bk['ids'], bk['lps'], bk['done_step'], bk['fin8']
+        ops._check_rows('cached generation', (B, S), proper_masks=context[self.index + '_proper_masks'],
+                        context_ids=context[self.index], article_mask=enc.article_mask)
+        cp['k_article'].copy_(k_src)
+        cp['proper'].copy_(context[self.index + '_proper_masks'])
+        cp['ctx_ids'].copy_(context[self.index])
+        if enc.article_mask is None:
+            cp['mask'].zero_()
+        else:
+            cp['mask'].copy_(enc.article_mask)
+        cp['hist'].fill_(-1)
+        cp['copied'].zero_()
+        cp['copied'][:, 0] = 1
+        cp['probs'].zero_()
+        cp['k_hist'].zero_()
+        cp['v_hist'].zero_()
+        k_article = cp['k_article'].transpose(0, 1)                          # the [S, B, E] view the kernel takes by strides
+        ids.fill_(self.padding_idx)
+        lps.zero_()
+        done_step.fill_(gen_len)
+        cur = caption_ids[:, 0:1].contiguous()
+        finished = cur[:, 0] == eos
+        ids[:, 0] = cur[:, 0]
+        done_step[finished] = 0
+        fin8.copy_(finished)
+        if sampling is not None:
+            step.seed.fill_(draw_seed())
+        next_cur = step.cur if step.static else torch.empty(B, 1, dtype=torch.long, device=dev)
+        next_cur.copy_(cur)
+        inv_temp = 1.0 / float(self.sampling_temp)
+        fc = self.entity_fc
+
+        def post(out, i, step_dev):
+            gen_tok, lp, x = out
+            xt = x.transpose(0, 1)                                           # [1, B, E]
+            k_new, v_new = ea.project_kv(xt)
+            attn = ops.entity_attn_step(ea.in_proj_q(xt)[0], k_new[0], v_new[0], cp['k_hist'], cp['v_hist'], He, scaling, i,
+                                        step_dev)
+            x_entity = ea._finish(attn.unsqueeze(0), xt)
+            ent = ops.entity_logits(x_entity, fc.weight_g, fc.weight_v, fc.bias)
+            ops.copy_decide(self._copy_q(xt[0]), k_article, self.bias_k, cp['mask'], cp['proper'], cp['ctx_ids'], ent,
+                            gen_tok.reshape(B), fin8, cp['hist'], cp['copied'], cp['probs'], i, H, cp['scratch'], cp['tok'],
+                            step_dev)
+            # the bookkeeping of the plain greedy decode, on the copy decision's token; the log-prob stays the generator's
+            ops.call('tell_greedy_update', cp['tok'], lp.reshape(B), fin8, ids, ids.stride(0), lps, lps.stride(0), done_step,
+                     next_cur, B, int(i), int(eos), inv_temp, step.counter_out, step_dev)
+        if step.static:
+            yield from step.steps(gen_len, check_every, post, fin8)
+        else:
+            for i in range(gen_len):
+                step(i, next_cur, post=post)
+                yield i
+                if (i + 1) % check_every == 0 and bool(fin8.all()):
+                    break
+        steps = max(int(done_step.max()), 1)                                  # one sync at the end
+        return (ids[:, :steps + 1].clone(), lps[:, :steps].clone(), cp['copied'][:, :steps + 1].bool(),
+                cp['probs'][:, :steps].clone())
 
     def get_metrics(self, reset=False):
         metrics = super().get_metrics(reset=False)

@@ -80,10 +80,16 @@ class DecodeStepper:
     tell_adaptive_logprob_topk_guided (k = 1 for the greedy decode) with pair_offset = B / 2, which writes the same candidates
     to both rows of a pair.  gamma lives in a device float of the cache entry (h['gamma'], step.set_guidance(gamma) per caption
     batch): the captured step reads it, so one graph serves every gamma.  ('guide', drop) joins the signature only when set;
-    it combines with nothing but beam search and its length penalty."""
+    it combines with nothing but beam search and its length penalty.
+
+    hidden=True (the copy models): the step hands out the decoder's last hidden row next to the pick -
+    (token, log-prob, x [B, 1, E]) - so that the caller's `post` can run its own tail on it (entity attention, copy decision, then
+    the bookkeeping launch); `post` is recorded into the captured single-step and multi-step graphs as ever, however many
+    launches it issues.  ('hidden',) joins the signature only when set."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False, pen=None, hyp=1, mask=False, guide=None):
+                 prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False):
+        self.hidden = bool(hidden)
         if guide is not None:
             for on, what in ((sample is not None, 'sampling (sampling_topk / sampling_topp / sampling_minp / sampling_typical)'),
                              (ban is not None, 'no_repeat_ngram_size / min_len'),
@@ -182,6 +188,8 @@ class DecodeStepper:
             sig = sig + (('mask',),)
         if self.guide is not None:                                # (... and every one without guidance)
             sig = sig + (('guide', self.guide),)
+        if self.hidden:                                           # (... and every one that keeps its hidden row to itself)
+            sig = sig + (('hidden',),)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -418,7 +426,8 @@ class DecodeStepper:
                 # slot = step index: the host's in an eager step; captured, the counter holds i - 1 (base 1)
                 kw['attn_sink'] = self.attn.at(1, sidx) if torch.is_tensor(sidx) else self.attn.at(int(sidx))
             out = self.dec({self.index: cur}, self.ctx, incremental_state=self.state, kv_cache=self.kv, **kw)
-            return self._head(out[0][:, -1:], sidx)
+            x = out[0][:, -1:]
+            return self._head(x, sidx) + ((x,) if self.hidden else ())
         finally:
             decode.CUR_LANE[0] = prev_lane
 

@@ -1522,12 +1522,13 @@ class CaptionModel(Model):
         return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None, hyp=1, mask=False, guide=None):
+                        prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
                              opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}),
-                             **({'mask': True} if mask else {}), **({'guide': guide} if guide is not None else {}))
+                             **({'mask': True} if mask else {}), **({'guide': guide} if guide is not None else {}),
+                             **({'hidden': True} if hidden else {}))
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,

@@ -2220,6 +2220,60 @@ def copy_step(q, k, bias_k, mask, proper, ctx_ids, rows, entity_logits, gen_tok,
     return tok, copied.bool(), prob
 
 
+def _step_args(step, step_dev):
+    """(step, step_dev) of the decode kernels: the host's index, or the device counter of a captured step (index = *counter + 1)"""
+    return (0, step_dev) if step_dev is not None else (int(step), None)
+
+
+def entity_attn_step(q, k_new, v_new, k_hist, v_hist, H, scale, step, step_dev=None):
+    """The entity attention of decode step `step` over a static history (include/tell_hip.h tell_entity_attn_step): q, k_new, v_new
+    [B, E] this step's projections, k_hist / v_hist [L, B, E]; row `step` of the histories is written, -> out [B, E]."""
+    B, E = q.shape
+    L = k_hist.shape[0]
+    _check_rows('entity_attn_step', (B, E), k_new=k_new, v_new=v_new)
+    _check_rows('entity_attn_step', (L, B, E), k_hist=k_hist, v_hist=v_hist)
+    if any(t.dtype != q.dtype or t.stride(-1) != 1 for t in (q, k_new, v_new, k_hist, v_hist)) or k_hist.stride() != v_hist.stride():
+        raise ValueError('entity_attn_step: operands of one dtype with unit inner stride, histories of one layout')
+    out = torch.empty(B, E, dtype=q.dtype, device=q.device)
+    s, sd = _step_args(step, step_dev)
+    call('tell_entity_attn_step', q, q.stride(0), k_new, k_new.stride(0), v_new, v_new.stride(0), k_hist, v_hist,
+         k_hist.stride(0), k_hist.stride(1), out, out.stride(0), B, H, E // H, L, float(scale), s, sd, hip.dt(q))
+    return out
+
+
+def copy_decide(q, k, bias_k, mask, proper, ctx_ids, entity_logits, gen_tok, finished, hist, copied, prob, step, H, scratch,
+                tok, step_dev=None):
+    """One decode step's copy decision over a static batch (include/tell_hip.h tell_copy_decide): q [B, E] scaled, k [S, B, E]
+    (any strides with a unit inner one), gen_tok int32 [B], finished uint8 [B] or None; unfinished rows get tok[r] (int32 [B]),
+    hist[r, step + 1] (int32 [B, L + 1]), copied[r, step + 1] (uint8 [B, L + 1]) and prob[r, step] (fp32 [B, L]); scratch fp32
+    [B, H, S]."""
+    B, E = q.shape
+    S = k.shape[0]
+    L = prob.shape[1]
+    _check_rows('copy_decide', (B, S), mask=mask, proper=proper, ctx_ids=ctx_ids)
+    _check_rows('copy_decide', (S, B, E), k=k)
+    _check_rows('copy_decide', (B, 2), entity_logits=entity_logits)
+    _check_rows('copy_decide', (B,), gen_tok=gen_tok, finished=finished, tok=tok)
+    _check_rows('copy_decide', (B, L + 1), hist=hist, copied=copied)
+    _check_rows('copy_decide', (B, H, S), scratch=scratch)
+    for name, t, dtype in (('gen_tok', gen_tok, torch.int32), ('tok', tok, torch.int32), ('hist', hist, torch.int32),
+                           ('copied', copied, torch.uint8), ('prob', prob, torch.float32), ('scratch', scratch, torch.float32),
+                           ('finished', finished, torch.uint8), ('mask', mask, torch.uint8), ('proper', proper, torch.int8),
+                           ('ctx_ids', ctx_ids, torch.int64), ('entity_logits', entity_logits, torch.float32),
+                           ('k', k, q.dtype), ('q', q, q.dtype)):
+        if t is not None and (t.dtype != dtype or (t.dim() and t.stride(-1) != 1)):
+            raise ValueError('copy_decide: %s must be %s with a unit inner stride' % (name, dtype))
+    for name, t in (('mask', mask), ('proper', proper), ('ctx_ids', ctx_ids), ('entity_logits', entity_logits),
+                    ('scratch', scratch)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError('copy_decide: %s must be contiguous' % name)
+    s, sd = _step_args(step, step_dev)
+    call('tell_copy_decide', q, q.stride(0), k, k.stride(0), k.stride(1), _bias_row(bias_k, q.dtype), mask, proper, ctx_ids,
+         entity_logits, gen_tok, finished, hist, hist.stride(0), copied, copied.stride(0), prob, prob.stride(0), L, s, sd, B, H, S,
+         E // H, scratch, tok, hip.dt(q))
+    return tok
+
+
 def entity_logits(x, g, v, b):
     """entity_fc of the generation step: x [1,Ba,E] -> logits [Ba,2] fp32 (tell_entity_logits)."""
     _, Ba, E = x.shape
