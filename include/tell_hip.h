@@ -965,6 +965,20 @@ int tell_copy_decide(const void* q, long q_sb, const void* k, long k_ss, long k_
                      const int* gen_tok, const uint8_t* finished, int* hist, long ld_hist, uint8_t* copied,
                      long ld_copied, float* prob, long ld_prob, int L, int step, const int* step_dev, int B, int H, int S,
                      int D, float* scratch, int* tok, int dtype, tell_stream_t stream);
+/* tell_copy_decide for per_image = n hypotheses of every image (1..16; generate(n_samples=n) of the copy models, DESIGN.md
+ * section 28): R = B * n rows, hypothesis j of image b is row r = b * n + j (the convention of tell_sample_rank).  R rows
+ * tall: q, entity_logits, gen_tok, finished, hist, copied, prob, tok and scratch (fp32 [R, H, S]); B rows, read at
+ * b = r / n: k [S,B,H*D], mask, proper, ctx_ids.  Every output of row r is, bit for bit, what tell_copy_decide writes for row
+ * r of the same batch with every image's keys, mask, proper mask and ids repeated n times - prob included.  Launch 1, grid
+ * (image, head, chunk of 4 hypotheses - all n when n < 4): a key's head slice is loaded once per workgroup and multiplied
+ * with every query of the chunk; a workgroup whose hypotheses are all finished returns at once; a finished row reads and
+ * writes nothing of its own.  Launch 2: one workgroup per row.  Limits, step / step_dev and declined calls as
+ * tell_copy_decide. */
+int tell_copy_decide_hyp(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k,
+                         const uint8_t* mask, const int8_t* proper, const long* ctx_ids, const float* entity_logits,
+                         const int* gen_tok, const uint8_t* finished, int* hist, long ld_hist, uint8_t* copied,
+                         long ld_copied, float* prob, long ld_prob, int L, int step, const int* step_dev, int B,
+                         int per_image, int H, int S, int D, float* scratch, int* tok, int dtype, tell_stream_t stream);
 
 #ifdef __cplusplus
 }

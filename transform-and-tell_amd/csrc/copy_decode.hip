@@ -13,6 +13,11 @@
 //    ascending order, proper mask, per-id chains, arg-max, the rules and the stores of copy_step_kernel.
 //    The arithmetic of a key does not depend on its position s (the same pieces, the same butterfly, the same exp), so
 //    byte-identical key rows get bit-equal weights.
+//  * tell_copy_decide_hyp: tell_copy_decide for n hypotheses per image, rows r = b n + j over the
+//    keys, masks and ids of B images.  Launch 1, grid (image, head, chunk of HYP_CHUNK hypotheses): every key slice is
+//    loaded once per workgroup and multiplied with the chunk's queries; per row the arithmetic of copy_probs_kernel, so its
+//    outputs are that kernel's over the n-times repeated keys, bit for bit.  Launch 2 is tell_copy_decide's with r / n as
+//    the row of proper and ctx_ids.
 //
 // Plain FMA code; every launcher is asynchronous: no host synchronisation, no allocation.
 #include "common.h"
@@ -22,6 +27,8 @@ namespace {
 constexpr int NT = 256;           // threads per workgroup
 constexpr int NW = NT / 64;
 constexpr int MAX_S = 512;        // article positions a workgroup keeps in LDS
+constexpr int MAX_HYP = 16;       // hypotheses per image (tell_sample_rank's limit)
+constexpr int HYP_CHUNK = 4;      // ... of which one workgroup of copy_probs_hyp_kernel serves this many
 
 template <typename T> __device__ __forceinline__ float ld(const T* p) { return Elem<T>::ld(p); }
 template <typename T> __device__ __forceinline__ void st(T* p, float v) { Elem<T>::st(p, v); }
@@ -149,6 +156,136 @@ __global__ __launch_bounds__(NT) void copy_probs_kernel(const T* __restrict__ q,
   for (int s = threadIdx.x; s < S; s += NT) out[s] = __expf(lg[s] - lz);
 }
 
+// block-wide reductions of CH values at once: per value the order of block_max / block_sum (wave reduction, then the waves
+// in ascending order), one pair of barriers for all of them; `red` holds CH * NW floats
+template <int CH>
+__device__ __forceinline__ void block_max_n(float (&v)[CH], float* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) v[c] = wave_max(v[c]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) red[c * NW + w] = v[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    float r = red[c * NW];
+    for (int i = 1; i < NW; ++i) r = fmaxf(r, red[c * NW + i]);
+    v[c] = r;
+  }
+}
+template <int CH>
+__device__ __forceinline__ void block_sum_n(float (&v)[CH], float* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) v[c] = wave_sum(v[c]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) red[c * NW + w] = v[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    float r = red[c * NW];
+    for (int i = 1; i < NW; ++i) r += red[c * NW + i];
+    v[c] = r;
+  }
+}
+
+// ------------------------------------------------------------------ copy decision for n hypotheses per image, launch 1
+// grid (B images, H, chunks of CH hypotheses).  copy_probs_kernel with CH queries against one pass over the image's keys:
+// hypothesis j of image b is row r = b n + j of q / finished / scratch, the keys and the mask are image b's.  A key's head
+// slice is loaded once per workgroup and multiplied with the CH queries the lanes keep in registers; per row the arithmetic
+// is copy_probs_kernel's, term by term (the lane pieces in element order, the xor butterfly, the strided partial sums of
+// the 256 threads, wave reduction, waves in ascending order, __expf(lg - lz)), so row r gets the bits copy_probs_kernel
+// gives it over the n-times repeated keys.  A finished hypothesis, or a slot past n in the last chunk, is `dead`: its query
+// is not loaded (zeros take its place in the products) and nothing is stored for it.
+template <typename T, int CH>
+__global__ __launch_bounds__(NT) void copy_probs_hyp_kernel(const T* __restrict__ q, long q_sb, const T* __restrict__ k,
+                                                            long k_ss, long k_sb, const T* __restrict__ bias_k,
+                                                            const uint8_t* __restrict__ mask,
+                                                            const uint8_t* __restrict__ finished, int n, int H, int S, int D,
+                                                            int vec, float* __restrict__ scratch) {
+  constexpr int VEC = Elem<T>::VEC, LPK = 64 / VEC, KPP = NT / LPK, UNR = 4;
+  __shared__ float lg[CH][MAX_S + 2];
+  __shared__ float red[CH * NW];
+  const int b = blockIdx.x, h = blockIdx.y, j0 = blockIdx.z * CH, S2 = S + 2;
+  const long r0 = (long)b * n + j0;
+  bool live[CH];
+  bool any = false;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    live[c] = j0 + c < n && !(finished && finished[r0 + c]);
+    any = any || live[c];
+  }
+  if (!any) return;                                            // (the whole workgroup, in front of every barrier and load)
+  const int g = threadIdx.x % LPK, slot = threadIdx.x / LPK, d0 = g * VEC;
+  float qv[CH][VEC];
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      qv[c][j] = live[c] && d0 + j < D ? ld(q + (r0 + c) * q_sb + (long)h * D + d0 + j) : 0.f;
+  for (int s0 = 0; s0 < S2; s0 += KPP * UNR) {
+    float kv[UNR][VEC];
+    bool masked[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int s = s0 + u * KPP + slot;
+      masked[u] = s < S && mask && mask[(long)b * S + s];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) kv[u][j] = 0.f;
+      if (s <= S && d0 < D) {
+        const T* kp = (s < S ? k + s * k_ss + b * k_sb : bias_k) + (long)h * D + d0;
+        if (vec) {
+          unpack16(*reinterpret_cast<const uint4*>(kp), kv[u], kp);
+        } else {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j)
+            if (d0 + j < D) kv[u][j] = ld(kp + j);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int s = s0 + u * KPP + slot;
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        float part = 0.f;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) part += qv[c][j] * kv[u][j];
+#pragma unroll
+        for (int o = LPK / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+        if (g == 0 && s < S2) lg[c][s] = masked[u] ? -INFINITY : part;
+      }
+    }
+  }
+  __syncthreads();
+  float m[CH], l[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    m[c] = -INFINITY;
+    for (int s = threadIdx.x; s < S2; s += NT) m[c] = fmaxf(m[c], lg[c][s]);
+  }
+  block_max_n<CH>(m, red);                                     // >= 0: the zero key is never masked
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    l[c] = 0.f;
+    for (int s = threadIdx.x; s < S2; s += NT) l[c] += __expf(lg[c][s] - m[c]);
+  }
+  block_sum_n<CH>(l, red);
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    if (!live[c]) continue;                                    // (the same in every thread; no barrier behind it)
+    const float lz = m[c] + __logf(l[c]);
+    float* out = scratch + ((r0 + c) * H + h) * S;
+    for (int s = threadIdx.x; s < S; s += NT) out[s] = __expf(lg[c][s] - lz);
+  }
+}
+
 // nxt[s] = the next position holding the same id (-1 at the end of a chain), head[s] = 1 at the first occurrence - what
 // dedupe_row of csrc/copy.hip computes, by another route: a thread finds the PREVIOUS occurrence of its position's id (the
 // last match of one walk over the positions in front of it, no data-dependent exit: every lane reads the same sid[j], an
@@ -183,7 +320,7 @@ __device__ void dedupe_row(const long* __restrict__ ids, int S, int* sid, int* n
 }
 
 // ------------------------------------------------------------------ copy decision, launch 2: the row's decision
-// grid B.  Head mean (heads added in ascending order), proper mask, per-id sums along the chains in position order, arg-max
+// grid rows (n rows per image; tell_copy_decide: n = 1).  Head mean (heads added in ascending order), proper mask, per-id sums along the chains in position order, arg-max
 // with ties to the lower id, the 1e-6 rule, the has-copied check against hist[b, 0 .. p], the entity arg-max (ties to
 // index 0); stores of an unfinished row: tok[b], hist[b, p + 1], copied[b, p + 1], prob[b, p].
 __global__ __launch_bounds__(NT) void copy_finish_kernel(const float* __restrict__ scratch, const int8_t* __restrict__ proper,
@@ -192,7 +329,7 @@ __global__ __launch_bounds__(NT) void copy_finish_kernel(const float* __restrict
                                                          int* __restrict__ hist, long ld_hist, uint8_t* __restrict__ copied,
                                                          long ld_copied, float* __restrict__ prob, long ld_prob, int L,
                                                          int step, const int* __restrict__ step_dev, int H, int S,
-                                                         int* __restrict__ tok) {
+                                                         int n, int* __restrict__ tok) {
   __shared__ float wsum[MAX_S];
   __shared__ int sid[MAX_S];
   __shared__ int nxt[MAX_S];
@@ -201,14 +338,15 @@ __global__ __launch_bounds__(NT) void copy_finish_kernel(const float* __restrict
   __shared__ int bestid[NT];
   const int p = step_dev ? *step_dev + 1 : step;
   const int b = blockIdx.x;
+  const long img = b / n;                                      // proper / ctx: one row per image, n rows (hypotheses) each
   if (p < 0 || p >= L || (finished && finished[b])) return;    // (the whole workgroup)
   for (int s = threadIdx.x; s < S; s += NT) {
     float w = 0.f;
     for (int h = 0; h < H; ++h) w += scratch[((long)b * H + h) * S + s];
-    const bool keep = !proper || proper[(long)b * S + s] >= 1;
+    const bool keep = !proper || proper[img * S + s] >= 1;
     wsum[s] = keep ? w / H : 0.f;
   }
-  dedupe_row(ctx + (long)b * S, S, sid, nxt, head);            // (its barriers publish wsum)
+  dedupe_row(ctx + img * S, S, sid, nxt, head);                   // (its barriers publish wsum)
   float bp = -1.f;
   int bi = 0x7fffffff;
   for (int s = threadIdx.x; s < S; s += NT) {
@@ -297,6 +435,61 @@ extern "C" int tell_copy_decide(const void* q, long q_sb, const void* k, long k_
                          k_ss, k_sb, (const float*)bias_k, mask, finished, H, S, D, vec, scratch);
   }
   hipLaunchKernelGGL(copy_finish_kernel, dim3(B), dim3(NT), 0, stream, (const float*)scratch, proper, ctx_ids, entity_logits,
-                     gen_tok, finished, hist, ld_hist, copied, ld_copied, prob, ld_prob, L, step, step_dev, H, S, tok);
+                     gen_tok, finished, hist, ld_hist, copied, ld_copied, prob, ld_prob, L, step, step_dev, H, S, 1, tok);
   return tell_check_launch("copy_decide");
+}
+
+namespace {
+
+template <typename T, int CH>
+void launch_probs_hyp(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k, const uint8_t* mask,
+                      const uint8_t* finished, int B, int n, int H, int S, int D, int vec, float* scratch,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL((copy_probs_hyp_kernel<T, CH>), dim3(B, H, (n + CH - 1) / CH), dim3(NT), 0, stream, (const T*)q, q_sb,
+                     (const T*)k, k_ss, k_sb, (const T*)bias_k, mask, finished, n, H, S, D, vec, scratch);
+}
+
+template <typename T>
+void launch_probs_hyp(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k, const uint8_t* mask,
+                      const uint8_t* finished, int B, int n, int H, int S, int D, int vec, float* scratch,
+                      hipStream_t stream) {
+  // the chunk: HYP_CHUNK hypotheses of an image per workgroup, all n of them when there are fewer
+  switch (n < HYP_CHUNK ? n : HYP_CHUNK) {
+    case 1: launch_probs_hyp<T, 1>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, n, H, S, D, vec, scratch, stream); break;
+    case 2: launch_probs_hyp<T, 2>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, n, H, S, D, vec, scratch, stream); break;
+    case 3: launch_probs_hyp<T, 3>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, n, H, S, D, vec, scratch, stream); break;
+    default: launch_probs_hyp<T, 4>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, n, H, S, D, vec, scratch, stream);
+  }
+}
+
+}  // namespace
+
+extern "C" int tell_copy_decide_hyp(const void* q, long q_sb, const void* k, long k_ss, long k_sb, const void* bias_k,
+                                    const uint8_t* mask, const int8_t* proper, const long* ctx_ids,
+                                    const float* entity_logits, const int* gen_tok, const uint8_t* finished, int* hist,
+                                    long ld_hist, uint8_t* copied, long ld_copied, float* prob, long ld_prob, int L, int step,
+                                    const int* step_dev, int B, int per_image, int H, int S, int D, float* scratch, int* tok,
+                                    int dtype, hipStream_t stream) {
+  TELL_REQUIRE(D > 0 && D <= 64 && H > 0 && S >= 0 && S <= MAX_S, "copy_decide_hyp: bad sizes (D <= 64, S <= 512)");
+  TELL_REQUIRE(per_image >= 1 && per_image <= MAX_HYP, "copy_decide_hyp: per_image must be in 1..16");
+  TELL_REQUIRE(bias_k != nullptr, "copy_decide_hyp: bias_k is required");
+  TELL_REQUIRE(dtype == TELL_F32 || dtype == TELL_BF16, "copy_decide_hyp: bad dtype");
+  TELL_REQUIRE(L > 0 && ld_hist >= L + 1 && ld_copied >= L + 1 && ld_prob >= L,
+               "copy_decide_hyp: hist / copied [R, L + 1], prob [R, L]");
+  TELL_REQUIRE(step_dev != nullptr || (step >= 0 && step < L), "copy_decide_hyp: the history is full (0 <= step < L)");
+  TELL_REQUIRE(q && entity_logits && gen_tok && hist && copied && prob && tok && (S == 0 || (k && ctx_ids && scratch)),
+               "copy_decide_hyp: null pointer");
+  if (B <= 0) return TELL_OK;
+  const long es = dtype == TELL_BF16 ? 2 : 4, vecn = 16 / es;
+  const int vec = aligned16(k) && aligned16(bias_k) && (k_ss * es) % 16 == 0 && (k_sb * es) % 16 == 0 && D % vecn == 0;
+  if (S > 0) {
+    if (dtype == TELL_BF16)
+      launch_probs_hyp<uint16_t>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, per_image, H, S, D, vec, scratch, stream);
+    else
+      launch_probs_hyp<float>(q, q_sb, k, k_ss, k_sb, bias_k, mask, finished, B, per_image, H, S, D, vec, scratch, stream);
+  }
+  hipLaunchKernelGGL(copy_finish_kernel, dim3(B * per_image), dim3(NT), 0, stream, (const float*)scratch, proper, ctx_ids,
+                     entity_logits, gen_tok, finished, hist, ld_hist, copied, ld_copied, prob, ld_prob, L, step, step_dev, H, S,
+                     per_image, tok);
+  return tell_check_launch("copy_decide_hyp");
 }

@@ -11,7 +11,9 @@ is entity_loss + copy_loss in bits; gen_loss is computed and logged only.
 Generation (_generate :427-696) is greedy: per step the decoder's token, the entity decision over the step's output
 and its history, and one copy-decision launch (csrc/copy.hip tell_copy_step) with the article keys projected once
 per batch.  With `cached_generation` / `generate(cached=True)` the same decode runs through the cached, captured step of the
-plain models (_pointer_steps; csrc/copy_decode.hip tell_entity_attn_step and tell_copy_decide)."""
+plain models (_pointer_steps; csrc/copy_decode.hip tell_entity_attn_step and tell_copy_decide), and a
+model that samples (`sampling_topp`) draws `n_samples` captions per image there, from one pass of the encoders, one cached
+context and one read of the article keys per step (tell_copy_decide_hyp)."""
 import logging
 import math
 from collections import defaultdict
@@ -45,6 +47,7 @@ class PointerModelBase(CaptionModel):
     EXTRA_CONTEXTS = ('faces',)
     COPY_VARIANT = 1
     SEARCH_OPTIONS = False         # the decode step ends in the copy decision: the search options are out of scope
+    CACHED_N_SAMPLES = True        # ... but n sampled hypotheses per image decode through the cached step (_pointer_steps)
     STEP_GRAPH = False             # the loss may be None (no copy target in the batch): the trainer stays eager
     # the trainer's shape buckets would pad the article with pad ids: transformer_pointer_2's reduced vocabulary counts
     # every id of the context, so padding the graphs need (and these models do not capture) would change its loss
@@ -181,7 +184,14 @@ class PointerModelBase(CaptionModel):
                  rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None, cached=None):
         """cached (None: the model's `cached_generation` key): the same greedy / nucleus decode through the cached generator -
         projected context K/V, a batch that keeps its shape, one captured step per token (_pointer_steps).  Everything refused
-        below is refused on both paths."""
+        below is refused on both paths.
+        n_samples = n (2..16): only on the cached path and only for a model that samples
+        (`sampling_topp`) - n draws per image, row b * n + j of the decode step draw j of image b, keyed (seed, b * n + j,
+        step), ranked by rank_by / rank_len_penalty as for the plain models (section 21).  The keys of n = 1 then hold the
+        first rank; added are 'gen_ids_samples' [B, n, L], 'log_probs_samples' [B, n, L - 1], 'scores_samples' [B, n],
+        'sample_index' [B, n], 'duplicate' [B, n], 'scores' [B], 'should_copy_samples' [B, n, L] bool, 'copy_probs_samples'
+        [B, n, L - 1] and 'generations_samples' / 'copied_texts_samples' (n strings per image), all in rank order.  On the eager
+        path, or for a greedy model, n > 1 is refused as before.  n_samples = 1: exactly the call of before."""
         if attention:
             self._check_attention(beam_size)
         self._check_mask_options(banned, ground, attention)           # (refused: the copy decision is out of scope)
@@ -190,17 +200,38 @@ class PointerModelBase(CaptionModel):
             self._check_prefix(prefix, 0)                             # (refused: the copy decision is out of scope)
         self._check_beam(beam_size)
         self._check_options(beam_size, attention, n_best)
-        self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)   # (n > 1 refused, like the prefix)
+        # (the shells of the host tests never ran __init__: no key means the eager path)
+        use_cached = getattr(self, 'cached_generation', False) if cached is None else bool(cached)
+        # n > 1: the cached path of a sampling model only, refused like the prefix otherwise
+        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, cached=use_cached)
         self._require_masks(context)
         enc = encoded if encoded is not None else self.encode(context, image)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, None, enc)
-        use_cached = self.cached_generation if cached is None else bool(cached)
+        if ns is not None:
+            return self._generate_samples(caption_ids, contexts, enc, context, ns)
         decode = self._generate_pointer_cached if use_cached else self._generate_pointer
         gen_ids, log_probs, should_copy, copy_probs = decode(caption_ids, contexts, enc, context)
         ids = gen_ids.cpu()
         return {'gen_ids': gen_ids, 'log_probs': log_probs, 'should_copy': should_copy, 'copy_probs': copy_probs,
                 'generations': [self.detokenize(x[x > 1]) for x in ids],
                 'copied_texts': [self.detokenize(x[should_copy[i].cpu()]) for i, x in enumerate(ids)]}
+
+    @torch.no_grad()
+    def _generate_samples(self, caption_ids, contexts, enc, context, ns):
+        """generate(n_samples=n > 1, cached=True): ns = (n, rule, alpha) of _check_n_samples -> the result dict, every
+        `_samples` key in rank order and the keys of n = 1 the first rank."""
+        n = ns[0]
+        _, _, _, _, smp = self._drive(self._pointer_steps(caption_ids, contexts, enc, context, n=n, rank=ns[1:]))
+        ids, sc = smp['gen_ids_samples'].cpu(), smp['should_copy_samples'].cpu()
+        out = dict(smp)
+        out['generations_samples'] = [[self.detokenize(x[x > 1]) for x in img] for img in ids]
+        out['copied_texts_samples'] = [[self.detokenize(x[sc[b, j]]) for j, x in enumerate(img)] for b, img in enumerate(ids)]
+        out.update(gen_ids=smp['gen_ids_samples'][:, 0].contiguous(), log_probs=smp['log_probs_samples'][:, 0].contiguous(),
+                   should_copy=smp['should_copy_samples'][:, 0].contiguous(),
+                   copy_probs=smp['copy_probs_samples'][:, 0].contiguous(), scores=smp['scores_samples'][:, 0].contiguous(),
+                   generations=[g[0] for g in out['generations_samples']],
+                   copied_texts=[g[0] for g in out['copied_texts_samples']])
+        return out
 
     @torch.no_grad()
     def _generate_pointer(self, caption_ids, contexts, enc, context, gen_len=100, eos=2):
@@ -276,22 +307,31 @@ class PointerModelBase(CaptionModel):
     def _generate_pointer_cached(self, caption_ids, contexts, enc, context, gen_len=100, eos=2, check_every=8):
         return self._drive(self._pointer_steps(caption_ids, contexts, enc, context, gen_len, eos, check_every))
 
-    def _pointer_steps(self, caption_ids, contexts, enc, context, gen_len=100, eos=2, check_every=8):
+    def _pointer_steps(self, caption_ids, contexts, enc, context, gen_len=100, eos=2, check_every=8, n=1, rank=('score', 0.0)):
         """_generate_pointer on the cached generator - a generator in the style of _greedy_steps (one `yield` per issued step or
         multi-step replay), same results.  The context K/V are projected once, the batch keeps its shape (finished rows are
         masked, never compacted), the entity K/V history and the copy bookkeeping are static buffers, and the step's tail -
         entity projections, tell_entity_attn_step, out_proj + LayerNorm, entity_fc, the copy query, tell_copy_decide and the
         unchanged tell_greedy_update - is the stepper's `post`: part of the captured single-step and multi-step graphs, with the
         step index from the device counter.  One host synchronisation per `check_every` steps and one at the end.  When the
-        stepper is not static (graphs disabled) the same launches run one by one over buffers of this call."""
+        stepper is not static (graphs disabled) the same launches run one by one over buffers of this call.
+        n > 1 (a sampling model; generate(n_samples=n)): R = images * n rows are resident, hypothesis j of
+        image b in row b * n + j, as in _greedy_steps - cur, ids, lps, done_step, fin8, hist, copied, probs, tok, the entity K/V
+        histories and the scratch are R rows tall; the contexts, the projected K/V and the copy buffers k_article, proper,
+        ctx_ids and mask stay one row per image (the stepper's hyp = n; the copy decision's per_image = n,
+        tell_copy_decide_hyp).  One seed, row r draws with (seed, r, step).  Behind the loop _rank_samples scores,
+        de-duplicates and ranks; the result gains a fifth entry, the dict of the `_samples` keys in rank order.  n = 1
+        allocates, keys, captures and launches exactly what it did before."""
         dec = self.decoder
-        B = caption_ids.shape[0]
+        n = int(n)
+        images = caption_ids.shape[0]
+        B = images * n                                                       # decode rows
         dev = caption_ids.device
         E = self.in_proj_weight.shape[1]
         H = self.copy_heads
         kv = dec.project_contexts(contexts)
         sampling = self._sampling()
-        step = self._decode_stepper(B, kv, contexts, gen_len, sample=sampling, hidden=True)
+        step = self._decode_stepper(B, kv, contexts, gen_len, sample=sampling, hidden=True, **({'hyp': n} if n > 1 else {}))
         k_src = self._copy_k(self._article_2(enc)).transpose(0, 1)           # [B, S, E], once per batch
         S, dtype = k_src.shape[1], k_src.dtype
         ea = self.entity_attn
@@ -303,10 +343,10 @@ class PointerModelBase(CaptionModel):
                         done_step=torch.empty(B, dtype=torch.long, device=dev), fin8=torch.empty(B, dtype=torch.uint8, device=dev))
 
         def make_copy():
-            return dict(k_article=torch.empty(B, S, E, dtype=dtype, device=dev),
-                        proper=torch.empty(B, S, dtype=torch.int8, device=dev),
-                        ctx_ids=torch.empty(B, S, dtype=torch.long, device=dev),
-                        mask=torch.empty(B, S, dtype=torch.uint8, device=dev),
+            return dict(k_article=torch.empty(images, S, E, dtype=dtype, device=dev),
+                        proper=torch.empty(images, S, dtype=torch.int8, device=dev),
+                        ctx_ids=torch.empty(images, S, dtype=torch.long, device=dev),
+                        mask=torch.empty(images, S, dtype=torch.uint8, device=dev),
                         hist=torch.empty(B, gen_len + 1, dtype=torch.int32, device=dev),
                         copied=torch.empty(B, gen_len + 1, dtype=torch.uint8, device=dev),
                         probs=torch.empty(B, gen_len, dtype=torch.float32, device=dev),
@@ -317,7 +357,7 @@ class PointerModelBase(CaptionModel):
         bk = step.book('greedy', make_book) if step.static else make_book()
         cp = step.book('pointer', make_copy) if step.static else make_copy()
         ids, lps, done_step, fin8 = bk['ids'], bk['lps'], bk['done_step'], bk['fin8']
-        ops._check_rows('cached generation', (B, S), proper_masks=context[self.index + '_proper_masks'],
+        ops._check_rows('cached generation', (images, S), proper_masks=context[self.index + '_proper_masks'],
                         context_ids=context[self.index], article_mask=enc.article_mask)
         cp['k_article'].copy_(k_src)
         cp['proper'].copy_(context[self.index + '_proper_masks'])
@@ -332,11 +372,11 @@ class PointerModelBase(CaptionModel):
         cp['probs'].zero_()
         cp['k_hist'].zero_()
         cp['v_hist'].zero_()
-        k_article = cp['k_article'].transpose(0, 1)                          # the [S, B, E] view the kernel takes by strides
+        k_article = cp['k_article'].transpose(0, 1)                          # the [S, images, E] view the kernel takes by strides
         ids.fill_(self.padding_idx)
         lps.zero_()
         done_step.fill_(gen_len)
-        cur = caption_ids[:, 0:1].contiguous()
+        cur = caption_ids[:, 0:1].contiguous() if n == 1 else caption_ids[:, 0:1].repeat_interleave(n, dim=0).contiguous()
         finished = cur[:, 0] == eos
         ids[:, 0] = cur[:, 0]
         done_step[finished] = 0
@@ -358,7 +398,7 @@ class PointerModelBase(CaptionModel):
             ent = ops.entity_logits(x_entity, fc.weight_g, fc.weight_v, fc.bias)
             ops.copy_decide(self._copy_q(xt[0]), k_article, self.bias_k, cp['mask'], cp['proper'], cp['ctx_ids'], ent,
                             gen_tok.reshape(B), fin8, cp['hist'], cp['copied'], cp['probs'], i, H, cp['scratch'], cp['tok'],
-                            step_dev)
+                            step_dev, **({'per_image': n} if n > 1 else {}))
             # the bookkeeping of the plain greedy decode, on the copy decision's token; the log-prob stays the generator's
             ops.call('tell_greedy_update', cp['tok'], lp.reshape(B), fin8, ids, ids.stride(0), lps, lps.stride(0), done_step,
                      next_cur, B, int(i), int(eos), inv_temp, step.counter_out, step_dev)
@@ -371,6 +411,17 @@ class PointerModelBase(CaptionModel):
                 if (i + 1) % check_every == 0 and bool(fin8.all()):
                     break
         steps = max(int(done_step.max()), 1)                                  # one sync at the end
+        if n > 1:
+            lp0, ids0, info = self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank)
+            smp = dict(info.samples)
+            order = smp['sample_index']
+
+            def ranked(t):                                                    # [R, W] -> [images, n, W] by the same order
+                t = t.reshape(images, n, -1)
+                return t.gather(1, order.unsqueeze(-1).expand(-1, -1, t.shape[-1]))
+            smp['should_copy_samples'] = ranked(cp['copied'][:, :steps + 1]).bool()
+            smp['copy_probs_samples'] = ranked(cp['probs'][:, :steps])
+            return (ids0, lp0, smp['should_copy_samples'][:, 0].contiguous(), smp['copy_probs_samples'][:, 0].contiguous(), smp)
         return (ids[:, :steps + 1].clone(), lps[:, :steps].clone(), cp['copied'][:, :steps + 1].bool(),
                 cp['probs'][:, :steps].clone())
 

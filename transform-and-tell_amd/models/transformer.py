@@ -773,12 +773,15 @@ class CaptionModel(Model):
                              'the cached DynamicConv generator only' % type(self).__name__)
         return check_prefix(prefix, batch_size, self.decoder.adaptive_softmax.vocab_size, gen_len, self.padding_idx, eos)
 
+    CACHED_N_SAMPLES = False       # a model with a decision launch of its own that still decodes n hypotheses per image
+
     def _check_n_samples(self, n_samples=1, rank_by='score', rank_len_penalty=0.0, beam_size=1, attention=False,
-                         forward=False):
+                         forward=False, cached=False):
         """generate(n_samples=n): check_n_samples, and for n > 1 what it combines with - a sampling
         decode of the cached DynamicConv generator, one seed per call; no beam search (n_best is the beam's own form), no
-        attention maps, not forward=True, not the arg-max decode, not the LSTM decoders nor the copy models.
-        -> (n, rule, alpha), or None for n = 1."""
+        attention maps, not forward=True, not the arg-max decode, not the LSTM decoders nor the copy models - except, with
+        cached=True (the call decodes through the cached step), a copy model that samples (CACHED_N_SAMPLES, DESIGN.md
+        section 28).  -> (n, rule, alpha), or None for n = 1."""
         n, rule, alpha = check_n_samples(n_samples, rank_by, rank_len_penalty)
         if n == 1:
             return None
@@ -790,7 +793,8 @@ class CaptionModel(Model):
                              'per sample' % n)
         if forward:
             raise ValueError('n_samples goes with generate, not with forward=True')
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+        has_cache = hasattr(getattr(self, 'decoder', None), 'project_contexts')
+        if not has_cache or not (self.SEARCH_OPTIONS or (cached and self.CACHED_N_SAMPLES and self._sampling() is not None)):
             raise ValueError('n_samples=%d: %s has a decode step with its own decision launch (LSTM decoders, copy models); '
                              'several samples per image cover the cached DynamicConv generator only' % (n, type(self).__name__))
         if self._sampling() is None:

@@ -2242,16 +2242,25 @@ def entity_attn_step(q, k_new, v_new, k_hist, v_hist, H, scale, step, step_dev=N
 
 
 def copy_decide(q, k, bias_k, mask, proper, ctx_ids, entity_logits, gen_tok, finished, hist, copied, prob, step, H, scratch,
-                tok, step_dev=None):
+                tok, step_dev=None, per_image=1):
     """One decode step's copy decision over a static batch (include/tell_hip.h tell_copy_decide): q [B, E] scaled, k [S, B, E]
     (any strides with a unit inner one), gen_tok int32 [B], finished uint8 [B] or None; unfinished rows get tok[r] (int32 [B]),
     hist[r, step + 1] (int32 [B, L + 1]), copied[r, step + 1] (uint8 [B, L + 1]) and prob[r, step] (fp32 [B, L]); scratch fp32
-    [B, H, S]."""
-    B, E = q.shape
+    [B, H, S].
+    per_image = n (1..16; tell_copy_decide_hyp): the rows are n hypotheses of each image, row b * n + j
+    hypothesis j of image b - q, entity_logits, gen_tok, finished, hist, copied, prob, tok and scratch are images * n rows
+    tall, k [S, images, E], mask, proper and ctx_ids keep one row per image.  The default issues tell_copy_decide."""
+    n = per_image
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 16:
+        raise ValueError('copy_decide: per_image must be an integer in 1..16 (got %r)' % (n,))
+    B, E = q.shape                                   # B: the rows (hypotheses)
     S = k.shape[0]
     L = prob.shape[1]
-    _check_rows('copy_decide', (B, S), mask=mask, proper=proper, ctx_ids=ctx_ids)
-    _check_rows('copy_decide', (S, B, E), k=k)
+    if B % n:
+        raise ValueError('copy_decide: q has %d rows, no multiple of per_image = %d' % (B, n))
+    images = B // n
+    _check_rows('copy_decide', (images, S), mask=mask, proper=proper, ctx_ids=ctx_ids)
+    _check_rows('copy_decide', (S, images, E), k=k)
     _check_rows('copy_decide', (B, 2), entity_logits=entity_logits)
     _check_rows('copy_decide', (B,), gen_tok=gen_tok, finished=finished, tok=tok)
     _check_rows('copy_decide', (B, L + 1), hist=hist, copied=copied)
@@ -2268,6 +2277,11 @@ def copy_decide(q, k, bias_k, mask, proper, ctx_ids, entity_logits, gen_tok, fin
         if t is not None and not t.is_contiguous():
             raise ValueError('copy_decide: %s must be contiguous' % name)
     s, sd = _step_args(step, step_dev)
+    if n > 1:
+        call('tell_copy_decide_hyp', q, q.stride(0), k, k.stride(0), k.stride(1), _bias_row(bias_k, q.dtype), mask, proper,
+             ctx_ids, entity_logits, gen_tok, finished, hist, hist.stride(0), copied, copied.stride(0), prob, prob.stride(0), L, s,
+             sd, images, n, H, S, E // H, scratch, tok, hip.dt(q))
+        return tok
     call('tell_copy_decide', q, q.stride(0), k, k.stride(0), k.stride(1), _bias_row(bias_k, q.dtype), mask, proper, ctx_ids,
          entity_logits, gen_tok, finished, hist, hist.stride(0), copied, copied.stride(0), prob, prob.stride(0), L, s, sd, B, H, S,
          E // H, scratch, tok, hip.dt(q))
