@@ -1011,7 +1011,9 @@ static int launch_gemm(const GemmArgs& a, hipStream_t stream, int* bm_used = nul
     if (a.K % 64 == 0 && tiles(128, 128) >= 256) {       // direct-to-LDS path
       const int force_env = (int)tell_opt(OPT_GEMM_TILE);   // tuning aid
       const bool no_pp = force_env == 7;                  // 7: the default choice without the ping-pong kernel (A/B)
-      const int force = no_pp ? 0 : force_env;
+      // a statistics launch (tell_gemm_bn_stats) ignores a forced 256x256 tile: that tile does not fit the staged
+      // statistics epilogue (gemm_nt_glds_epilogue), so nothing would be written for bn_finish_kernel to combine
+      const int force = (no_pp || (force_env == 5 && a.stat_mean)) ? 0 : force_env;
       static const int n_cu = [] { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); (void)hipGetDeviceProperties(&pr, d); return pr.multiProcessorCount; }();
       // 256x192 (8 waves as 4x2, 64x96 per wave): the QKV projection (N = 3072) quantises to whole rounds with it
       if ((force == 0 || force == 9) && a.N % 192 == 0 && tiles(256, 192) % n_cu == 0 && a.K <= 2048 && !a.accumulate &&
@@ -1092,9 +1094,10 @@ static int launch_gemm(const GemmArgs& a, hipStream_t stream, int* bm_used = nul
         TELL_GEMM_LAUNCH(gemm_label("gemm_nt_glds_kernel", -1, sizeof(OutT) == 2, 256, 256), (gemm_nt_glds_kernel<OutT, 256, 256, 2, 4>), dim3((unsigned)tiles(256, 256)), dim3(512));
         return g_gemm_plan ? TELL_OK : tell_check_launch("gemm_nt_glds");
       }
-      if (force == 2)     // 256x128 (8 waves, 1 workgroup/CU) ties 128x128 (2 workgroups/CU) on MI355X: opt-in only
+      if (force == 2) {   // 256x128 (8 waves, 1 workgroup/CU) ties 128x128 (2 workgroups/CU) on MI355X: opt-in only
+        *bm_used = 256;   // (the chunk height of the statistics epilogue: one chunk per m-tile)
         TELL_GEMM_LAUNCH(gemm_label("gemm_nt_glds_kernel", -1, sizeof(OutT) == 2, 256, 128), (gemm_nt_glds_kernel<OutT, 256, 128, 4, 2>), dim3((unsigned)tiles(256, 128)), dim3(512));
-      else
+      } else
         TELL_GEMM_LAUNCH(gemm_label("gemm_nt_glds_kernel", -1, sizeof(OutT) == 2, 128, 128), (gemm_nt_glds_kernel<OutT, 128, 128, 2, 2>), dim3((unsigned)tiles(128, 128)), dim3(256));
       return g_gemm_plan ? TELL_OK : tell_check_launch("gemm_nt_glds");
     }
