@@ -798,7 +798,12 @@ int tell_bertadam_step2(float* param, float* grad, float* m, float* v, const int
 /* skip (int[2], may be NULL): skip[0] != 0 -> the step leaves parameters / moments untouched (gradient still cleared)
  * and skip[1] counts such steps; tell_loss_flag sets skip[0] = !isfinite(loss) (the NaN-loss skip of
  * callback_apex_trainer.py:225-227 without a host sync), the norm pass ORs in 2 for a non-finite gradient (what apex
- * amp O2's overflow check does). */
+ * amp O2's overflow check does).
+ * Limits: the gradient is inspected by the norm pass only - with max_norm <= 0 (no clipping) a NaN / Inf gradient is
+ * NOT detected and goes into m, v and the parameter of its element (tell_loss_flag still covers a non-finite loss); a
+ * finite gradient whose scaled sum of squares overflows fp32 counts as non-finite and skips the step.  eps must be
+ * positive (refused otherwise: the zero padding between tensors would become 0 / 0).  param, grad, m, v 16-byte
+ * aligned, shadow_bf16 and grad_wire_bf16 8-byte aligned; a refused call launches nothing and writes nothing. */
 int tell_loss_flag(const float* loss, int* skip, tell_stream_t stream);
 
 /* ---- ResNet-152 trunk helpers, tell/models/resnet.py:92-108 (NHWC) ----------- */

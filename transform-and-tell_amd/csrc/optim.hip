@@ -164,10 +164,15 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
       const long o = (c0 + u) * OPT_CHUNK / 4 + threadIdx.x;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
+        // Every multiply-add spelled out, none left to the compiler's contraction: written as plain expressions the
+        // U = 1 instantiation fused m and v differently from the U = 2 / 4 ones (1 ulp apart in m, v and p on a few
+        // percent of the elements).  This is the arithmetic the U = 2 / 4 instantiations - the default - always had.
+#pragma clang fp contract(off)
         const float gg = g[u][k] * coef[u];
-        mm[u][k] = b1 * mm[u][k] + (1.f - b1) * gg;
-        vv[u][k] = b2 * vv[u][k] + (1.f - b2) * gg * gg;
-        p[u][k] -= lr * (mm[u][k] / (sqrtf(vv[u][k]) + eps) + wd * p[u][k]);
+        mm[u][k] = __builtin_fmaf(1.f - b1, gg, b1 * mm[u][k]);
+        const float g2 = ((1.f - b2) * gg) * gg;
+        vv[u][k] = b2 * vv[u][k] + g2;
+        p[u][k] = __builtin_fmaf(-lr, __builtin_fmaf(wd, p[u][k], mm[u][k] / (sqrtf(vv[u][k]) + eps)), p[u][k]);
       }
       stf(param, o, p[u]); stf(m, o, mm[u]); stf(v, o, vv[u]);
       if (shadow) {
@@ -193,12 +198,18 @@ extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v
                                    const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
                                    const int* keep_grad, hipStream_t stream) {
   if (n_chunks <= 0) return TELL_OK;
+  // (every refusal before the first launch: a refused call writes nothing, *lr_dev included)
+  TELL_REQUIRE(((uintptr_t)grad_wire_bf16 & 7) == 0 && ((uintptr_t)shadow_bf16 & 7) == 0,
+               "bertadam: the bf16 gradient and the bf16 shadow must be 8-byte aligned");
+  const uint16_t* wire = static_cast<const uint16_t*>(grad_wire_bf16);
+  TELL_REQUIRE(((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0 && ((uintptr_t)m & 15) == 0 &&
+                   ((uintptr_t)v & 15) == 0,
+               "bertadam: buffers must be 16-byte aligned");
+  // eps = 0: the zero padding between tensors (m = v = 0) would become 0 / 0 in the master and the shadow
+  TELL_REQUIRE(eps > 0.f, "bertadam: eps must be positive");
   if (step_dev)      // device-side schedule: this step's learning rate from the count of updates applied so far
     hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, lr_base, warmup, t_total,
                        const_cast<float*>(lr_dev));
-  TELL_REQUIRE(((uintptr_t)grad_wire_bf16 & 7) == 0, "bertadam: the bf16 gradient must be 8-byte aligned");
-  const uint16_t* wire = static_cast<const uint16_t*>(grad_wire_bf16);
-  TELL_REQUIRE(((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0, "bertadam: buffers must be 16-byte aligned");
   // TELL_ADAM_VAR (A/B aid, read once): 0 = one chunk per iteration, default cache policy (the round-4 kernel's shape);
   // 1 = U 2; 2 = U 4; 3 = U 2 + non-temporal; 4 = U 4 + non-temporal.  tools/probes/stream_probe.hip has the same shapes
   // on bare buffers.
