@@ -791,6 +791,27 @@ int tell_bertadam_step2(float* param, float* grad, float* m, float* v, const int
                         float grad_scale, void* shadow_bf16, int zero_grad, int* skip, const void* grad_wire_bf16,
                         int* step_dev, float lr_base, float warmup, float t_total, const int* keep_grad,
                         tell_stream_t stream);
+/* The same step, which also keeps an exponential moving average of the masters.  ema: flat fp32,
+ * same layout as param, 16-byte aligned; ema_omd_dev: one device float, scratch for this step's 1 - d_t.  With n =
+ * *step_dev before this launch increments it: d_t = ema_decay when ema_warm <= 0 or step_dev is NULL, else
+ * min(ema_decay, (1 + n) / (ema_warm + n)), in double from the fp32 arguments; omd = (float)(1 - d_t) goes to
+ * *ema_omd_dev in a single-thread launch next to the learning-rate one; per element e' = fmaf(omd, p' - e, e) in fp32
+ * with p' the master this step has just computed.  A skipped step (skip[0] != 0) leaves ema untouched and, as step_dev
+ * does not advance, costs no tick of this schedule either.  Everything else is bit for bit what tell_bertadam_step2
+ * writes from the same inputs; the padding between tensors stays +0 in ema.  Refused (negative code, nothing launched,
+ * nothing written, *lr_dev and *ema_omd_dev included): ema or ema_omd_dev NULL, ema not 16-byte aligned, ema_decay
+ * outside [0, 1) or not finite, ema_warm negative or not finite, and whatever tell_bertadam_step2 refuses. */
+int tell_bertadam_step_ema(float* param, float* grad, float* m, float* v, const int* chunk_tensor,
+                           const long* chunk_begin, long n_chunks, int n_tensors, float* partial, float* norms,
+                           const float* lr_dev, float b1, float b2, float eps, float wd, float max_norm,
+                           float grad_scale, void* shadow_bf16, int zero_grad, int* skip, const void* grad_wire_bf16,
+                           int* step_dev, float lr_base, float warmup, float t_total, const int* keep_grad,
+                           float* ema, float* ema_omd_dev, float ema_decay, float ema_warm, tell_stream_t stream);
+/* One pass over n elements (a whole number of tell_opt_chunk() chunks): param and ema exchange values, shadow_bf16 (may
+ * be NULL) becomes the round-to-nearest-even bf16 of the new param.  Applied twice it restores all three buffers bit for
+ * bit.  Values move and no pointer changes, so captured graphs that hold these buffers stay valid.  param, ema 16-byte
+ * aligned, shadow_bf16 8-byte aligned; a refused call launches nothing and writes nothing. */
+int tell_ema_swap(float* param, float* ema, void* shadow_bf16, long n, tell_stream_t stream);
 /* step_dev (device int32, may be NULL): the count of updates APPLIED so far.  When given, the library first writes
  * *lr_dev = lr_base * warmup_linear(*step_dev / t_total, warmup) (t_total <= 0: lr_base) and the update kernel
  * increments *step_dev only when the step is not skipped - a skipped batch costs no tick of the schedule, exactly as in

@@ -17,6 +17,7 @@
 // (tools/decoder_profile.py, TELL_ADAM_VAR = 0..4): 6.93 / 6.82 / 6.75 / 6.80 / 6.73 ms.
 #define TELL_ADAM_DEFAULT 4
 #include <stdlib.h>
+#include <type_traits>
 
 // partial[c] = sum of squares of (grad * grad_scale) over chunk c
 // (wire != NULL: the gradient of this step is the bf16 buffer the data-parallel exchange left - read it as it is
@@ -98,12 +99,36 @@ __global__ void lr_schedule_kernel(const int* __restrict__ step, float lr, float
   }
   lr_dev[0] = (float)((double)lr * f);
 }
+// Exponential moving average of the masters: this step's 1 - d_t from the same count of APPLIED
+// updates n = *step (read before the update kernel increments it), d_t = min(decay, (1 + n) / (warm + n)) - the average
+// follows the weights closely while there are few of them.  warm <= 0 or no device counter: d_t = decay.  In double from
+// the fp32 arguments, like the learning rate above.  A skipped step leaves *step alone, so this schedule does not tick.
+__global__ void ema_schedule_kernel(const int* __restrict__ step, float decay, float warm, float* __restrict__ omd_dev) {
+  double d = (double)decay;
+  if (step && warm > 0.f) {
+    const double n = (double)step[0];
+    d = fmin(d, (1.0 + n) / ((double)warm + n));
+  }
+  omd_dev[0] = (float)(1.0 - d);
+}
 // One pass over the flat buffers: BertAdam update of the fp32 masters, the bf16 working copy the next forward
 // reads (shadow; no per-tensor cast kernels), and the zeroing of the gradient for the next step.
 // U: chunks per block iteration (all 4 U loads of a thread in flight before the first use); NT: the streams nobody reads
 // again soon (master, m, v, the zeroed gradient) go out with non-temporal stores and come in with non-temporal loads -
 // the bf16 shadow, which the next forward pass reads, keeps the default policy.
-template <int U, bool NT>
+// EMA (an EmaArgs as the one trailing argument): the same pass also moves the moving average e of the masters towards the
+// fresh master p' it holds in a register, e' = fma(omd, p' - e, e) with omd = *omd_dev = 1 - d_t (ema_schedule_kernel): one
+// more fp32 stream in and out (8 of 42 B per parameter), loaded with the other loads of the iteration and non-temporal
+// where the master is.  A skipped step leaves e alone.  The switch is the presence of that argument and not a third
+// `bool EMA` in the template list: without it an instantiation keeps its name (bertadam_update_kernel<4, true> - tests and
+// the recorded profiles look for it), its kernel arguments and, instruction for instruction, its code; an unused pointer
+// pair at the end of the argument list, or the body inlined into two wrapper kernels, changed the register allocation
+// of all five.
+struct EmaArgs {
+  float* ema;
+  const float* omd_dev;
+};
+template <int U, bool NT, typename... Ema>
 __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict__ param,
                                                               float* __restrict__ grad,
                                                               float* __restrict__ m, float* __restrict__ v,
@@ -115,9 +140,19 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
                                                               int zero_grad, int* __restrict__ skip,
                                                               const uint16_t* __restrict__ wire,
                                                               int* __restrict__ step_dev,
-                                                              const int* __restrict__ keep_grad) {
+                                                              const int* __restrict__ keep_grad, Ema... ema_args) {
+  static_assert(sizeof...(Ema) == 0 || (sizeof...(Ema) == 1 && (std::is_same<Ema, EmaArgs>::value && ...)),
+                "the optional trailing argument is one EmaArgs");
+  constexpr bool EMA = sizeof...(Ema) == 1;
   typedef __attribute__((ext_vector_type(4))) float f4;
   const float lr = *lr_dev;
+  float* ema = nullptr;
+  float omd = 0.f;
+  if constexpr (EMA) {
+    const EmaArgs ea[] = {ema_args...};
+    ema = ea[0].ema;
+    omd = *ea[0].omd_dev;
+  }
   // keep_grad[t] != 0: tensor t's gradient is rewritten whole (beta = 0 stores) by its single producer in the next
   // backward pass - not zeroed here (4 B / parameter less to write, and the producer does not read it back)
   if (skip && skip[0] != 0) {      // non-finite loss or gradient: leave p, m, v and the shadow alone, only clear the gradient
@@ -138,7 +173,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
     if (NT) __builtin_nontemporal_store(val, q); else *q = val;
   };
   for (long c0 = (long)blockIdx.x * U; c0 < n_chunks; c0 += (long)gridDim.x * U) {
-    f4 g[U], p[U], mm[U], vv[U];
+    f4 g[U], p[U], mm[U], vv[U], e[EMA ? U : 1];
     float coef[U];
     int tensor[U];
 #pragma unroll
@@ -148,6 +183,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
       if (wire) { const float4 w = load_grad4(grad, wire, o); g[u] = f4{w.x, w.y, w.z, w.w}; }
       else g[u] = ldf(grad, o);
       p[u] = ldf(param, o); mm[u] = ldf(m, o); vv[u] = ldf(v, o);
+      if constexpr (EMA) e[u] = ldf(ema, o);
       tensor[u] = chunk_tensor[c];
     }
 #pragma unroll
@@ -173,8 +209,13 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
         const float g2 = ((1.f - b2) * gg) * gg;
         vv[u][k] = b2 * vv[u][k] + g2;
         p[u][k] = __builtin_fmaf(-lr, __builtin_fmaf(wd, p[u][k], mm[u][k] / (sqrtf(vv[u][k]) + eps)), p[u][k]);
+        if constexpr (EMA) {             // (the difference rounded once, the multiply-add rounded once)
+          const float d = p[u][k] - e[u][k];
+          e[u][k] = __builtin_fmaf(omd, d, e[u][k]);
+        }
       }
       stf(param, o, p[u]); stf(m, o, mm[u]); stf(v, o, vv[u]);
+      if constexpr (EMA) stf(ema, o, e[u]);
       if (shadow) {
         uint2 sw;
         sw.x = (uint32_t)f2bf(p[u][0]) | ((uint32_t)f2bf(p[u][1]) << 16);
@@ -186,18 +227,58 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
   }
 }
 
+// One pass that exchanges the masters with their moving average and rewrites the bf16 working copy from what is now in
+// `param` (Trainer.ema_weights: evaluation with the averaged weights - values move, no pointer that a captured graph
+// holds changes).  Applied twice it restores all three buffers bit for bit.  One float4 of each stream per thread and
+// trip; both fp32 streams non-temporal (the next reader of the weights reads the shadow).
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ param, float* __restrict__ ema,
+                                                       uint16_t* __restrict__ shadow, long n4) {
+  typedef __attribute__((ext_vector_type(4))) float f4;
+  for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < n4; o += (long)gridDim.x * 256) {
+    f4* pp = reinterpret_cast<f4*>(param) + o;
+    f4* pe = reinterpret_cast<f4*>(ema) + o;
+    const f4 p = __builtin_nontemporal_load(pp), e = __builtin_nontemporal_load(pe);
+    __builtin_nontemporal_store(e, pp);
+    __builtin_nontemporal_store(p, pe);
+    if (shadow) {
+      uint2 sw;
+      sw.x = (uint32_t)f2bf(e[0]) | ((uint32_t)f2bf(e[1]) << 16);
+      sw.y = (uint32_t)f2bf(e[2]) | ((uint32_t)f2bf(e[3]) << 16);
+      reinterpret_cast<uint2*>(shadow)[o] = sw;
+    }
+  }
+}
+extern "C" int tell_ema_swap(float* param, float* ema, void* shadow_bf16, long n, hipStream_t stream) {
+  TELL_REQUIRE(param && ema, "ema_swap: param and ema must not be NULL");
+  TELL_REQUIRE(((uintptr_t)param & 15) == 0 && ((uintptr_t)ema & 15) == 0, "ema_swap: buffers must be 16-byte aligned");
+  TELL_REQUIRE(((uintptr_t)shadow_bf16 & 7) == 0, "ema_swap: the bf16 shadow must be 8-byte aligned");
+  TELL_REQUIRE(n >= 0 && n % OPT_CHUNK == 0, "ema_swap: n must be a whole number of chunks");
+  if (n == 0) return TELL_OK;
+  const long chunks = n / OPT_CHUNK;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3((int)(chunks < 8192 ? chunks : 8192)), dim3(256), 0, stream, param, ema,
+                     (uint16_t*)shadow_bf16, n / 4);
+  return tell_check_launch("ema_swap");
+}
+
 extern "C" int tell_opt_chunk(void) { return OPT_CHUNK; }
 
 // workspace `partial`: n_chunks floats; `norms`: n_tensors floats
 // keep_grad: device int32[n_tensors] or NULL - tensors whose gradient the zeroing leaves alone (see the kernel)
-extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v,
-                                   const int* chunk_tensor, const long* chunk_begin, long n_chunks,
-                                   int n_tensors, float* partial, float* norms, const float* lr_dev,
-                                   float b1, float b2, float eps, float wd, float max_norm,
-                                   float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
-                                   const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
-                                   const int* keep_grad, hipStream_t stream) {
+// EMA: tell_bertadam_step_ema - the moving average `ema` and the device scalar `omd_dev` join the update launch
+template <bool EMA>
+static int bertadam_launch(float* param, float* grad, float* m, float* v, const int* chunk_tensor, const long* chunk_begin,
+                           long n_chunks, int n_tensors, float* partial, float* norms, const float* lr_dev, float b1, float b2,
+                           float eps, float wd, float max_norm, float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
+                           const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
+                           const int* keep_grad, float* ema, float* omd_dev, float ema_decay, float ema_warm,
+                           hipStream_t stream) {
   if (n_chunks <= 0) return TELL_OK;
+  if (EMA) {
+    TELL_REQUIRE(ema && omd_dev, "bertadam: ema and ema_omd_dev must not be NULL");
+    TELL_REQUIRE(((uintptr_t)ema & 15) == 0, "bertadam: ema must be 16-byte aligned");
+    TELL_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "bertadam: ema_decay must be in [0, 1)");      // (false for NaN)
+    TELL_REQUIRE(ema_warm >= 0.f && ema_warm <= 3.4e38f, "bertadam: ema_warm must be finite and not negative");
+  }
   // (every refusal before the first launch: a refused call writes nothing, *lr_dev included)
   TELL_REQUIRE(((uintptr_t)grad_wire_bf16 & 7) == 0 && ((uintptr_t)shadow_bf16 & 7) == 0,
                "bertadam: the bf16 gradient and the bf16 shadow must be 8-byte aligned");
@@ -210,6 +291,7 @@ extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v
   if (step_dev)      // device-side schedule: this step's learning rate from the count of updates applied so far
     hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, lr_base, warmup, t_total,
                        const_cast<float*>(lr_dev));
+  if (EMA) hipLaunchKernelGGL(ema_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, ema_decay, ema_warm, omd_dev);
   // TELL_ADAM_VAR (A/B aid, read once): 0 = one chunk per iteration, default cache policy (the round-4 kernel's shape);
   // 1 = U 2; 2 = U 4; 3 = U 2 + non-temporal; 4 = U 4 + non-temporal.  tools/probes/stream_probe.hip has the same shapes
   // on bare buffers.
@@ -224,7 +306,17 @@ extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v
     hipLaunchKernelGGL((sqsum_chunks_kernel<4>), dim3(gs), dim3(256), 0, stream, grad, wire, n_chunks, grad_scale, partial);
     hipLaunchKernelGGL(tensor_norms_kernel, dim3(n_tensors), dim3(256), 0, stream, partial, chunk_begin, n_tensors, norms, skip);
   }
-#define TELL_ADAM_LAUNCH(UU, NTT) hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT>), dim3(g), dim3(256), 0, stream, param, grad, m, v, chunk_tensor, norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale, (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad)
+#define TELL_ADAM_LAUNCH(UU, NTT)                                                                                               \
+  do {                                                                                                                        \
+    if (EMA)                                                                                                                  \
+      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, EmaArgs>), dim3(g), dim3(256), 0, stream, param, grad, m, v,              \
+                         chunk_tensor, norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale,                        \
+                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, EmaArgs{ema, omd_dev});           \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT>), dim3(g), dim3(256), 0, stream, param, grad, m, v, chunk_tensor,   \
+                         norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale, (uint16_t*)shadow_bf16, zero_grad,   \
+                         skip, wire, step_dev, keep_grad);                                                                    \
+  } while (0)
   switch (var) {
     case 1: TELL_ADAM_LAUNCH(2, false); break;
     case 2: TELL_ADAM_LAUNCH(4, false); break;
@@ -234,6 +326,29 @@ extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v
   }
 #undef TELL_ADAM_LAUNCH
   return tell_check_launch("bertadam_step");
+}
+extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v,
+                                   const int* chunk_tensor, const long* chunk_begin, long n_chunks,
+                                   int n_tensors, float* partial, float* norms, const float* lr_dev,
+                                   float b1, float b2, float eps, float wd, float max_norm,
+                                   float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
+                                   const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
+                                   const int* keep_grad, hipStream_t stream) {
+  return bertadam_launch<false>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev, b1,
+                                b2, eps, wd, max_norm, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev,
+                                lr_base, warmup, t_total, keep_grad, nullptr, nullptr, 0.f, 0.f, stream);
+}
+extern "C" int tell_bertadam_step_ema(float* param, float* grad, float* m, float* v,
+                                      const int* chunk_tensor, const long* chunk_begin, long n_chunks,
+                                      int n_tensors, float* partial, float* norms, const float* lr_dev,
+                                      float b1, float b2, float eps, float wd, float max_norm,
+                                      float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
+                                      const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
+                                      const int* keep_grad, float* ema, float* ema_omd_dev, float ema_decay, float ema_warm,
+                                      hipStream_t stream) {
+  return bertadam_launch<true>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev, b1,
+                               b2, eps, wd, max_norm, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev,
+                               lr_base, warmup, t_total, keep_grad, ema, ema_omd_dev, ema_decay, ema_warm, stream);
 }
 extern "C" int tell_bertadam_step(float* param, float* grad, float* m, float* v,
                                   const int* chunk_tensor, const long* chunk_begin, long n_chunks,

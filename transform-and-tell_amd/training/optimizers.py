@@ -3,7 +3,9 @@ multi-tensor HIP kernel over flat fp32 buffers.  Update rule restated from
 pytorch_pretrained_bert.BertAdam (third-party, absent here; parity unpinned):
 per-tensor gradient-norm clipping, no bias correction, decoupled-style weight decay added
 to the update, `warmup_linear` schedule evaluated at the step count BEFORE the increment."""
+import math
 import re
+import warnings
 
 import torch
 
@@ -73,7 +75,15 @@ class FlatParams:
         self.accum_pending = False
         self.partial = torch.empty(max(self.n_chunks, 1), dtype=torch.float32, device=device)
         self.norms = torch.zeros(len(self.params), dtype=torch.float32, device=device)
+        # exponential moving average of the masters and the device scalar 1 - d_t of the current step: allocated by
+        # enable_ema (BertAdam(ema_decay=...)), absent otherwise
+        self.ema = self.ema_omd = None
         rt.bump_weights_epoch()
+
+    def enable_ema(self):
+        if self.ema is None:
+            self.ema = self.flat.clone()
+            self.ema_omd = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
 
     def refresh_shadow(self):
         """Re-derive the bf16 working copy from the fp32 masters (after anything but the optimizer kernel wrote the
@@ -122,8 +132,22 @@ class FlatParams:
 
 class BertAdam:
     def __init__(self, flat, lr=1e-4, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999,
-                 e=1e-6, weight_decay=0.01, max_grad_norm=1.0, parameter_groups=None):
+                 e=1e-6, weight_decay=0.01, max_grad_norm=1.0, parameter_groups=None, ema_decay=None, ema_warmup=10.0):
+        """ema_decay (None: off): keep an exponential moving average of the fp32 masters in flat.ema, updated by the step
+        kernel itself with the decay d_t = min(ema_decay, (1 + n) / (ema_warmup + n)) after n applied updates
+        (ema_warmup <= 0: always ema_decay); csrc/optim.hip, DESIGN.md section 31."""
         assert schedule == 'warmup_linear'
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or \
+                    not (math.isfinite(ema_decay) and 0.0 <= ema_decay < 1.0):
+                raise ValueError('bert_adam: ema_decay must be a number in [0, 1) or None, got %r' % (ema_decay,))
+            if isinstance(ema_warmup, bool) or not isinstance(ema_warmup, (int, float)) or \
+                    not (math.isfinite(ema_warmup) and ema_warmup >= 0.0):
+                raise ValueError('bert_adam: ema_warmup must be a finite number >= 0, got %r' % (ema_warmup,))
+        self.ema_decay, self.ema_warmup = ema_decay, ema_warmup
+        # True while Trainer.ema_weights() has exchanged the masters with the average: no update may run then
+        self.ema_swapped = False
+        self._warned = set()
         self.flat = flat
         self.lr, self.warmup, self.t_total = lr, warmup, t_total
         self.b1, self.b2, self.e, self.weight_decay, self.max_grad_norm = b1, b2, e, weight_decay, max_grad_norm
@@ -134,6 +158,20 @@ class BertAdam:
         # loss / gradient; the learning rate of a step is computed from it on the device (csrc/optim.hip)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.parameter_groups = parameter_groups    # all groups of the configs carry `{}` overrides
+        if ema_decay is not None:
+            flat.enable_ema()
+
+    def reset_ema(self):
+        """The average restarts from the current masters (after anything but the step kernel wrote them: the initial
+        data-parallel broadcast, a checkpoint without an average)."""
+        if self.ema_decay is None:
+            raise ValueError('bert_adam: reset_ema() needs ema_decay (got ema_decay=None)')
+        self.flat.ema.copy_(self.flat.flat)
+
+    def _warn_once(self, text):
+        if text not in self._warned:
+            self._warned.add(text)
+            warnings.warn(text)
 
     def applied_steps(self):
         """Updates applied so far = issued steps minus the skipped ones (one host sync)."""
@@ -162,14 +200,21 @@ class BertAdam:
         """grad_wire: optional bf16 copy of the whole flat gradient (the data-parallel exchange's wire buffer after the
         all-reduce): the kernels read it in place of flat.grad - no pass that widens it back first."""
         f = self.flat
+        if self.ema_swapped:
+            raise RuntimeError('bert_adam: no optimizer step inside Trainer.ema_weights() - the masters sit in the '
+                               'EMA buffer')
         from .. import ops
         keep = f.keep_grad if (zero_grad and ops.grad_store_on()) else None
         if zero_grad:
             f.accum_pending = False
-        hip.call('tell_bertadam_step2', f.flat, f.grad, f.m, f.v, f.chunk_tensor, f.chunk_begin, f.n_chunks,
-                 len(f.params), f.partial, f.norms, self.lr_dev, self.b1, self.b2, self.e, self.weight_decay,
-                 self.max_grad_norm, float(grad_scale), f.shadow, int(zero_grad), skip, grad_wire,
-                 self.step_dev, float(self.lr), float(self.warmup), float(self.t_total), keep)
+        args = (f.flat, f.grad, f.m, f.v, f.chunk_tensor, f.chunk_begin, f.n_chunks,
+                len(f.params), f.partial, f.norms, self.lr_dev, self.b1, self.b2, self.e, self.weight_decay,
+                self.max_grad_norm, float(grad_scale), f.shadow, int(zero_grad), skip, grad_wire,
+                self.step_dev, float(self.lr), float(self.warmup), float(self.t_total), keep)
+        if self.ema_decay is None:
+            hip.call('tell_bertadam_step2', *args)
+        else:
+            hip.call('tell_bertadam_step_ema', *args, f.ema, f.ema_omd, float(self.ema_decay), float(self.ema_warmup))
 
     def advance(self):
         """Host part after the kernels.  The host cannot see a device-side skip without a synchronisation, so it bumps
@@ -179,13 +224,26 @@ class BertAdam:
         rt.bump_weights_epoch()
 
     def state_dict(self):
-        return {'step': self.applied_steps(), 'm': self.flat.m, 'v': self.flat.v}
+        sd = {'step': self.applied_steps(), 'm': self.flat.m, 'v': self.flat.v}
+        if self.ema_decay is not None:
+            sd['ema'] = self.flat.ema
+        return sd
 
     def load_state_dict(self, sd):
+        """The weights themselves travel with the model's state dict - load that first: a state without 'ema' restarts
+        the average from the masters as they are now."""
         self.step_count = sd['step']
         self.step_dev.fill_(int(sd['step']))
         self.flat.m.copy_(sd['m'])
         self.flat.v.copy_(sd['v'])
+        if self.ema_decay is not None:
+            if 'ema' in sd:
+                self.flat.ema.copy_(sd['ema'])
+            else:
+                self._warn_once("bert_adam: the loaded state has no 'ema' - the average restarts from the loaded weights")
+                self.reset_ema()
+        elif 'ema' in sd:
+            self._warn_once("bert_adam: the loaded state has an 'ema' but ema_decay is None - ignored")
 
 
 def apply_no_grad(model, patterns):

@@ -10,6 +10,7 @@ DP equivalence with a single-GPU run on the concatenated batch: every rank's los
 re-weighted by n_local*world/n_global (token counts all-reduced on the device) before
 backward, then gradients are averaged.  Ranks that see no target of a tail cluster still
 contribute zeros: the flat buffer is always reduced as a whole."""
+import contextlib
 import os
 
 import torch
@@ -81,6 +82,10 @@ class Trainer:
             self.dist.broadcast(self.flat.flat, src=0)
             self.flat.refresh_shadow()
             rt.bump_weights_epoch()
+        # the optimizer was built before that broadcast: an average taken then would differ between ranks.  From here on
+        # every rank computes the same average from the same reduced gradients - no communication
+        if self.optimizer.ema_decay is not None:
+            self.optimizer.reset_ema()
         # TELL_ASYNC_UPDATE=1: gradient all-reduce + BertAdam + gradient zeroing run on their own stream and the model
         # waits for it right before its first trainable weight (rt.wait_weight_update).  Off by default: with the
         # encoders of the next batch already running on their two streams, a fourth / fifth stream of ours costs more
@@ -174,6 +179,38 @@ class Trainer:
         """Make the current stream wait for an in-flight weight update (checkpointing, evaluation, ...)."""
         rt.wait_weight_update()
 
+    def _swap_ema(self):
+        f = self.flat
+        with hip.bound_stream():
+            hip.call('tell_ema_swap', f.flat, f.ema, f.shadow, f.total)
+        self.optimizer.ema_swapped = not self.optimizer.ema_swapped
+        rt.bump_weights_epoch()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights():` - inside, the model's parameters (state_dict(), forward, generate*,
+        score_captions) are the exponential moving average of the weights (optimizer option ema_decay).  One pass
+        exchanges the VALUES of the masters and the average and rewrites the bf16 working copy (tell_ema_swap); no
+        pointer changes, so every captured graph stays valid exactly as after an optimizer step, and the weights epoch
+        is bumped for the caches keyed on it.  The same pass on exit restores all three buffers bit for bit.  No
+        training step inside: the masters sit in the EMA buffer."""
+        if self.optimizer.ema_decay is None:
+            raise ValueError('Trainer.ema_weights() needs the optimizer option ema_decay (got ema_decay=None)')
+        if self.optimizer.ema_swapped:
+            raise RuntimeError('Trainer.ema_weights() does not nest')
+        self.finish_update()
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def ema_state_dict(self):
+        """A detached copy of the model's state dict with the averaged weights in place of the trained ones - what to
+        save in order to evaluate with them later."""
+        with self.ema_weights():
+            return {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+
     def train_one_batch(self, batch, next_batch=None):
         """callback_apex_trainer.py:208-247 for one batch; returns the (detached) loss tensor.
 
@@ -182,6 +219,8 @@ class Trainer:
         issued, so ResNet-152 / RoBERTa-large of step N+1 fill the GPU underneath the latency-bound decoder
         forward, backward and optimizer of step N.  Numerics are unchanged: the encoders read no trainable
         weight, and BatchNorm running statistics are still updated in batch order on the encoder stream."""
+        if self.optimizer.ema_swapped:
+            raise RuntimeError('train_one_batch inside Trainer.ema_weights(): the masters sit in the EMA buffer')
         with hip.bound_stream():
             return self._train_one_batch(batch, next_batch)
 
