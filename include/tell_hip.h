@@ -807,6 +807,24 @@ int tell_bertadam_step_ema(float* param, float* grad, float* m, float* v, const 
                            float grad_scale, void* shadow_bf16, int zero_grad, int* skip, const void* grad_wire_bf16,
                            int* step_dev, float lr_base, float warmup, float t_total, const int* keep_grad,
                            float* ema, float* ema_omd_dev, float ema_decay, float ema_warm, tell_stream_t stream);
+/* The same step with per-tensor hyperparameters (parameter groups), still one update launch.
+ * group_hp: HOST array of n_groups rows (lr_base, warmup, t_total, b1, b2, eps, wd, max_norm), 1 <= n_groups <= 16; it is
+ * validated here and travels into the kernels by value, so nothing of the host's has to outlive the call or a captured
+ * graph.  tensor_group: device int32[n_tensors], the row of tensor t (an index outside 0..n_groups-1 counts as row 0).
+ * lr_dev: n_groups device floats; with step_dev the schedule launch writes lr_dev[g] for every row from the one shared
+ * *step_dev, without it the caller's lr_dev[g] are used.  The norm pass runs iff any row has max_norm > 0 and then covers
+ * every tensor, as does its non-finite flag; a tensor is clipped iff its own row's max_norm > 0; the skip is global and
+ * *step_dev advances once per applied step.  ema and ema_omd_dev may be NULL together: no average, ema_decay / ema_warm
+ * ignored.  Within every chunk of a tensor of row g the call writes bit for bit what tell_bertadam_step2 (tell_bertadam_
+ * step_ema with an average) writes when called with row g's eight values.  Refused (negative code, nothing launched,
+ * nothing written): n_groups outside 1..16, tensor_group / group_hp / lr_dev NULL, a row with eps <= 0, one of ema /
+ * ema_omd_dev NULL and the other not, and whatever tell_bertadam_step_ema refuses. */
+int tell_bertadam_step_groups(float* param, float* grad, float* m, float* v, const int* chunk_tensor,
+                              const long* chunk_begin, long n_chunks, int n_tensors, float* partial, float* norms,
+                              float* lr_dev, const int* tensor_group, const float* group_hp, int n_groups,
+                              float grad_scale, void* shadow_bf16, int zero_grad, int* skip, const void* grad_wire_bf16,
+                              int* step_dev, const int* keep_grad, float* ema, float* ema_omd_dev, float ema_decay,
+                              float ema_warm, tell_stream_t stream);
 /* One pass over n elements (a whole number of tell_opt_chunk() chunks): param and ema exchange values, shadow_bf16 (may
  * be NULL) becomes the round-to-nearest-even bf16 of the new param.  Applied twice it restores all three buffers bit for
  * bit.  Values move and no pointer changes, so captured graphs that hold these buffers stay valid.  param, ema 16-byte

@@ -99,6 +99,33 @@ __global__ void lr_schedule_kernel(const int* __restrict__ step, float lr, float
   }
   lr_dev[0] = (float)((double)lr * f);
 }
+// Parameter groups: up to TELL_ADAM_MAX_GROUPS rows of (lr_base, warmup, t_total, b1, b2, eps, wd,
+// max_norm), handed to the kernels BY VALUE - 512 B of kernel arguments, so a replayed graph needs nothing of the host's -
+// and tensor_group[t], the row of tensor t.  A chunk belongs to one tensor, hence to one row: everything read from the
+// table is uniform across the workgroup.
+#define TELL_ADAM_MAX_GROUPS 16
+enum { HP_LR = 0, HP_WARMUP, HP_T_TOTAL, HP_B1, HP_B2, HP_EPS, HP_WD, HP_MAX_NORM, HP_COLS };
+struct GroupTable {
+  float row[TELL_ADAM_MAX_GROUPS][HP_COLS];
+};
+struct GroupArgs {
+  const int* tensor_group;
+  int n_groups;
+  GroupTable hp;
+};
+// lr_dev[g] = lr_schedule_kernel's value for row g from the one shared step counter: one thread per group
+__global__ void lr_schedule_groups_kernel(const int* __restrict__ step, GroupTable hp, int n_groups,
+                                          float* __restrict__ lr_dev) {
+  const int g = threadIdx.x;
+  if (g >= n_groups) return;
+  const float lr = hp.row[g][HP_LR], warmup = hp.row[g][HP_WARMUP], t_total = hp.row[g][HP_T_TOTAL];
+  double f = 1.0;
+  if (t_total > 0.f) {
+    const double x = (double)step[0] / (double)t_total, w = (double)warmup;
+    f = x < w ? x / w : fmax((x - 1.0) / (w - 1.0), 0.0);
+  }
+  lr_dev[g] = (float)((double)lr * f);
+}
 // Exponential moving average of the masters: this step's 1 - d_t from the same count of APPLIED
 // updates n = *step (read before the update kernel increments it), d_t = min(decay, (1 + n) / (warm + n)) - the average
 // follows the weights closely while there are few of them.  warm <= 0 or no device counter: d_t = decay.  In double from
@@ -124,11 +151,23 @@ __global__ void ema_schedule_kernel(const int* __restrict__ step, float decay, f
 // the recorded profiles look for it), its kernel arguments and, instruction for instruction, its code; an unused pointer
 // pair at the end of the argument list, or the body inlined into two wrapper kernels, changed the register allocation
 // of all five.
+// Groups (a GroupArgs as the last trailing argument, after the EmaArgs when both are there): lr, b1, b2, eps, wd and max_norm
+// of a chunk come from the row of its tensor - lr from lr_dev[row] - instead of the scalar arguments, which are then not
+// read.  The index loads go out with the iteration's other loads; an index outside the table counts as row 0.
 struct EmaArgs {
   float* ema;
   const float* omd_dev;
 };
-template <int U, bool NT, typename... Ema>
+template <typename T>
+__device__ __forceinline__ const T* trailing_arg() { return nullptr; }
+template <typename T, typename A, typename... R>
+__device__ __forceinline__ const T* trailing_arg(const A& a, const R&... rest) {
+  if constexpr (std::is_same<T, A>::value) return &a;
+  else return trailing_arg<T>(rest...);
+}
+template <typename T, typename... Ts>
+constexpr int count_of = (0 + ... + (std::is_same<T, Ts>::value ? 1 : 0));
+template <int U, bool NT, typename... Ext>
 __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict__ param,
                                                               float* __restrict__ grad,
                                                               float* __restrict__ m, float* __restrict__ v,
@@ -140,19 +179,29 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
                                                               int zero_grad, int* __restrict__ skip,
                                                               const uint16_t* __restrict__ wire,
                                                               int* __restrict__ step_dev,
-                                                              const int* __restrict__ keep_grad, Ema... ema_args) {
-  static_assert(sizeof...(Ema) == 0 || (sizeof...(Ema) == 1 && (std::is_same<Ema, EmaArgs>::value && ...)),
-                "the optional trailing argument is one EmaArgs");
-  constexpr bool EMA = sizeof...(Ema) == 1;
+                                                              const int* __restrict__ keep_grad, Ext... ext) {
+  constexpr bool EMA = count_of<EmaArgs, Ext...> == 1, GROUPS = count_of<GroupArgs, Ext...> == 1;
+  static_assert(sizeof...(Ext) == (EMA ? 1 : 0) + (GROUPS ? 1 : 0),
+                "the optional trailing arguments are one EmaArgs, one GroupArgs, or both in that order");
   typedef __attribute__((ext_vector_type(4))) float f4;
-  const float lr = *lr_dev;
+  struct Hp { float lr, b1, b2, eps, wd, max_norm; };
+  Hp one = {0.f, b1, b2, eps, wd, max_norm};
+  if constexpr (!GROUPS) one.lr = *lr_dev;
   float* ema = nullptr;
   float omd = 0.f;
-  if constexpr (EMA) {
-    const EmaArgs ea[] = {ema_args...};
+  // (the EMA-only forms keep the spelling they had, and the lookup below is compiled only with groups: taking a reference to
+  //  the EmaArgs in trailing_arg gave those five other register numbers and another schedule - DESIGN.md section 32)
+  if constexpr (EMA && !GROUPS) {
+    const EmaArgs ea[] = {ext...};
     ema = ea[0].ema;
     omd = *ea[0].omd_dev;
+  } else if constexpr (EMA) {
+    const EmaArgs* ea = trailing_arg<EmaArgs>(ext...);
+    ema = ea->ema;
+    omd = *ea->omd_dev;
   }
+  const GroupArgs* ga = nullptr;
+  if constexpr (GROUPS) ga = trailing_arg<GroupArgs>(ext...);
   // keep_grad[t] != 0: tensor t's gradient is rewritten whole (beta = 0 stores) by its single producer in the next
   // backward pass - not zeroed here (4 B / parameter less to write, and the producer does not read it back)
   if (skip && skip[0] != 0) {      // non-finite loss or gradient: leave p, m, v and the shadow alone, only clear the gradient
@@ -175,7 +224,8 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
   for (long c0 = (long)blockIdx.x * U; c0 < n_chunks; c0 += (long)gridDim.x * U) {
     f4 g[U], p[U], mm[U], vv[U], e[EMA ? U : 1];
     float coef[U];
-    int tensor[U];
+    int tensor[U], group[GROUPS ? U : 1];
+    Hp hp[GROUPS ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long c = c0 + u < n_chunks ? c0 + u : n_chunks - 1;               // (clamped: the tail repeats the last chunk's loads)
@@ -185,9 +235,16 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
       p[u] = ldf(param, o); mm[u] = ldf(m, o); vv[u] = ldf(v, o);
       if constexpr (EMA) e[u] = ldf(ema, o);
       tensor[u] = chunk_tensor[c];
+      if constexpr (GROUPS) group[u] = ga->tensor_group[tensor[u]];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      if constexpr (GROUPS) {
+        const int gi = (unsigned)group[u] < (unsigned)ga->n_groups ? group[u] : 0;
+        const float* row = ga->hp.row[gi];
+        hp[u] = Hp{lr_dev[gi], row[HP_B1], row[HP_B2], row[HP_EPS], row[HP_WD], row[HP_MAX_NORM]};
+      }
+      const float max_norm = GROUPS ? hp[GROUPS ? u : 0].max_norm : one.max_norm;
       coef[u] = grad_scale;
       if (max_norm > 0.f) {
         const float cc = max_norm / (norms[tensor[u]] + 1e-6f);
@@ -198,6 +255,8 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
     for (int u = 0; u < U; ++u) {
       if (c0 + u >= n_chunks) break;
       const long o = (c0 + u) * OPT_CHUNK / 4 + threadIdx.x;
+      const Hp h = GROUPS ? hp[GROUPS ? u : 0] : one;
+      const float lr = h.lr, b1 = h.b1, b2 = h.b2, eps = h.eps, wd = h.wd;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         // Every multiply-add spelled out, none left to the compiler's contraction: written as plain expressions the
@@ -265,13 +324,14 @@ extern "C" int tell_opt_chunk(void) { return OPT_CHUNK; }
 // workspace `partial`: n_chunks floats; `norms`: n_tensors floats
 // keep_grad: device int32[n_tensors] or NULL - tensors whose gradient the zeroing leaves alone (see the kernel)
 // EMA: tell_bertadam_step_ema - the moving average `ema` and the device scalar `omd_dev` join the update launch
+// groups (host, may be NULL): tell_bertadam_step_groups - the table replaces b1 .. max_norm and lr_base .. t_total
 template <bool EMA>
 static int bertadam_launch(float* param, float* grad, float* m, float* v, const int* chunk_tensor, const long* chunk_begin,
                            long n_chunks, int n_tensors, float* partial, float* norms, const float* lr_dev, float b1, float b2,
                            float eps, float wd, float max_norm, float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
                            const void* grad_wire_bf16, int* step_dev, float lr_base, float warmup, float t_total,
                            const int* keep_grad, float* ema, float* omd_dev, float ema_decay, float ema_warm,
-                           hipStream_t stream) {
+                           const GroupArgs* groups, hipStream_t stream) {
   if (n_chunks <= 0) return TELL_OK;
   if (EMA) {
     TELL_REQUIRE(ema && omd_dev, "bertadam: ema and ema_omd_dev must not be NULL");
@@ -287,10 +347,23 @@ static int bertadam_launch(float* param, float* grad, float* m, float* v, const 
                    ((uintptr_t)v & 15) == 0,
                "bertadam: buffers must be 16-byte aligned");
   // eps = 0: the zero padding between tensors (m = v = 0) would become 0 / 0 in the master and the shadow
-  TELL_REQUIRE(eps > 0.f, "bertadam: eps must be positive");
-  if (step_dev)      // device-side schedule: this step's learning rate from the count of updates applied so far
-    hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, lr_base, warmup, t_total,
-                       const_cast<float*>(lr_dev));
+  if (groups) {      // the norm pass runs iff any row clips; it then covers every tensor, and so does its non-finite flag
+    max_norm = 0.f;
+    for (int i = 0; i < groups->n_groups; ++i) {
+      TELL_REQUIRE(groups->hp.row[i][HP_EPS] > 0.f, "bertadam: eps must be positive in every group");
+      if (groups->hp.row[i][HP_MAX_NORM] > 0.f) max_norm = groups->hp.row[i][HP_MAX_NORM];
+    }
+  } else {
+    TELL_REQUIRE(eps > 0.f, "bertadam: eps must be positive");
+  }
+  if (step_dev) {    // device-side schedule: this step's learning rate from the count of updates applied so far
+    if (groups)
+      hipLaunchKernelGGL(lr_schedule_groups_kernel, dim3(1), dim3(TELL_ADAM_MAX_GROUPS), 0, stream, step_dev, groups->hp,
+                         groups->n_groups, const_cast<float*>(lr_dev));
+    else
+      hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, lr_base, warmup, t_total,
+                         const_cast<float*>(lr_dev));
+  }
   if (EMA) hipLaunchKernelGGL(ema_schedule_kernel, dim3(1), dim3(1), 0, stream, step_dev, ema_decay, ema_warm, omd_dev);
   // TELL_ADAM_VAR (A/B aid, read once): 0 = one chunk per iteration, default cache policy (the round-4 kernel's shape);
   // 1 = U 2; 2 = U 4; 3 = U 2 + non-temporal; 4 = U 4 + non-temporal.  tools/probes/stream_probe.hip has the same shapes
@@ -308,7 +381,15 @@ static int bertadam_launch(float* param, float* grad, float* m, float* v, const 
   }
 #define TELL_ADAM_LAUNCH(UU, NTT)                                                                                               \
   do {                                                                                                                        \
-    if (EMA)                                                                                                                  \
+    if (EMA && groups)                                                                                                        \
+      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, EmaArgs, GroupArgs>), dim3(g), dim3(256), 0, stream, param, grad, m,  \
+                         v, chunk_tensor, norms, n_chunks, lr_dev, 0.f, 0.f, 0.f, 0.f, 0.f, grad_scale,                        \
+                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, EmaArgs{ema, omd_dev}, *groups);  \
+    else if (groups)                                                                                                          \
+      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, GroupArgs>), dim3(g), dim3(256), 0, stream, param, grad, m, v,        \
+                         chunk_tensor, norms, n_chunks, lr_dev, 0.f, 0.f, 0.f, 0.f, 0.f, grad_scale,                          \
+                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, *groups);                         \
+    else if (EMA)                                                                                                             \
       hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, EmaArgs>), dim3(g), dim3(256), 0, stream, param, grad, m, v,              \
                          chunk_tensor, norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale,                        \
                          (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, EmaArgs{ema, omd_dev});           \
@@ -336,7 +417,7 @@ extern "C" int tell_bertadam_step2(float* param, float* grad, float* m, float* v
                                    const int* keep_grad, hipStream_t stream) {
   return bertadam_launch<false>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev, b1,
                                 b2, eps, wd, max_norm, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev,
-                                lr_base, warmup, t_total, keep_grad, nullptr, nullptr, 0.f, 0.f, stream);
+                                lr_base, warmup, t_total, keep_grad, nullptr, nullptr, 0.f, 0.f, nullptr, stream);
 }
 extern "C" int tell_bertadam_step_ema(float* param, float* grad, float* m, float* v,
                                       const int* chunk_tensor, const long* chunk_begin, long n_chunks,
@@ -348,7 +429,29 @@ extern "C" int tell_bertadam_step_ema(float* param, float* grad, float* m, float
                                       hipStream_t stream) {
   return bertadam_launch<true>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev, b1,
                                b2, eps, wd, max_norm, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev,
-                               lr_base, warmup, t_total, keep_grad, ema, ema_omd_dev, ema_decay, ema_warm, stream);
+                               lr_base, warmup, t_total, keep_grad, ema, ema_omd_dev, ema_decay, ema_warm, nullptr, stream);
+}
+extern "C" int tell_bertadam_step_groups(float* param, float* grad, float* m, float* v, const int* chunk_tensor,
+                                         const long* chunk_begin, long n_chunks, int n_tensors, float* partial, float* norms,
+                                         float* lr_dev, const int* tensor_group, const float* group_hp, int n_groups,
+                                         float grad_scale, void* shadow_bf16, int zero_grad, int* skip,
+                                         const void* grad_wire_bf16, int* step_dev, const int* keep_grad, float* ema,
+                                         float* ema_omd_dev, float ema_decay, float ema_warm, hipStream_t stream) {
+  if (n_chunks <= 0) return TELL_OK;
+  TELL_REQUIRE(n_groups >= 1 && n_groups <= TELL_ADAM_MAX_GROUPS, "bertadam: n_groups must be in 1..16");
+  TELL_REQUIRE(tensor_group && group_hp && lr_dev, "bertadam: tensor_group, group_hp and lr_dev must not be NULL");
+  TELL_REQUIRE((ema == nullptr) == (ema_omd_dev == nullptr), "bertadam: ema and ema_omd_dev must be given together");
+  GroupArgs ga = {};          // (rows past n_groups stay 0: the kernels never index them)
+  ga.tensor_group = tensor_group;
+  ga.n_groups = n_groups;
+  for (int i = 0; i < n_groups * HP_COLS; ++i) ga.hp.row[i / HP_COLS][i % HP_COLS] = group_hp[i];
+  if (ema)
+    return bertadam_launch<true>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev,
+                                 0.f, 0.f, 0.f, 0.f, 0.f, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev,
+                                 0.f, 0.f, 0.f, keep_grad, ema, ema_omd_dev, ema_decay, ema_warm, &ga, stream);
+  return bertadam_launch<false>(param, grad, m, v, chunk_tensor, chunk_begin, n_chunks, n_tensors, partial, norms, lr_dev, 0.f,
+                                0.f, 0.f, 0.f, 0.f, grad_scale, shadow_bf16, zero_grad, skip, grad_wire_bf16, step_dev, 0.f,
+                                0.f, 0.f, keep_grad, nullptr, nullptr, 0.f, 0.f, &ga, stream);
 }
 extern "C" int tell_bertadam_step(float* param, float* grad, float* m, float* v,
                                   const int* chunk_tensor, const long* chunk_begin, long n_chunks,

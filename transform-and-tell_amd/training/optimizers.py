@@ -3,6 +3,7 @@ multi-tensor HIP kernel over flat fp32 buffers.  Update rule restated from
 pytorch_pretrained_bert.BertAdam (third-party, absent here; parity unpinned):
 per-tensor gradient-norm clipping, no bias correction, decoupled-style weight decay added
 to the update, `warmup_linear` schedule evaluated at the step count BEFORE the increment."""
+import ctypes
 import math
 import re
 import warnings
@@ -18,6 +19,74 @@ def warmup_linear(progress, warmup):
     if progress < warmup:
         return progress / warmup
     return max((progress - 1.0) / (warmup - 1.0), 0.0)
+
+
+# what a parameter group may override, in the order of a row of tell_bertadam_step_groups' table (include/tell_hip.h)
+GROUP_KEYS = ('lr', 'warmup', 't_total', 'b1', 'b2', 'e', 'weight_decay', 'max_grad_norm')
+MAX_GROUPS = 16
+
+
+def resolve_parameter_groups(names, defaults, parameter_groups):
+    """AllenNLP's `parameter_groups` ([[regex, ...], {overrides}] per group) over the tensor names of a FlatParams.
+    A tensor belongs to the FIRST listed group of which any regex matches its name (re.search); one that no regex matches
+    belongs to the default group, which carries `defaults` (the constructor's own eight values).  A group inherits what
+    it does not override; listed groups that end up empty are dropped; groups whose eight values are equal are merged.
+    -> (groups, tensor_group): groups a list of dicts (GROUP_KEYS + 'names'), listed ones first in their order, the
+    default group last; tensor_group[i] the index into it of names[i]."""
+    listed = []
+    for gi, entry in enumerate(parameter_groups or []):
+        try:
+            regexes, overrides = entry
+            regexes, overrides = list(regexes), dict(overrides)
+        except (TypeError, ValueError):
+            raise ValueError('bert_adam: parameter_groups[%d] must be [[regex, ...], {overrides}], got %r' % (gi, entry))
+        values = dict(defaults)
+        for key, value in overrides.items():
+            where = 'bert_adam: parameter_groups[%d], key %r: ' % (gi, key)
+            if key == 'schedule':
+                if value != 'warmup_linear':
+                    raise ValueError(where + "only 'warmup_linear' is implemented, got %r" % (value,))
+                continue
+            if key not in GROUP_KEYS:
+                raise ValueError(where + 'not a key a group can override (%s)' % ', '.join(GROUP_KEYS))
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+                raise ValueError(where + 'must be a finite number, got %r' % (value,))
+            if key == 'e' and not ctypes.c_float(value).value > 0:
+                raise ValueError(where + 'must be positive as an fp32 number, got %r' % (value,))
+            if key in ('b1', 'b2') and not 0.0 <= value <= 1.0:
+                raise ValueError(where + 'must be in [0, 1], got %r' % (value,))
+            values[key] = value
+        listed.append((regexes, values))
+    used = {rx: False for regexes, _ in listed for rx in regexes}
+    members = [[] for _ in listed] + [[]]
+    for name in names:
+        home = len(listed)
+        for gi, (regexes, _) in enumerate(listed):
+            hit = [rx for rx in regexes if re.search(rx, name)]
+            for rx in hit:
+                used[rx] = True
+            if hit and home == len(listed):
+                home = gi
+        members[home].append(name)
+    for rx, hit in used.items():
+        if not hit:
+            warnings.warn('bert_adam: the parameter_groups regex %r matches no trainable tensor' % (rx,))
+    groups, index, group_of = [], {}, {}
+    for (_, values), mine in zip(listed + [(None, dict(defaults))], members):
+        if not mine:
+            continue
+        key = tuple(float(values[k]) for k in GROUP_KEYS)
+        if key not in index:
+            index[key] = len(groups)
+            groups.append(dict(values, names=[]))
+        for name in mine:
+            group_of[name] = index[key]
+    if len(groups) > MAX_GROUPS:
+        raise ValueError('bert_adam: parameter_groups resolve to %d distinct groups, the step kernel takes %d' %
+                         (len(groups), MAX_GROUPS))
+    for name in names:          # (a merged group keeps its tensors in the order of `names`)
+        groups[group_of[name]]['names'].append(name)
+    return groups or [dict(defaults, names=[])], [group_of[name] for name in names]
 
 
 class FlatParams:
@@ -78,7 +147,13 @@ class FlatParams:
         # exponential moving average of the masters and the device scalar 1 - d_t of the current step: allocated by
         # enable_ema (BertAdam(ema_decay=...)), absent otherwise
         self.ema = self.ema_omd = None
+        # device int32[n_tensors], the parameter group of every tensor: only with more than one group (set_tensor_group)
+        self.tensor_group = None
         rt.bump_weights_epoch()
+
+    def set_tensor_group(self, tensor_group):
+        assert len(tensor_group) == len(self.params)
+        self.tensor_group = torch.tensor(list(tensor_group), dtype=torch.int32).to(self.flat.device)
 
     def enable_ema(self):
         if self.ema is None:
@@ -133,7 +208,10 @@ class FlatParams:
 class BertAdam:
     def __init__(self, flat, lr=1e-4, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999,
                  e=1e-6, weight_decay=0.01, max_grad_norm=1.0, parameter_groups=None, ema_decay=None, ema_warmup=10.0):
-        """ema_decay (None: off): keep an exponential moving average of the fp32 masters in flat.ema, updated by the step
+        """parameter_groups: AllenNLP's [[regex, ...], {overrides}] list over flat.names (resolve_parameter_groups); with
+        more than one distinct group the step is tell_bertadam_step_groups - still one update launch, the hyperparameters
+        looked up per chunk - and with one it is the launch it always was.
+        ema_decay (None: off): keep an exponential moving average of the fp32 masters in flat.ema, updated by the step
         kernel itself with the decay d_t = min(ema_decay, (1 + n) / (ema_warmup + n)) after n applied updates
         (ema_warmup <= 0: always ema_decay); csrc/optim.hip, DESIGN.md section 31."""
         assert schedule == 'warmup_linear'
@@ -153,11 +231,19 @@ class BertAdam:
         self.b1, self.b2, self.e, self.weight_decay, self.max_grad_norm = b1, b2, e, weight_decay, max_grad_norm
         self.step_count = 0         # optimisation steps ISSUED by the host (incl. steps the device skipped)
         dev = flat.flat.device
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        defaults = dict(zip(GROUP_KEYS, (lr, warmup, t_total, b1, b2, e, weight_decay, max_grad_norm)))
+        self.groups, tensor_group = resolve_parameter_groups(flat.names, defaults, parameter_groups)
+        self._group_of = dict(zip(flat.names, tensor_group))
+        self.group_hp = None
+        if len(self.groups) > 1:        # the table of tell_bertadam_step_groups, a host array that it takes by value
+            flat.set_tensor_group(tensor_group)
+            self.group_hp = (ctypes.c_float * (len(GROUP_KEYS) * len(self.groups)))(
+                *[float(g[k]) for g in self.groups for k in GROUP_KEYS])
+        self.lr_dev = torch.zeros(len(self.groups), dtype=torch.float32, device=dev)     # one per group
         # updates APPLIED: advanced by the update kernel itself, only when the step is not skipped for a non-finite
         # loss / gradient; the learning rate of a step is computed from it on the device (csrc/optim.hip)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.parameter_groups = parameter_groups    # all groups of the configs carry `{}` overrides
+        self.parameter_groups = parameter_groups
         if ema_decay is not None:
             flat.enable_ema()
 
@@ -177,13 +263,31 @@ class BertAdam:
         """Updates applied so far = issued steps minus the skipped ones (one host sync)."""
         return int(self.step_dev.item())
 
-    def current_lr(self, step=None):
+    def group_of(self, name):
+        """index into self.groups of the tensor called `name` (one of flat.names)"""
+        return self._group_of[name]
+
+    def current_lr(self, step=None, group=None):
         """Learning rate of the step that follows `step` applied updates (default: the host's count of issued steps;
-        pass applied_steps() for what the device will actually use after skipped batches)."""
+        pass applied_steps() for what the device will actually use after skipped batches).  group: an index into
+        self.groups, or a regex - the group of the tensors whose names it matches; needed once there are several groups."""
         step = self.step_count if step is None else step
-        if self.t_total != -1:
-            return self.lr * warmup_linear(step / self.t_total, self.warmup)
-        return self.lr
+        if group is None:
+            if len(self.groups) > 1:
+                raise ValueError('bert_adam: there are %d parameter groups - current_lr() needs group=, a group index or '
+                                 'a regex over the tensor names' % len(self.groups))
+            group = 0
+        if isinstance(group, str):
+            hits = sorted({g for name, g in self._group_of.items() if re.search(group, name)})
+            if len(hits) != 1:
+                raise ValueError('bert_adam: the regex %r matches tensors of %d groups (%s), not of one' %
+                                 (group, len(hits), hits))
+            group = hits[0]
+        g = self.groups[group]
+        lr, warmup, t_total = g['lr'], g['warmup'], g['t_total']
+        if t_total != -1:
+            return lr * warmup_linear(step / t_total, warmup)
+        return lr
 
     def step(self, grad_scale=1.0, zero_grad=False, skip=None, grad_wire=None):
         """zero_grad: also clear the gradient buffer (fused into the update pass).  skip: device int32[2] flag -
@@ -207,10 +311,19 @@ class BertAdam:
         keep = f.keep_grad if (zero_grad and ops.grad_store_on()) else None
         if zero_grad:
             f.accum_pending = False
+        if len(self.groups) > 1:
+            ema = self.ema_decay is not None
+            hip.call('tell_bertadam_step_groups', f.flat, f.grad, f.m, f.v, f.chunk_tensor, f.chunk_begin, f.n_chunks,
+                     len(f.params), f.partial, f.norms, self.lr_dev, f.tensor_group, self.group_hp, len(self.groups),
+                     float(grad_scale), f.shadow, int(zero_grad), skip, grad_wire, self.step_dev, keep,
+                     f.ema if ema else None, f.ema_omd if ema else None, float(self.ema_decay) if ema else 0.0,
+                     float(self.ema_warmup) if ema else 0.0)
+            return
+        g = self.groups[0]          # (the constructor's own values, unless one overriding group holds every tensor)
         args = (f.flat, f.grad, f.m, f.v, f.chunk_tensor, f.chunk_begin, f.n_chunks,
-                len(f.params), f.partial, f.norms, self.lr_dev, self.b1, self.b2, self.e, self.weight_decay,
-                self.max_grad_norm, float(grad_scale), f.shadow, int(zero_grad), skip, grad_wire,
-                self.step_dev, float(self.lr), float(self.warmup), float(self.t_total), keep)
+                len(f.params), f.partial, f.norms, self.lr_dev, g['b1'], g['b2'], g['e'], g['weight_decay'],
+                g['max_grad_norm'], float(grad_scale), f.shadow, int(zero_grad), skip, grad_wire,
+                self.step_dev, float(g['lr']), float(g['warmup']), float(g['t_total']), keep)
         if self.ema_decay is None:
             hip.call('tell_bertadam_step2', *args)
         else:
