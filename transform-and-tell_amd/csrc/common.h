@@ -37,6 +37,28 @@ static inline int tell_check_launch(const char* what) {
     }                            \
   } while (0)
 
+// ---------------------------------------------------------------- narrow launch form
+// Option bw_wgs = G > 0: the step's long bandwidth-bound launches run as at most G workgroups of 1024 threads instead of
+// one 256-thread block per piece of work.  A dynamic LDS request of TELL_NARROW_LDS bytes (more than half a CU's 160 KB)
+// keeps it at one workgroup per CU, so such a launch occupies at most G CUs and the GEMM launches of the other streams
+// find the rest free.  A narrow workgroup walks the WIDE launch's 256-thread block indices ("virtual blocks"), one per
+// 256-thread quarter and trip: every block-level reduction sees the same elements in the same order, and the results are
+// bit-identical to the wide launch for any G.  No workgroup waits on another.
+#define TELL_NARROW_LDS (96 * 1024)
+template <typename... KA, typename... A>
+static inline void tell_launch_narrow(void (*kern)(KA...), long wgs, int threads, hipStream_t stream, A... args) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, TELL_NARROW_LDS);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(wgs < 1 ? 1 : wgs)), dim3(threads), TELL_NARROW_LDS, stream, args...);
+}
+// the 256-thread quarter of a narrow workgroup this wave belongs to, in a scalar register: what the wide kernels derive from
+// blockIdx.x (chunk and tensor indices, hyperparameters, row pointers) stays wave-uniform in the narrow ones
+__device__ __forceinline__ int tell_quarter() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)); }
+// workgroups of a narrow launch: G, but no more than the virtual blocks need at `per_wg` of them per trip
+static inline long tell_narrow_wgs(long G, long virtual_blocks, int per_wg = 4) {
+  const long need = (virtual_blocks + per_wg - 1) / per_wg;
+  return G < need ? G : need;
+}
+
 // ---------------------------------------------------------------- conversions
 __device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {  // round-to-nearest-even, NaN preserved

@@ -4,6 +4,7 @@
 // All loops are grid-stride over 16-byte chunks where the layout allows.
 #include "common.h"
 #include "gemm_common.h"    // gelu_erf2, pack2_bf16, u32x4
+#include "options.h"
 
 static inline int grid_for(long work, int per_block) {
   long g = (work + per_block - 1) / per_block;
@@ -316,14 +317,28 @@ struct WNMulti {
   unsigned store;                      // backward: bit i = tensor i's dg / dv are stored, not accumulated
 };
 template <typename OutT, bool BWD>
-__global__ __launch_bounds__(256) void wn_multi_kernel(WNMulti m) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= m.row_start[m.n]) return;
+__device__ __forceinline__ void wn_multi_row(const WNMulti& m, int row, int lane) {
   int i = 0;
   while (i + 1 < m.n && row >= m.row_start[i + 1]) ++i;       // wave-uniform
   const int r = row - m.row_start[i];
   if constexpr (BWD) wn_backward_row(m.a[i], m.g[i], m.v[i], m.norms[i], r, m.cols[i], m.dg[i], static_cast<float*>(m.w[i]), lane, (m.store >> i) & 1u);
   else wn_weight_row<OutT>(m.g[i], m.v[i], r, m.cols[i], static_cast<OutT*>(m.w[i]), m.norms[i], lane);
+}
+template <typename OutT, bool BWD>
+__global__ __launch_bounds__(256) void wn_multi_kernel(WNMulti m) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= m.row_start[m.n]) return;
+  wn_multi_row<OutT, BWD>(m, row, lane);
+}
+// Narrow form (common.h): a row is one wave's work with the same lanes in the same order whichever workgroup the wave is
+// in, so the waves of the few workgroups simply take the rows in turn.  Forward 1024 threads; backward 512, because its row
+// keeps 2 x 16 float4 in registers and a wave of a 1024-thread workgroup may have 128 in all.
+template <typename OutT, bool BWD, int THREADS>
+__global__ __launch_bounds__(THREADS) void wn_multi_narrow_kernel(WNMulti m) {
+  constexpr int W = THREADS / 64;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  for (long row = (long)blockIdx.x * W + wave; row < m.row_start[m.n]; row += (long)gridDim.x * W)
+    wn_multi_row<OutT, BWD>(m, (int)row, lane);
 }
 template <bool BWD>
 static int wn_multi_launch(int n, const void* const* a, const void* const* g, const void* const* v, void* const* w,
@@ -350,7 +365,13 @@ static int wn_multi_launch(int n, const void* const* a, const void* const* g, co
       if (BWD && store && store[j]) m.store |= 1u << i;
     }
     const dim3 grid((m.row_start[m.n] + 3) / 4);
-    if (BWD) hipLaunchKernelGGL((wn_multi_kernel<float, true>), grid, dim3(256), 0, stream, m);
+    const long G = tell_opt(OPT_BW_WGS);
+    if (G > 0) {
+      const int total = m.row_start[m.n];
+      if (BWD) tell_launch_narrow(wn_multi_narrow_kernel<float, true, 512>, tell_narrow_wgs(G, total, 8), 512, stream, m);
+      else if (out_dtype == TELL_BF16) tell_launch_narrow(wn_multi_narrow_kernel<uint16_t, false, 1024>, tell_narrow_wgs(G, total, 16), 1024, stream, m);
+      else tell_launch_narrow(wn_multi_narrow_kernel<float, false, 1024>, tell_narrow_wgs(G, total, 16), 1024, stream, m);
+    } else if (BWD) hipLaunchKernelGGL((wn_multi_kernel<float, true>), grid, dim3(256), 0, stream, m);
     else if (out_dtype == TELL_BF16) hipLaunchKernelGGL((wn_multi_kernel<uint16_t, false>), grid, dim3(256), 0, stream, m);
     else hipLaunchKernelGGL((wn_multi_kernel<float, false>), grid, dim3(256), 0, stream, m);
   }
@@ -588,10 +609,13 @@ extern "C" int tell_nan_rows(const float* x, int rows, int C, void* y, int out_d
 
 // ---------------------------------------------------------------- RoBERTa layer mix (transformer_faces_objects.py:355-364)
 // out[i] = sum_l softmax(w)[l] * H[l][i];   H is a contiguous stack [L][n]
+// Narrow forms (common.h), `*_narrow_kernel` below.  Forward: an output element is one thread's work and depends on nothing
+// else, so the same body runs under 1024-thread launch bounds over a short grid.  Backward: partial[b] is the reduction of
+// block b's elements in block b's order - quarter q of a narrow workgroup works as block vb0 + q of the wide launch's nvb
+// (a quarter past the last block loads nothing and stores nothing, but reaches the barriers).
 template <typename T>
-__global__ __launch_bounds__(256) void mix_fwd_kernel(const T* __restrict__ H, const float* __restrict__ w,
-                                                      int L, long n, T* __restrict__ out) {
-  __shared__ float sw[64];
+__device__ __forceinline__ void mix_fwd_body(const T* __restrict__ H, const float* __restrict__ w, int L, long n,
+                                             T* __restrict__ out, float* sw) {
   if (threadIdx.x < 64) {
     float v = threadIdx.x < L ? w[threadIdx.x] : -INFINITY;
     float m = wave_max(v);
@@ -608,31 +632,60 @@ __global__ __launch_bounds__(256) void mix_fwd_kernel(const T* __restrict__ H, c
     Elem<T>::st(out + i, acc);
   }
 }
-// partial[b][l] = sum over this block's elements of dOut[i] * H[l][i]
 template <typename T>
-__global__ __launch_bounds__(256) void mix_bwd_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
-                                                      int L, long n, float* __restrict__ partial) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ __launch_bounds__(256) void mix_fwd_kernel(const T* __restrict__ H, const float* __restrict__ w,
+                                                      int L, long n, T* __restrict__ out) {
+  __shared__ float sw[64];
+  mix_fwd_body<T>(H, w, L, n, out, sw);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void mix_fwd_narrow_kernel(const T* __restrict__ H, const float* __restrict__ w,
+                                                              int L, long n, T* __restrict__ out) {
+  __shared__ float sw[64];
+  mix_fwd_body<T>(H, w, L, n, out, sw);
+}
+// partial[b][l] = sum over this block's elements of dOut[i] * H[l][i]
+// (b of nb: the block's index and the number of blocks; tid: the thread's index in the block; red: the block's own LDS)
+template <typename T>
+__device__ __forceinline__ void mix_bwd_block(const T* __restrict__ H, const T* __restrict__ dOut, int L, long n,
+                                              float* __restrict__ partial, long b, long nb, int tid, bool active,
+                                              float (*red)[64]) {
+  const int lane = tid & 63, wave = tid >> 6;
   for (int l = 0; l < L; ++l) {
     float acc = 0.f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    for (long i = active ? b * 256 + tid : n; i < n; i += nb * 256)
       acc += Elem<T>::ld(dOut + i) * Elem<T>::ld(H + (long)l * n + i);
     acc = wave_sum(acc);
     if (lane == 0) red[wave][l] = acc;
   }
   __syncthreads();
-  if (threadIdx.x < L)
-    partial[(long)blockIdx.x * L + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if (active && tid < L) partial[b * L + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+template <typename T>
+__global__ __launch_bounds__(256) void mix_bwd_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
+                                                      int L, long n, float* __restrict__ partial) {
+  __shared__ float red[4][64];
+  mix_bwd_block<T>(H, dOut, L, n, partial, blockIdx.x, gridDim.x, threadIdx.x, true, red);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void mix_bwd_narrow_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
+                                                              int L, long n, float* __restrict__ partial, long nvb) {
+  __shared__ float red[4][4][64];
+  const int q = tell_quarter();
+  for (long vb0 = (long)blockIdx.x * 4; vb0 < nvb; vb0 += (long)gridDim.x * 4) {
+    mix_bwd_block<T>(H, dOut, L, n, partial, vb0 + q, nvb, threadIdx.x & 255, vb0 + q < nvb, red[q]);
+    __syncthreads();      // (red is written again in the next trip)
+  }
 }
 // 16-byte-chunk variants (L <= 32): every thread owns one chunk position and walks the L layers, so the stack is
 // streamed exactly once with 16 B per lane (HBM-bound: L*n elements read, n written / L*n + n read).
-template <typename T>
-__global__ __launch_bounds__(256) void mix_fwd_vec_kernel(const T* __restrict__ H, const float* __restrict__ w,
-                                                          int L, long n, T* __restrict__ out) {
+// Layers are loaded LB at a time: all 32 at once (128 registers of data, 213 in all) in the wide kernel; in batches of 8 in
+// the narrow one, whose waves have 128 registers in all (the compiler still starts the next batches' loads early: 115
+// registers, none spilled; batches of 12 or 16 spill).  The sum over the layers keeps its order.
+template <typename T, int LB>
+__device__ __forceinline__ void mix_fwd_vec_body(const T* __restrict__ H, const float* __restrict__ w, int L, long n,
+                                                 T* __restrict__ out, float* sw) {
   constexpr int VEC = Elem<T>::VEC;
-  __shared__ float sw[64];
   if (threadIdx.x < 64) {
     float v = threadIdx.x < L ? w[threadIdx.x] : -INFINITY;
     float m = wave_max(v);
@@ -647,36 +700,51 @@ __global__ __launch_bounds__(256) void mix_fwd_vec_kernel(const T* __restrict__ 
     // 840 MB stack at 3.9 TB/s where the backward kernel, whose loop is unrolled whole, reads the same stack at 4.8);
     // the stack is read once per step: non-temporal
     typedef __attribute__((ext_vector_type(4))) unsigned int u4;
-    u4 hv[32];
-#pragma unroll
-    for (int l = 0; l < 32; ++l)
-      if (l < L) hv[l] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(H + (long)l * n + i * VEC));
     float acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
 #pragma unroll
-    for (int l = 0; l < 32; ++l)
-      if (l < L) {
-        float v[VEC];
-        unpack16(make_uint4(hv[l][0], hv[l][1], hv[l][2], hv[l][3]), v, (const T*)nullptr);
-        const float wl = sw[l];
+    for (int l0 = 0; l0 < 32; l0 += LB) {
+      u4 hv[LB];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] += wl * v[k];
-      }
+      for (int l = 0; l < LB; ++l)
+        if (l0 + l < L) hv[l] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(H + (long)(l0 + l) * n + i * VEC));
+#pragma unroll
+      for (int l = 0; l < LB; ++l)
+        if (l0 + l < L) {
+          float v[VEC];
+          unpack16(make_uint4(hv[l][0], hv[l][1], hv[l][2], hv[l][3]), v, (const T*)nullptr);
+          const float wl = sw[l0 + l];
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) acc[k] += wl * v[k];
+        }
+    }
     *reinterpret_cast<uint4*>(out + i * VEC) = pack16(acc, (const T*)nullptr);
   }
 }
 template <typename T>
-__global__ __launch_bounds__(256) void mix_bwd_vec_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
-                                                          int L, long n, float* __restrict__ partial) {
+__global__ __launch_bounds__(256) void mix_fwd_vec_kernel(const T* __restrict__ H, const float* __restrict__ w,
+                                                          int L, long n, T* __restrict__ out) {
+  __shared__ float sw[64];
+  mix_fwd_vec_body<T, 32>(H, w, L, n, out, sw);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void mix_fwd_vec_narrow_kernel(const T* __restrict__ H, const float* __restrict__ w,
+                                                                 int L, long n, T* __restrict__ out) {
+  __shared__ float sw[64];
+  mix_fwd_vec_body<T, 8>(H, w, L, n, out, sw);
+}
+template <typename T>
+__device__ __forceinline__ void mix_bwd_vec_block(const T* __restrict__ H, const T* __restrict__ dOut, int L, long n,
+                                                  float* __restrict__ partial, long b, long nb, int tid, bool active,
+                                                  float (*red)[32]) {
   constexpr int VEC = Elem<T>::VEC;
-  __shared__ float red[4][32];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = tid & 63, wave = tid >> 6;
   float acc[32];
 #pragma unroll
   for (int l = 0; l < 32; ++l) acc[l] = 0.f;
   const long nv = n / VEC;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+  for (long i = active ? b * 256 + tid : nv; i < nv; i += nb * 256) {
     float d[VEC];
     unpack16(*reinterpret_cast<const uint4*>(dOut + i * VEC), d, (const T*)nullptr);
 #pragma unroll
@@ -697,19 +765,39 @@ __global__ __launch_bounds__(256) void mix_bwd_vec_kernel(const T* __restrict__ 
     if (lane == 0) red[wave][l] = a;
   }
   __syncthreads();
-  if (threadIdx.x < L)
-    partial[(long)blockIdx.x * L + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if (active && tid < L) partial[b * L + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+template <typename T>
+__global__ __launch_bounds__(256) void mix_bwd_vec_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
+                                                          int L, long n, float* __restrict__ partial) {
+  __shared__ float red[4][32];
+  mix_bwd_vec_block<T>(H, dOut, L, n, partial, blockIdx.x, gridDim.x, threadIdx.x, true, red);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void mix_bwd_vec_narrow_kernel(const T* __restrict__ H, const T* __restrict__ dOut,
+                                                                 int L, long n, float* __restrict__ partial, long nvb) {
+  __shared__ float red[4][4][32];
+  const int q = tell_quarter();
+  for (long vb0 = (long)blockIdx.x * 4; vb0 < nvb; vb0 += (long)gridDim.x * 4) {
+    mix_bwd_vec_block<T>(H, dOut, L, n, partial, vb0 + q, nvb, threadIdx.x & 255, vb0 + q < nvb, red[q]);
+    __syncthreads();      // (red is written again in the next trip)
+  }
 }
 extern "C" int tell_mix_fwd(const void* H, const float* w, int L, long n, void* out, int dtype,
                             hipStream_t stream) {
   TELL_REQUIRE(L >= 1 && L <= 64, "mix_fwd: L must be in [1,64]");
+  const long G = tell_opt(OPT_BW_WGS);
   if (L <= 32 && n % 8 == 0 && (((uintptr_t)H | (uintptr_t)out) & 15) == 0 && dtype == TELL_BF16) {
-    hipLaunchKernelGGL((mix_fwd_vec_kernel<uint16_t>), dim3(grid_for(n / 8, 256)), dim3(256), 0, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
+    const int gv = grid_for(n / 8, 256);
+    if (G > 0) tell_launch_narrow(mix_fwd_vec_narrow_kernel<uint16_t>, tell_narrow_wgs(G, gv), 1024, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
+    else hipLaunchKernelGGL((mix_fwd_vec_kernel<uint16_t>), dim3(gv), dim3(256), 0, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
     return tell_check_launch("mix_fwd_vec");
   }
   int g = grid_for(n, 256 * 4);
-  if (dtype == TELL_BF16) hipLaunchKernelGGL((mix_fwd_kernel<uint16_t>), dim3(g), dim3(256), 0, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
+  if (G > 0) {
+    if (dtype == TELL_BF16) tell_launch_narrow(mix_fwd_narrow_kernel<uint16_t>, tell_narrow_wgs(G, g), 1024, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
+    else tell_launch_narrow(mix_fwd_narrow_kernel<float>, tell_narrow_wgs(G, g), 1024, stream, (const float*)H, w, L, n, (float*)out);
+  } else if (dtype == TELL_BF16) hipLaunchKernelGGL((mix_fwd_kernel<uint16_t>), dim3(g), dim3(256), 0, stream, (const uint16_t*)H, w, L, n, (uint16_t*)out);
   else hipLaunchKernelGGL((mix_fwd_kernel<float>), dim3(g), dim3(256), 0, stream, (const float*)H, w, L, n, (float*)out);
   return tell_check_launch("mix_fwd");
 }
@@ -718,9 +806,16 @@ extern "C" int tell_mix_bwd(const void* H, const void* dOut, int L, long n, floa
                             int n_blocks, int dtype, hipStream_t stream) {
   TELL_REQUIRE(L >= 1 && L <= 64, "mix_bwd: L must be in [1,64]");
   TELL_REQUIRE(n_blocks >= 1, "mix_bwd: n_blocks");
+  const long G = tell_opt(OPT_BW_WGS), nvb = n_blocks;
   if (L <= 32 && n % 8 == 0 && (((uintptr_t)H | (uintptr_t)dOut) & 15) == 0 && dtype == TELL_BF16) {
-    hipLaunchKernelGGL((mix_bwd_vec_kernel<uint16_t>), dim3(n_blocks), dim3(256), 0, stream, (const uint16_t*)H, (const uint16_t*)dOut, L, n, partial);
+    if (G > 0) tell_launch_narrow(mix_bwd_vec_narrow_kernel<uint16_t>, tell_narrow_wgs(G, nvb), 1024, stream, (const uint16_t*)H, (const uint16_t*)dOut, L, n, partial, nvb);
+    else hipLaunchKernelGGL((mix_bwd_vec_kernel<uint16_t>), dim3(n_blocks), dim3(256), 0, stream, (const uint16_t*)H, (const uint16_t*)dOut, L, n, partial);
     return tell_check_launch("mix_bwd_vec");
+  }
+  if (G > 0) {
+    if (dtype == TELL_BF16) tell_launch_narrow(mix_bwd_narrow_kernel<uint16_t>, tell_narrow_wgs(G, nvb), 1024, stream, (const uint16_t*)H, (const uint16_t*)dOut, L, n, partial, nvb);
+    else tell_launch_narrow(mix_bwd_narrow_kernel<float>, tell_narrow_wgs(G, nvb), 1024, stream, (const float*)H, (const float*)dOut, L, n, partial, nvb);
+    return tell_check_launch("mix_bwd");
   }
   if (dtype == TELL_BF16) hipLaunchKernelGGL((mix_bwd_kernel<uint16_t>), dim3(n_blocks), dim3(256), 0, stream, (const uint16_t*)H, (const uint16_t*)dOut, L, n, partial);
   else hipLaunchKernelGGL((mix_bwd_kernel<float>), dim3(n_blocks), dim3(256), 0, stream, (const float*)H, (const float*)dOut, L, n, partial);

@@ -32,26 +32,52 @@ __device__ __forceinline__ float4 load_grad4(const float* __restrict__ grad, con
 }
 // U chunks per block iteration, every load of the iteration in flight before the first reduction (one chunk per iteration
 // left a block with a single 16-byte load outstanding per thread between two barriers)
+// One trip of one 256-thread block: chunks c0 .. c0 + U - 1 (those below n_chunks; none of them: two barriers and nothing
+// else).  tid: the thread's index in the block; red: the block's own U x 4 floats of LDS.
+template <int U>
+__device__ __forceinline__ void sqsum_chunks_trip(const float* __restrict__ grad, const uint16_t* __restrict__ wire,
+                                                  long n_chunks, float grad_scale, float* __restrict__ partial, long c0,
+                                                  int tid, float (*red)[4]) {
+  float4 g[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    g[u] = c0 + u < n_chunks ? load_grad4(grad, wire, (c0 + u) * OPT_CHUNK / 4 + tid) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    // Every multiply-add spelled out, none left to the compiler's contraction, which chose differently in the wide and the
+    // narrow kernel.  This is the arithmetic the wide kernel always had: the first chunk of a trip unfused, the others as
+    // one chain of multiply-adds that starts from y * y.
+#pragma clang fp contract(off)
+    float s;
+    if (u == 0) s = ((g[u].x * g[u].x + g[u].y * g[u].y) + g[u].z * g[u].z) + g[u].w * g[u].w;
+    else s = __builtin_fmaf(g[u].w, g[u].w, __builtin_fmaf(g[u].z, g[u].z, __builtin_fmaf(g[u].x, g[u].x, g[u].y * g[u].y)));
+    s = (s * grad_scale) * grad_scale;
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[u][tid >> 6] = s;
+  }
+  __syncthreads();
+  if (tid < U && c0 + tid < n_chunks) partial[c0 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+  __syncthreads();
+}
 template <int U>
 __global__ __launch_bounds__(256) void sqsum_chunks_kernel(const float* __restrict__ grad, const uint16_t* __restrict__ wire,
                                                            long n_chunks, float grad_scale, float* __restrict__ partial) {
   __shared__ float red[U][4];
-  for (long c0 = (long)blockIdx.x * U; c0 < n_chunks; c0 += (long)gridDim.x * U) {
-    float4 g[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      g[u] = c0 + u < n_chunks ? load_grad4(grad, wire, (c0 + u) * OPT_CHUNK / 4 + threadIdx.x) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float s = (g[u].x * g[u].x + g[u].y * g[u].y + g[u].z * g[u].z + g[u].w * g[u].w) * grad_scale * grad_scale;
-      s = wave_sum(s);
-      if ((threadIdx.x & 63) == 0) red[u][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < U && c0 + threadIdx.x < n_chunks)
-      partial[c0 + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    __syncthreads();
-  }
+  for (long c0 = (long)blockIdx.x * U; c0 < n_chunks; c0 += (long)gridDim.x * U)
+    sqsum_chunks_trip<U>(grad, wire, n_chunks, grad_scale, partial, c0, threadIdx.x, red);
+}
+// Narrow form (common.h): quarter q of a 1024-thread workgroup is virtual block vb0 + q of the wide launch's nvb.  The trip
+// count is that of vb0, the largest of the four, and a quarter with nothing left (or with no virtual block at all) runs its
+// trips past n_chunks: every thread reaches every barrier.
+template <int U>
+__global__ __launch_bounds__(1024) void sqsum_chunks_narrow_kernel(const float* __restrict__ grad,
+                                                                   const uint16_t* __restrict__ wire, long n_chunks,
+                                                                   float grad_scale, float* __restrict__ partial, long nvb) {
+  __shared__ float red[4][U][4];
+  const int q = tell_quarter(), tid = threadIdx.x & 255;
+  for (long vb0 = (long)blockIdx.x * 4; vb0 < nvb; vb0 += (long)gridDim.x * 4)
+    for (long c0 = vb0 * U; c0 < n_chunks; c0 += nvb * U)
+      sqsum_chunks_trip<U>(grad, wire, n_chunks, grad_scale, partial, vb0 + q < nvb ? c0 + q * U : n_chunks, tid, red[q]);
 }
 // norms[t] = sqrt(sum of the tensor's chunk partials); one 256-thread block per tensor, four loads in flight per thread,
 // partial sums folded in a fixed order (deterministic).  (One wave per tensor walked the 50 k chunks of the embedding
@@ -158,6 +184,13 @@ struct EmaArgs {
   float* ema;
   const float* omd_dev;
 };
+// Narrow form (common.h; a NarrowArgs as the FIRST trailing argument): 1024-thread workgroups, each 256-thread quarter takes
+// the wide launch's blocks quarter, quarter + 4 * gridDim.x, ... of nvb in turn and does with each what that block did.
+// There is no barrier in this kernel, so the quarters need not keep step.  Like the other two switches it is the presence
+// of an argument: the wide instantiations keep their names and their code.
+struct NarrowArgs {
+  long nvb;
+};
 template <typename T>
 __device__ __forceinline__ const T* trailing_arg() { return nullptr; }
 template <typename T, typename A, typename... R>
@@ -168,7 +201,7 @@ __device__ __forceinline__ const T* trailing_arg(const A& a, const R&... rest) {
 template <typename T, typename... Ts>
 constexpr int count_of = (0 + ... + (std::is_same<T, Ts>::value ? 1 : 0));
 template <int U, bool NT, typename... Ext>
-__global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict__ param,
+__global__ __launch_bounds__((count_of<NarrowArgs, Ext...> == 1 ? 1024 : 256)) void bertadam_update_kernel(float* __restrict__ param,
                                                               float* __restrict__ grad,
                                                               float* __restrict__ m, float* __restrict__ v,
                                                               const int* __restrict__ chunk_tensor,
@@ -181,8 +214,13 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
                                                               int* __restrict__ step_dev,
                                                               const int* __restrict__ keep_grad, Ext... ext) {
   constexpr bool EMA = count_of<EmaArgs, Ext...> == 1, GROUPS = count_of<GroupArgs, Ext...> == 1;
-  static_assert(sizeof...(Ext) == (EMA ? 1 : 0) + (GROUPS ? 1 : 0),
-                "the optional trailing arguments are one EmaArgs, one GroupArgs, or both in that order");
+  constexpr bool NARROW = count_of<NarrowArgs, Ext...> == 1;
+  static_assert(sizeof...(Ext) == (NARROW ? 1 : 0) + (EMA ? 1 : 0) + (GROUPS ? 1 : 0),
+                "the optional trailing arguments are one NarrowArgs, one EmaArgs, one GroupArgs, or several in that order");
+  // the block of the wide launch this thread works as, the thread's index in it, and the number of such blocks
+  const int tid = NARROW ? threadIdx.x & 255 : threadIdx.x;
+  long vb = NARROW ? (long)blockIdx.x * 4 + tell_quarter() : blockIdx.x, nvb = gridDim.x;
+  if constexpr (NARROW) nvb = trailing_arg<NarrowArgs>(ext...)->nvb;
   typedef __attribute__((ext_vector_type(4))) float f4;
   struct Hp { float lr, b1, b2, eps, wd, max_norm; };
   Hp one = {0.f, b1, b2, eps, wd, max_norm};
@@ -191,7 +229,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
   float omd = 0.f;
   // (the EMA-only forms keep the spelling they had, and the lookup below is compiled only with groups: taking a reference to
   //  the EmaArgs in trailing_arg gave those five other register numbers and another schedule - DESIGN.md section 32)
-  if constexpr (EMA && !GROUPS) {
+  if constexpr (EMA && !GROUPS && !NARROW) {
     const EmaArgs ea[] = {ext...};
     ema = ea[0].ema;
     omd = *ea[0].omd_dev;
@@ -207,9 +245,9 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
   if (skip && skip[0] != 0) {      // non-finite loss or gradient: leave p, m, v and the shadow alone, only clear the gradient
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(skip + 1, 1);          // running count of skipped steps
     if (zero_grad)
-      for (long c = blockIdx.x; c < n_chunks; c += gridDim.x)
+      for (long c = vb; c < n_chunks; c += NARROW ? (long)gridDim.x * 4 : nvb)
         if (!keep_grad || !keep_grad[chunk_tensor[c]])
-          reinterpret_cast<float4*>(grad)[c * OPT_CHUNK / 4 + threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+          reinterpret_cast<float4*>(grad)[c * OPT_CHUNK / 4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
   if (step_dev && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(step_dev, 1);   // (nobody reads it inside this launch)
@@ -221,7 +259,9 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
     f4* q = reinterpret_cast<f4*>(base) + o;
     if (NT) __builtin_nontemporal_store(val, q); else *q = val;
   };
-  for (long c0 = (long)blockIdx.x * U; c0 < n_chunks; c0 += (long)gridDim.x * U) {
+  if (NARROW && vb >= nvb) return;
+  do      // (wide: once)
+  for (long c0 = vb * U; c0 < n_chunks; c0 += nvb * U) {
     f4 g[U], p[U], mm[U], vv[U], e[EMA ? U : 1];
     float coef[U];
     int tensor[U], group[GROUPS ? U : 1];
@@ -229,7 +269,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long c = c0 + u < n_chunks ? c0 + u : n_chunks - 1;               // (clamped: the tail repeats the last chunk's loads)
-      const long o = c * OPT_CHUNK / 4 + threadIdx.x;
+      const long o = c * OPT_CHUNK / 4 + tid;
       if (wire) { const float4 w = load_grad4(grad, wire, o); g[u] = f4{w.x, w.y, w.z, w.w}; }
       else g[u] = ldf(grad, o);
       p[u] = ldf(param, o); mm[u] = ldf(m, o); vv[u] = ldf(v, o);
@@ -254,7 +294,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (c0 + u >= n_chunks) break;
-      const long o = (c0 + u) * OPT_CHUNK / 4 + threadIdx.x;
+      const long o = (c0 + u) * OPT_CHUNK / 4 + tid;
       const Hp h = GROUPS ? hp[GROUPS ? u : 0] : one;
       const float lr = h.lr, b1 = h.b1, b2 = h.b2, eps = h.eps, wd = h.wd;
 #pragma unroll
@@ -284,6 +324,7 @@ __global__ __launch_bounds__(256) void bertadam_update_kernel(float* __restrict_
       if (zero_grad && !(keep_grad && keep_grad[tensor[u]])) stf(grad, o, f4{0.f, 0.f, 0.f, 0.f});
     }
   }
+  while (NARROW && (vb += (long)gridDim.x * 4) < nvb);
 }
 
 // One pass that exchanges the masters with their moving average and rewrites the bf16 working copy from what is now in
@@ -325,6 +366,35 @@ extern "C" int tell_opt_chunk(void) { return OPT_CHUNK; }
 // keep_grad: device int32[n_tensors] or NULL - tensors whose gradient the zeroing leaves alone (see the kernel)
 // EMA: tell_bertadam_step_ema - the moving average `ema` and the device scalar `omd_dev` join the update launch
 // groups (host, may be NULL): tell_bertadam_step_groups - the table replaces b1 .. max_norm and lr_base .. t_total
+struct AdamFixed {        // the update kernel's arguments before the optional trailing ones, in its order
+  float *param, *grad, *m, *v;
+  const int* chunk_tensor;
+  const float* norms;
+  long n_chunks;
+  const float* lr_dev;
+  float b1, b2, eps, wd, max_norm, grad_scale;
+  uint16_t* shadow;
+  int zero_grad;
+  int* skip;
+  const uint16_t* wire;
+  int* step_dev;
+  const int* keep_grad;
+};
+// g blocks of 256 threads, or (option bw_wgs = G > 0) the same g blocks walked by at most G workgroups of 1024
+template <int U, bool NT, typename... Ext>
+static void adam_launch(long G, int g, hipStream_t stream, const AdamFixed& f, Ext... ext) {
+  if (G > 0) {
+    void (*kern)(float*, float*, float*, float*, const int*, const float*, long, const float*, float, float, float, float, float,
+                 float, uint16_t*, int, int*, const uint16_t*, int*, const int*, NarrowArgs, Ext...) =
+        bertadam_update_kernel<U, NT, NarrowArgs, Ext...>;
+    tell_launch_narrow(kern, tell_narrow_wgs(G, g), 1024, stream, f.param, f.grad, f.m, f.v, f.chunk_tensor, f.norms, f.n_chunks,
+                       f.lr_dev, f.b1, f.b2, f.eps, f.wd, f.max_norm, f.grad_scale, f.shadow, f.zero_grad, f.skip, f.wire,
+                       f.step_dev, f.keep_grad, NarrowArgs{g}, ext...);
+  } else
+    hipLaunchKernelGGL((bertadam_update_kernel<U, NT, Ext...>), dim3(g), dim3(256), 0, stream, f.param, f.grad, f.m, f.v,
+                       f.chunk_tensor, f.norms, f.n_chunks, f.lr_dev, f.b1, f.b2, f.eps, f.wd, f.max_norm, f.grad_scale,
+                       f.shadow, f.zero_grad, f.skip, f.wire, f.step_dev, f.keep_grad, ext...);
+}
 template <bool EMA>
 static int bertadam_launch(float* param, float* grad, float* m, float* v, const int* chunk_tensor, const long* chunk_begin,
                            long n_chunks, int n_tensors, float* partial, float* norms, const float* lr_dev, float b1, float b2,
@@ -373,30 +443,29 @@ static int bertadam_launch(float* param, float* grad, float* m, float* v, const 
   const int U = (var == 1 || var == 3) ? 2 : (var == 2 || var == 4) ? 4 : 1;
   const long iters = (n_chunks + U - 1) / U;
   int g = iters < grid_env ? (int)iters : grid_env;
+  const long G = tell_opt(OPT_BW_WGS);
   if (max_norm > 0.f) {
     const long it4 = (n_chunks + 3) / 4;
     const int gs = it4 < 4096 ? (int)it4 : 4096;
-    hipLaunchKernelGGL((sqsum_chunks_kernel<4>), dim3(gs), dim3(256), 0, stream, grad, wire, n_chunks, grad_scale, partial);
+    if (G > 0)
+      tell_launch_narrow(sqsum_chunks_narrow_kernel<4>, tell_narrow_wgs(G, gs), 1024, stream, grad, wire, n_chunks, grad_scale,
+                         partial, (long)gs);
+    else
+      hipLaunchKernelGGL((sqsum_chunks_kernel<4>), dim3(gs), dim3(256), 0, stream, grad, wire, n_chunks, grad_scale, partial);
     hipLaunchKernelGGL(tensor_norms_kernel, dim3(n_tensors), dim3(256), 0, stream, partial, chunk_begin, n_tensors, norms, skip);
   }
-#define TELL_ADAM_LAUNCH(UU, NTT)                                                                                               \
-  do {                                                                                                                        \
-    if (EMA && groups)                                                                                                        \
-      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, EmaArgs, GroupArgs>), dim3(g), dim3(256), 0, stream, param, grad, m,  \
-                         v, chunk_tensor, norms, n_chunks, lr_dev, 0.f, 0.f, 0.f, 0.f, 0.f, grad_scale,                        \
-                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, EmaArgs{ema, omd_dev}, *groups);  \
-    else if (groups)                                                                                                          \
-      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, GroupArgs>), dim3(g), dim3(256), 0, stream, param, grad, m, v,        \
-                         chunk_tensor, norms, n_chunks, lr_dev, 0.f, 0.f, 0.f, 0.f, 0.f, grad_scale,                          \
-                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, *groups);                         \
-    else if (EMA)                                                                                                             \
-      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT, EmaArgs>), dim3(g), dim3(256), 0, stream, param, grad, m, v,              \
-                         chunk_tensor, norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale,                        \
-                         (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad, EmaArgs{ema, omd_dev});           \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((bertadam_update_kernel<UU, NTT>), dim3(g), dim3(256), 0, stream, param, grad, m, v, chunk_tensor,   \
-                         norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale, (uint16_t*)shadow_bf16, zero_grad,   \
-                         skip, wire, step_dev, keep_grad);                                                                    \
+  const AdamFixed f = {param, grad, m, v, chunk_tensor, norms, n_chunks, lr_dev, b1, b2, eps, wd, max_norm, grad_scale,
+                       (uint16_t*)shadow_bf16, zero_grad, skip, wire, step_dev, keep_grad};
+  // (with groups the scalar hyperparameters are not read: b1 .. max_norm arrive as 0 from tell_bertadam_step_groups, and
+  //  max_norm, which the loop above set for the norm pass, goes to the kernel as 0 like them)
+#define TELL_ADAM_LAUNCH(UU, NTT)                                                                          \
+  do {                                                                                                     \
+    AdamFixed fg = f;                                                                                      \
+    fg.max_norm = 0.f;                                                                                     \
+    if (EMA && groups) adam_launch<UU, NTT>(G, g, stream, fg, EmaArgs{ema, omd_dev}, *groups);             \
+    else if (groups) adam_launch<UU, NTT>(G, g, stream, fg, *groups);                                      \
+    else if (EMA) adam_launch<UU, NTT>(G, g, stream, f, EmaArgs{ema, omd_dev});                            \
+    else adam_launch<UU, NTT>(G, g, stream, f);                                                            \
   } while (0)
   switch (var) {
     case 1: TELL_ADAM_LAUNCH(2, false); break;

@@ -48,6 +48,7 @@
   X(OPT_ARGMAX_REGS, "argmax_regs", 1)                                                                                  \
   X(OPT_ADAM_VAR, "adam_var", -1)          /* -1: the built-in default shape */                                         \
   X(OPT_ADAM_GRID, "adam_grid", 4096)                                                                                   \
+  X(OPT_BW_WGS, "bw_wgs", 0)               /* G > 0: BertAdam, its norm pass, the layer mix and the multi weight-norm launches as <= G one-per-CU workgroups (common.h) */ \
   X(OPT_SK_ROWS, "sk_rows", 0)             /* 128: 128-row skinny-linear workgroups above 64 rows (default: 32 rows everywhere) */ \
   X(OPT_SK_SPLIT, "sk_split", 0)           /* 1 / 2: share a long reduction of a skinny linear between 4 / 2 workgroups (split_ws) */ \
   X(OPT_SK_TALL_WAVES, "sk_tall_waves", 4) /* 8: the 128-row skinny workgroup as 8 waves x K / 8 */                   \

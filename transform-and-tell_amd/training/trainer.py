@@ -74,6 +74,18 @@ class Trainer:
             # with static tile lists for N = 8 / 16 / 32, -> 1498-1514 with the counters (1570 with no CU held).
             if 'TELL_Q4_DYNAMIC' not in os.environ:           # (an explicit choice at load time stands)
                 hip.set_option('q4_dynamic', 1)
+        # The step's long bandwidth-bound launches (BertAdam and its norm pass, the layer mix, the multi weight-norm
+        # launches) fill all 256 CUs while they run, and the next batch's RoBERTa GEMMs - one workgroup per CU - cannot
+        # start a tile meanwhile.  On the GPU the trainer issues them in the narrow form on at most 128 CUs (csrc/common.h,
+        # same results bit for bit) and lets the GEMMs claim their tiles from the per-XCD counters,
+        # so that they take whatever CUs are free.  MEASURED (bench.py, profiles/narrow_bw_bench.txt): 20.23 -> 19.62 ms per
+        # step.  Scoped to the train_one_batch calls that get a next_batch (launches recorded into the step / encoder
+        # graphs keep the choice they were captured with); an explicit TELL_BW_WGS / TELL_Q4_DYNAMIC at load time stands.
+        self._lib_options = {}
+        if torch.device(device).type == 'cuda':
+            for key, value in (('bw_wgs', 128), ('q4_dynamic', 1)):
+                if 'TELL_' + key.upper() not in os.environ:
+                    self._lib_options[key] = value
         if self.dp:
             # every rank draws its own dropout masks: the counter-hash seed is process-global with the same default on
             # all ranks; the rank is mixed in where the seed is READ (runtime.seed), not written into the global seed
@@ -221,7 +233,11 @@ class Trainer:
         weight, and BatchNorm running statistics are still updated in batch order on the encoder stream."""
         if self.optimizer.ema_swapped:
             raise RuntimeError('train_one_batch inside Trainer.ema_weights(): the masters sit in the EMA buffer')
-        with hip.bound_stream():
+        # (only with a next batch to encode underneath: alone the narrow launches are 1.3x slower and nothing fills the
+        #  CUs they leave - the decoder step alone 6.87 -> 7.48 ms)
+        overlapped = bool(self._lib_options) and next_batch is not None
+        scoped = hip.options(**self._lib_options) if overlapped else contextlib.nullcontext()
+        with hip.bound_stream(), scoped:
             return self._train_one_batch(batch, next_batch)
 
     def _encoded_for(self, batch):
