@@ -2,7 +2,8 @@
 entry points and template variants, its norm pass, the RoBERTa layer mix forward and backward and the two multi weight-norm
 launches write, with bw_wgs = 1 / 8 / 13 / 64, bit for bit what they write with bw_wgs = 0.  Nothing here has a tolerance:
 a narrow workgroup walks the wide launch's 256-thread blocks, so every reduction sees the same elements in the same order.
-The wide launch itself is held to float64 by the kernels' own test files.
+The wide launch itself is held to float64 by the kernels' own test files (BertAdam: tests/test_gpu_optim.py; mix and weight
+norm: tests/test_gpu_small_reduce.py).
 Run on the MI355X box:  python -m pytest tests/test_gpu_narrow_launch.py -m gpu"""
 import ctypes
 
