@@ -640,6 +640,7 @@ extern "C" int tell_layernorm_cat_fwd(int n, const void* const* x, long ld_x, co
   int rc = ln_cat_check(n, C, dtype, "fwd");
   if (rc) return rc;
   TELL_REQUIRE(p >= 0.f && p < 1.f, "layernorm_cat_fwd: p must be in [0,1)");
+  TELL_REQUIRE(res && y && mean && rstd, "layernorm_cat_fwd: res, y, mean and rstd are required");
   TELL_REQUIRE(ld_x % 8 == 0 && ld_r % 8 == 0 && ld_y % 8 == 0 && (((uintptr_t)res | (uintptr_t)y) & 15) == 0,
                "layernorm_cat_fwd: rows must be 16-byte aligned");
   LNCatArgs a;
@@ -669,6 +670,7 @@ extern "C" int tell_layernorm_cat_bwd(int n, const void* dcat, long ld_dcat, con
   int rc = ln_cat_check(n, C, dtype, "bwd");
   if (rc) return rc;
   TELL_REQUIRE(p >= 0.f && p < 1.f, "layernorm_cat_bwd: p must be in [0,1)");
+  TELL_REQUIRE(res && dcat && mean && rstd, "layernorm_cat_bwd: res, dcat, mean and rstd are required");
   TELL_REQUIRE(ld_x % 8 == 0 && ld_r % 8 == 0 && ld_dcat % 8 == 0 && ld_dx % 8 == 0 && ld_dres % 8 == 0 &&
                (((uintptr_t)res | (uintptr_t)dcat | (uintptr_t)dres) & 15) == 0,
                "layernorm_cat_bwd: rows must be 16-byte aligned");
