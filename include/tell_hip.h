@@ -657,6 +657,33 @@ int tell_adaptive_logprob_forced(const float* head, long ld_head, int c0, int n_
                                  int rows, int k, const long* prefix, long ld_prefix, int P, const int* plen,
                                  int n_samples, const int* row_ids, int beams, int step, const int* step_dev, int pad,
                                  int* tokens, float* lps, tell_stream_t stream);
+/* per-token statistics: runs BEHIND the step's pick launch - and behind tell_adaptive_logprob_forced
+ * when there is a prefix - over the same logits.  chosen int32 [rows, ld_chosen]: column 0 is the token the step took (the
+ * pick kernels' tokens buffer as it stands); finished uint8 [rows] or NULL; n = 1..8 alternatives.  The statistics are those
+ * of the MODEL'S OWN distribution (no temperature, penalty, mask or guidance), lp_t as tell_adaptive_logprob_argmax /
+ * tell_adaptive_logprob_topk compute it (head: head[t] - lse_h; tail i: tail[j] + ((head[c0 + i] - lse_h) - lse_i); maxima
+ * and sums in the order of the top-k kernel of the same form, option argmax_regs).  Slot s of the outputs is `step`, or
+ * *step_dev + 1 when step_dev is given (the device counter of a captured decode step - the convention of
+ * tell_adaptive_logprob_forced).  Row r, with c = chosen[r][0], writes
+ *   alt_tok int32 / alt_lp fp32 [slots, rows, n]: bit for bit what tell_adaptive_logprob_topk(k = n) returns on these buffers
+ *     (value descending, lower id first; (0x7fffffff, -inf) where the vocabulary has fewer than n tokens);
+ *   chosen_lp fp32 [slots, rows]: lp_c;
+ *   rank int32 [slots, rows]: #{t : lp_t > lp_c or (lp_t == lp_c and t < c)} on the kernel's own fp32 values, 0 = the arg-max;
+ *     so rank < n implies alt_tok[rank] == c and alt_lp[rank] == chosen_lp, and rank >= n that c is no alternative;
+ *   entropy fp32 [slots, rows], in nats, by the chain rule: per cluster H = log s - u / s with s = sum exp(x - m),
+ *     u = sum exp(x - m) * (x - m); H = H_head + sum_i exp(head[c0 + i] - lse_h) * H_tail_i; fp32 in a fixed order (a thread's
+ *     elements in static order, the wave, the waves).  Logits are finite; nothing is promised for +-inf.
+ * A row with finished[r] != 0 writes (pad, 0, -1, 0, 0) to (alt_tok, alt_lp, rank, entropy, chosen_lp) and requests no logit.
+ * c outside [0, V): rank = -1 and chosen_lp = 0; alternatives and entropy are still written.  With step_dev, a slot outside
+ * [0, slots) writes nothing.  Declined with a negative code and no launch: step outside [0, slots) without step_dev, n
+ * outside 1..8, rows < 1, n_tails > 3, a NULL output.  Synchronises nothing, allocates nothing.  Register form (one
+ * 1024-thread workgroup per row, the logits requested once) under the capacity rule of tell_adaptive_logprob_argmax;
+ * otherwise the streaming form on the streaming top-k kernel's 256 threads. */
+int tell_adaptive_logprob_stats(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                int rows, const int* chosen, long ld_chosen, const uint8_t* finished, int n, int slots,
+                                int step, const int* step_dev, int pad, int* alt_tok, float* alt_lp, int* rank,
+                                float* entropy, float* chosen_lp, tell_stream_t stream);
 /* top-k sampling with a temperature (transformer_faces_objects.py:38-55, 443-470: lprobs.topk(k), / T, torch.multinomial).
  * Per row r at step i with seed s:
  *   1. candidates: the k (1..64) largest log-probs of the full adaptive softmax, each computed as in

@@ -425,9 +425,43 @@ struct PenArgs { const int* tok; const int* cnt; long ld; const int* n_pen; cons
 struct NoPen {};
 __device__ __forceinline__ NoPen pen_pick() { return NoPen{}; }
 __device__ __forceinline__ const PenArgs& pen_pick(const PenArgs& a) { return a; }
-// the trailing argument of the top-k kernels: the ban list, or with PEN the penalty list
-template <bool PEN, bool MSK = false> struct ListOf { typedef BanArgs type; };
+// STA (tell_adaptive_logprob_stats, include/tell_hip.h): the K = 4 / 8 top-k form also counts the chosen
+// token's rank and sums the entropy terms while the row is in registers; outputs [slots, rows(, n)].
+struct StatsArgs {
+  const int* chosen; long ld_chosen; const uint8_t* finished;
+  int n, slots, step; const int* step_dev; int pad;
+  int* alt_tok; float* alt_lp; int* rank; float* entropy; float* chosen_lp;
+};
+// the trailing argument of the top-k kernels: the ban list, or with PEN the penalty list, or with STA the statistics' arguments
+template <bool PEN, bool MSK = false, bool STA = false> struct ListOf { typedef BanArgs type; };
 template <> struct ListOf<true, false> { typedef PenArgs type; };
+template <> struct ListOf<false, false, true> { typedef StatsArgs type; };
+// the slot of this step (`step`, or *step_dev + 1: the convention of tell_adaptive_logprob_forced), -1: nothing is written
+__device__ __forceinline__ int stats_slot(const StatsArgs& a) {
+  const int s = a.step_dev ? *a.step_dev + 1 : a.step;
+  return s < 0 || s >= a.slots ? -1 : s;
+}
+__device__ __forceinline__ void stats_neutral(const StatsArgs& a, long so) {      // a finished row: pad, 0, -1, 0, 0
+  for (int q = 0; q < a.n; ++q) { a.alt_tok[so * a.n + q] = a.pad; a.alt_lp[so * a.n + q] = 0.f; }
+  a.rank[so] = -1; a.entropy[so] = 0.f; a.chosen_lp[so] = 0.f;
+}
+// token t -> its segment (0 = head, c + 1 = tail c) and offset there; -1: outside the vocabulary
+__device__ __forceinline__ int stats_locate(const LogProbArgs& p, int t, int& local) {
+  local = t;
+  if (t < 0) return -1;
+  if (t < p.c0) return 0;
+  int base = p.c0;
+  for (int c = 0; c < p.n_tails; ++c) {
+    if (t < base + p.tail_n[c]) { local = t - base; return c + 1; }
+    base += p.tail_n[c];
+  }
+  return -1;
+}
+__device__ __forceinline__ float stats_term(float e, float d) { return e > 0.f ? e * d : 0.f; }   // (padding: 0 * -inf)
+// a wave-uniform value into a scalar register: the row's 64 VGPRs leave no room for the maxima, sums and offsets
+__device__ __forceinline__ float stats_uni(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
 #define PEN_MAX_LIST 256
 __device__ __forceinline__ int pen_count(const PenArgs& pa, int row) {
   const int np = pa.n_pen[row];
@@ -496,9 +530,9 @@ __device__ __forceinline__ void mask_stage(const MaskArgs& ma, int row) {
 }
 // (the register-resident kernel takes `ba` as a trailing argument that BAN = false never reads: its code stays the kernel's
 //  own, not an inlined body - this is the launch every greedy and beam step ends with)
-template <int K, bool BAN, bool PEN = false, bool MSK = false>
+template <int K, bool BAN, bool PEN = false, bool MSK = false, bool STA = false>
 __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k, int* __restrict__ tokens,
-                                                            float* __restrict__ lps, typename ListOf<PEN, MSK>::type ba) {
+                                                            float* __restrict__ lps, typename ListOf<PEN, MSK, STA>::type ba) {
   __shared__ float red[4][16];
   __shared__ float best_v[16];
   __shared__ int best_i[16];
@@ -511,6 +545,14 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
   for (int c = 0; c < 3; ++c) {
     rowp[c + 1] = c < p.n_tails ? p.tail[c] + (long)i * p.ld_tail[c] : rowp[0];
     n[c + 1] = c < p.n_tails ? p.tail_n[c] : 0;
+  }
+  [[maybe_unused]] long so = 0;                        // STA: (slot, row) in the [slots, rows] outputs
+  if constexpr (STA) {                                 // (uniform over the workgroup; a row that leaves requests no logit)
+    const int slot = stats_slot(ba);
+    if (slot < 0) return;
+    so = (long)slot * p.rows + i;
+    if (ba.finished && ba.finished[i]) { if (tid == 0) stats_neutral(ba, so); return; }
+    k = ba.n; tokens = ba.alt_tok + (long)slot * p.rows * k; lps = ba.alt_lp + (long)slot * p.rows * k;
   }
   int nb = 0;                                          // (requested before the row: its wait does not cover the row's loads)
   if constexpr (BAN) { nb = ba.n_ban[i]; nb = nb < 0 ? 0 : (nb > (int)ba.ld_ban ? (int)ba.ld_ban : nb); }
@@ -552,21 +594,31 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
     float m = red[s][0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) m = fmaxf(m, red[s][w]);
-    mx[s] = m;
+    mx[s] = STA ? stats_uni(m) : m;
   }
   __syncthreads();
+  [[maybe_unused]] float us[4] = {0.f, 0.f, 0.f, 0.f};  // STA: this wave's sum of exp(x - m) * (x - m), paired like the sum of exp(x - m)
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     float t = 0.f;
+    [[maybe_unused]] float u = 0.f;
     if (s < nseg) {
 #pragma unroll
       for (int q = 0; q < LPF_CAP[s]; ++q) {
         const f4 v = x[LPF_OFF[s] + q];
-        t += (__expf(v.x - mx[s]) + __expf(v.y - mx[s])) + (__expf(v.z - mx[s]) + __expf(v.w - mx[s]));
+        if constexpr (STA) {
+          const f4 d = {v.x - mx[s], v.y - mx[s], v.z - mx[s], v.w - mx[s]};
+          const f4 e = {__expf(d.x), __expf(d.y), __expf(d.z), __expf(d.w)};
+          t += (e.x + e.y) + (e.z + e.w);
+          u += (stats_term(e.x, d.x) + stats_term(e.y, d.y)) + (stats_term(e.z, d.z) + stats_term(e.w, d.w));
+        } else {
+          t += (__expf(v.x - mx[s]) + __expf(v.y - mx[s])) + (__expf(v.z - mx[s]) + __expf(v.w - mx[s]));
+        }
       }
     }
     t = wave_sum(t);
     if (lane == 0) red[s][wave] = t;
+    if constexpr (STA) us[s] = stats_uni(wave_sum(u));
   }
   __syncthreads();
 #pragma unroll
@@ -574,13 +626,56 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
     float t = 0.f;
 #pragma unroll
     for (int w = 0; w < 16; ++w) t += red[s][w];
-    sm[s] = t;
+    sm[s] = STA ? stats_uni(t) : t;
   }
-  const float lse_h = mx[0] + __logf(sm[0]);
+  const float lse_h = STA ? stats_uni(mx[0] + __logf(sm[0])) : mx[0] + __logf(sm[0]);
   float tv[K]; int ti[K];
 #pragma unroll
   for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
   auto better = [](float v, int j, float w, int m) { return v > w || (v == w && j < m); };
+  [[maybe_unused]] int ch = 0, ch_seg = -1, cnt = 0;   // STA: the chosen token, its segment, how many tokens come before it
+  [[maybe_unused]] float ch_lp = 0.f;
+  if constexpr (STA) {
+    __syncthreads();                                   // (red: the sums are consumed; thread 0 adds the waves' u at the end)
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (lane == 0) red[s][wave] = us[s];
+    ch = ba.chosen[(long)i * ba.ld_chosen];
+    int local;
+    ch_seg = stats_locate(p, ch, local);
+    if (ch_seg == 0) ch_lp = rowp[0][local] - lse_h;   // (the expressions of the scan below, on the same operands)
+#pragma unroll
+    for (int s = 1; s < 4; ++s)
+      if (s == ch_seg) ch_lp = rowp[s][local] + ((rowp[0][p.c0 + s - 1] - lse_h) - (mx[s] + __logf(sm[s])));
+    ch_lp = stats_uni(ch_lp);
+    // the rank count is a scan of its own, before the candidate lists exist (they would not fit next to it): the log-probs
+    // of the scan below, compared with the chosen token's
+    if (ch_seg >= 0) {
+#pragma unroll
+      for (int q = 0; q < LPF_CAP[0]; ++q) {
+        const int j = (q * 1024 + tid) * 4;
+        cnt += (j < p.c0 && better(x[q].x - lse_h, j, ch_lp, ch)) + (j + 1 < p.c0 && better(x[q].y - lse_h, j + 1, ch_lp, ch)) +
+               (j + 2 < p.c0 && better(x[q].z - lse_h, j + 2, ch_lp, ch)) + (j + 3 < p.c0 && better(x[q].w - lse_h, j + 3, ch_lp, ch));
+      }
+      int base = p.c0;
+#pragma unroll
+      for (int s = 1; s < 4; ++s) {
+        if (s < nseg) {
+          const float off = (rowp[0][p.c0 + s - 1] - lse_h) - (mx[s] + __logf(sm[s]));
+#pragma unroll
+          for (int q = 0; q < LPF_CAP[s]; ++q) {
+            const int j = (q * 1024 + tid) * 4;
+            const f4 v = x[LPF_OFF[s] + q];
+            cnt += (j < n[s] && better(v.x + off, base + j, ch_lp, ch)) + (j + 1 < n[s] && better(v.y + off, base + j + 1, ch_lp, ch)) +
+                   (j + 2 < n[s] && better(v.z + off, base + j + 2, ch_lp, ch)) + (j + 3 < n[s] && better(v.w + off, base + j + 3, ch_lp, ch));
+          }
+          base += n[s];
+        }
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    cnt = __builtin_amdgcn_readfirstlane(cnt);         // (this wave's count)
+  }
   auto consider = [&](float v, int j) {
     if (!better(v, j, tv[K - 1], ti[K - 1])) return;
     if (BAN && nb > 0 && ((ban_bits[j >> 5] >> (j & 31)) & 1u)) return;
@@ -622,6 +717,27 @@ __global__ __launch_bounds__(1024) void logprob_regs_kernel(LogProbArgs p, int k
         if (j + 3 < n[s]) consider(v.w + off, base + j + 3);
       }
       base += n[s];
+    }
+  }
+  if constexpr (STA) {                                 // rank: a thread's count, the wave (above), then the waves
+    if (lane == 0) best_i[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+      int total = 0;
+      for (int w = 0; w < 16; ++w) total += best_i[w];
+      float ut[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        ut[s] = 0.f;
+        for (int w = 0; w < 16; ++w) ut[s] += red[s][w];
+      }
+      float H = __logf(sm[0]) - ut[0] / sm[0];         // chain rule: the head, then every tail weighted by its cluster
+#pragma unroll
+      for (int s = 1; s < 4; ++s)
+        if (s < nseg) H += __expf(rowp[0][p.c0 + s - 1] - lse_h) * (__logf(sm[s]) - ut[s] / sm[s]);
+      ba.rank[so] = ch_seg >= 0 ? total : -1;
+      ba.chosen_lp[so] = ch_seg >= 0 ? ch_lp : 0.f;
+      ba.entropy[so] = H;
     }
   }
   for (int r = 0; r < k; ++r) {                       // pop the block-wide best k times (lowest index wins ties)
@@ -1111,6 +1227,115 @@ extern "C" int tell_adaptive_logprob_forced(const float* head, long ld_head, int
   }
   hipLaunchKernelGGL((logprob_forced_kernel<false>), dim3(rows), dim3(1024), 0, stream, p, a);
   return tell_check_launch("logprob_forced");
+}
+
+// ------------------------------------------------------------------ per-token statistics
+// Runs BEHIND the step's pick (and forced) launch over the same logits: the n best tokens of the model's own distribution,
+// the rank and log-prob of the token the step took (chosen[r][0]) and the row's entropy, into slot `step` of static buffers.
+// Register form: logprob_regs_kernel<8, ..., STA> above - the K = 8 top-k kernel itself, so the alternatives are its bits.
+// Streaming form (below): logprob_topk_body<8> writes the alternatives - the streaming top-k kernel's own code, hence ITS 256
+// threads and sum order -, then the same two passes per cluster once more with the entropy sum riding on the second, then one
+// pass that counts the rank.  Three more reads of the row than the register form: this is the fall-back for rows that do not
+// fit LPF_CAP or do not start on 16 bytes.
+__device__ __forceinline__ void stats_cluster_stream(const float* __restrict__ row, int n, float* red, float& lse, float& H) {
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < n; j += 256) mx = fmaxf(mx, row[j]);
+  mx = block_max(mx, red);
+  float s = 0.f, u = 0.f;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const float d = row[j] - mx, e = __expf(d);
+    s += e;
+    u += stats_term(e, d);
+  }
+  s = block_sum(s, red);
+  u = block_sum(u, red);
+  lse = mx + __logf(s);
+  H = __logf(s) - u / s;
+}
+__global__ __launch_bounds__(256) void logprob_stats_stream_kernel(LogProbArgs p, StatsArgs a) {
+  __shared__ float red[4];
+  __shared__ int cnt_w[4];
+  const int i = blockIdx.x;
+  const int slot = stats_slot(a);                              // (uniform over the workgroup, like everything up to the body)
+  if (slot < 0) return;
+  const long so = (long)slot * p.rows + i;
+  if (a.finished && a.finished[i]) { if (threadIdx.x == 0) stats_neutral(a, so); return; }
+  logprob_topk_body<8, false>(p, a.n, a.alt_tok + (long)slot * p.rows * a.n, a.alt_lp + (long)slot * p.rows * a.n,
+                              BanArgs{nullptr, 0, nullptr, 0});
+  __syncthreads();
+  const float* hrow = p.head + (long)i * p.ld_head;
+  float lse_h, H, off[3] = {0.f, 0.f, 0.f};
+  stats_cluster_stream(hrow, p.head_n, red, lse_h, H);
+  for (int c = 0; c < p.n_tails; ++c) {
+    float lse_t, H_t;
+    stats_cluster_stream(p.tail[c] + (long)i * p.ld_tail[c], p.tail_n[c], red, lse_t, H_t);
+    off[c] = (hrow[p.c0 + c] - lse_h) - lse_t;
+    H += __expf(hrow[p.c0 + c] - lse_h) * H_t;
+  }
+  const int ch = a.chosen[(long)i * a.ld_chosen];
+  int local;
+  const int seg = stats_locate(p, ch, local);
+  float ch_lp = 0.f;
+  if (seg == 0) ch_lp = hrow[local] - lse_h;
+  else if (seg > 0) ch_lp = p.tail[seg - 1][(long)i * p.ld_tail[seg - 1] + local] + off[seg - 1];
+  int cnt = 0;
+  if (seg >= 0) {
+    auto before = [&](float v, int j) { return v > ch_lp || (v == ch_lp && j < ch); };
+    for (int j = threadIdx.x; j < p.c0; j += 256) cnt += before(hrow[j] - lse_h, j) ? 1 : 0;
+    int base = p.c0;
+    for (int c = 0; c < p.n_tails; ++c) {
+      const float* trow = p.tail[c] + (long)i * p.ld_tail[c];
+      for (int j = threadIdx.x; j < p.tail_n[c]; j += 256) cnt += before(trow[j] + off[c], base + j) ? 1 : 0;
+      base += p.tail_n[c];
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) cnt_w[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.rank[so] = seg >= 0 ? (cnt_w[0] + cnt_w[1]) + (cnt_w[2] + cnt_w[3]) : -1;
+    a.chosen_lp[so] = seg >= 0 ? ch_lp : 0.f;
+    a.entropy[so] = H;
+  }
+}
+extern "C" int tell_adaptive_logprob_stats(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
+                                           int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
+                                           int rows, const int* chosen, long ld_chosen, const uint8_t* finished, int n,
+                                           int slots, int step, const int* step_dev, int pad, int* alt_tok, float* alt_lp,
+                                           int* rank, float* entropy, float* chosen_lp, hipStream_t stream) {
+  TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_stats: up to 3 tails");
+  TELL_REQUIRE(n >= 1 && n <= 8, "logprob_stats: 1 <= n <= 8 alternatives");
+  TELL_REQUIRE(rows >= 1, "logprob_stats: rows >= 1");
+  TELL_REQUIRE(chosen && ld_chosen >= 1, "logprob_stats: chosen int32 [rows, ld_chosen >= 1]");
+  TELL_REQUIRE(slots >= 1 && (step_dev || (step >= 0 && step < slots)), "logprob_stats: 0 <= step < slots");
+  TELL_REQUIRE(alt_tok && alt_lp && rank && entropy && chosen_lp,
+               "logprob_stats: alt_tok / alt_lp [slots, rows, n] and rank / entropy / chosen_lp [slots, rows]");
+  LogProbArgs p;
+  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
+  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n_tails > 0 ? n0 : 0;
+  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n_tails > 1 ? n1 : 0;
+  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n_tails > 2 ? n2 : 0;
+  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  StatsArgs a;
+  a.chosen = chosen; a.ld_chosen = ld_chosen; a.finished = finished; a.n = n; a.slots = slots; a.step = step;
+  a.step_dev = step_dev; a.pad = pad; a.alt_tok = alt_tok; a.alt_lp = alt_lp; a.rank = rank; a.entropy = entropy;
+  a.chosen_lp = chosen_lp;
+  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
+                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
+                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
+                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
+  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
+  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
+      (n_tails < 3 || n2 <= 2 * 4096)) {
+    // (K as tell_adaptive_logprob_topk picks it for k = n: the alternatives come from the same instantiation's code)
+    if (n <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, false, false, true>), dim3(rows), dim3(1024), 0, stream, p, n,
+                                   (int*)nullptr, (float*)nullptr, a);
+    else hipLaunchKernelGGL((logprob_regs_kernel<8, false, false, false, true>), dim3(rows), dim3(1024), 0, stream, p, n,
+                            (int*)nullptr, (float*)nullptr, a);
+    return tell_check_launch("logprob_stats (registers)");
+  }
+  hipLaunchKernelGGL(logprob_stats_stream_kernel, dim3(rows), dim3(256), 0, stream, p, a);
+  return tell_check_launch("logprob_stats");
 }
 
 // ------------------------------------------------------------------ top-k sampling with a temperature

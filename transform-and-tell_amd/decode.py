@@ -208,7 +208,8 @@ def embed_step(embedder, ids, start):
     return out.view(1, M, E)
 
 
-def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None, mask=None, guide=None):
+def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=None, force=None, pen=None, mask=None, guide=None,
+              stats=None):
     """Greedy head of a generation step (softmax.py:193-222 + topk(1)) as four launches: head logits | cluster logits |
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
@@ -220,7 +221,11 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     pen (ops._pen_args; with topk or sample): the last launch is tell_adaptive_logprob_topk_penalised / _sample_penalised.
     mask (ops._mask_args; with topk - a ban list may join it - or a top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked.
     guide = (pair_offset, gamma_dev) (context guidance; with topk alone): the last launch is
-    tell_adaptive_logprob_topk_guided over the N / 2 pairs of rows (r, r + pair_offset)."""
+    tell_adaptive_logprob_topk_guided over the N / 2 pairs of rows (r, r + pair_offset).
+    stats (a StatsSink; per-token statistics): one more launch behind the pick and the forced pick,
+    tell_adaptive_logprob_stats over the same logits and the tokens as they then stand (ops.logprob_stats) - on both layouts."""
+    if stats is not None and guide is not None:
+        raise ValueError('head_step: token statistics do not combine with guidance (paired rows)')
     if guide is not None and (not topk or sample is not None or ban is not None or force is not None or pen is not None or
                               mask is not None):
         raise ValueError('head_step: guidance goes with topk = k >= 1 alone')
@@ -274,7 +279,9 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         lds = [LD if i < n_tails else 0 for i in range(3)]
 
         def forced(picked):
-            return picked if force is None else ops.logprob_forced(logits, LD, c0, n_tails, tl, lds, ns, N, picked, force)
+            if force is not None:
+                ops.logprob_forced(logits, LD, c0, n_tails, tl, lds, ns, N, picked, force)
+            return picked if stats is None else ops.logprob_stats(logits, LD, c0, n_tails, tl, lds, ns, N, picked, stats)
         if sample is not None:
             return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
         if topk:
@@ -316,7 +323,9 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         ops.gemm_grouped(big)
 
     def forced(picked):
-        return picked if force is None else ops.logprob_forced(head, ld, c0, n_tails, tl, lds, ns, N, picked, force)
+        if force is not None:
+            ops.logprob_forced(head, ld, c0, n_tails, tl, lds, ns, N, picked, force)
+        return picked if stats is None else ops.logprob_stats(head, ld, c0, n_tails, tl, lds, ns, N, picked, stats)
     if sample is not None:
         return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
     if topk:
@@ -400,6 +409,37 @@ def attn_decode_usable(mods, kv_layer, names, q):
         if k.dim() == 4 and (k.shape[3] != 64 or kv_layer[nm][1].dim() != 4):      # head-major cache [S, B, H, 64] views
             return False
     return True
+
+
+class StatsSink:
+    """Where a generation step leaves its per-token statistics (model.generate(token_stats=n)): static
+    buffers alt_tok int32 / alt_lp fp32 [slots, rows, n] and rank int32 / entropy fp32 / chosen_lp fp32 [slots, rows], one slot
+    per decode step - the outputs of tell_adaptive_logprob_stats.  `step` is the step index of an eager step or the device
+    counter of a captured one (it holds step - 1), `fin` the caller's finished flags uint8 [rows] (read BEFORE the step's
+    bookkeeping launch) or None - AttnSink's convention for the slot, ban_source's for the flags."""
+
+    def __init__(self, n, slots, rows, pad, device):
+        self.n, self.slots, self.rows, self.pad = int(n), int(slots), int(rows), int(pad)
+        if not 1 <= self.n <= 8:
+            raise ValueError('token_stats: 1..8 alternatives, got %r' % (n,))
+        self.alt_tok = torch.full((self.slots, self.rows, self.n), self.pad, dtype=torch.int32, device=device)
+        self.alt_lp = torch.zeros(self.slots, self.rows, self.n, dtype=torch.float32, device=device)
+        self.rank = torch.full((self.slots, self.rows), -1, dtype=torch.int32, device=device)
+        self.entropy = torch.zeros(self.slots, self.rows, dtype=torch.float32, device=device)
+        self.chosen_lp = torch.zeros(self.slots, self.rows, dtype=torch.float32, device=device)
+        self.step, self.fin = 0, None
+
+    def reset(self):
+        """Every slot back to the neutral values (pad, 0, -1, 0, 0): what a slot no step wrote reads as."""
+        self.alt_tok.fill_(self.pad)
+        self.alt_lp.zero_()
+        self.rank.fill_(-1)
+        self.entropy.zero_()
+        self.chosen_lp.zero_()
+
+    def at(self, step):
+        self.step = step if torch.is_tensor(step) else int(step)
+        return self
 
 
 class AttnSink:

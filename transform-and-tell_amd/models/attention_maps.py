@@ -127,3 +127,41 @@ def caption_attention(model, batch, gen, bpe=None):
             words.append(entry)
         out.append(words)
     return out
+
+
+def caption_confidence(model, batch, gen, bpe=None):
+    """The word-level view of the per-token statistics: gen is generate's output with token_stats=n ('gen_ids', 'alt_ids',
+    'token_rank', 'token_entropy', 'token_model_lp').  Generated pieces are merged into words as in `caption_attention`
+    (<s> dropped, everything from the row's </s> on ignored; a piece opens a word when it is the first or starts with 'Ġ').
+    -> one list per caption of
+        {'tokens': word, 'log_prob': the sum of its pieces' token_model_lp, 'entropy': the maximum of its pieces' entropies,
+         'rank': the rank of its first piece, 'alternatives': the decoded first-piece alternatives, best first}.
+    bpe: as in `caption_attention`.  `batch` is unused (kept for the signature of the attention view).  Host code only."""
+    need = ('gen_ids', 'alt_ids', 'token_rank', 'token_entropy', 'token_model_lp')
+    if any(k not in gen for k in need):
+        raise ValueError('caption_confidence needs the output of generate(..., token_stats=n)')
+    if bpe is None:
+        from ..data.bpe import RobertaBPE
+        from ..data.indexers import bpe_directory
+        bpe = RobertaBPE(bpe_directory())
+    d = bpe.source_dictionary
+    pad = int(getattr(model, 'padding_idx', d.pad_index))
+    gen_ids = torch.as_tensor(gen['gen_ids']).cpu().tolist()
+    alt =torch.as_tensor(gen['alt_ids']).cpu().tolist()
+    rank = torch.as_tensor(gen['token_rank']).cpu().tolist()
+    ent = torch.as_tensor(gen['token_entropy']).to(torch.float64).cpu().tolist()
+    mlp = torch.as_tensor(gen['token_model_lp']).to(torch.float64).cpu().tolist()
+    out = []
+    for i, row in enumerate(gen_ids):
+        toks = row[1:]                                            # (column 0 is the seed the generator was given)
+        for stop in (d.eos_index, pad):                           # (the row's </s> and everything behind it are gone)
+            if stop in toks:
+                toks = toks[:toks.index(stop)]
+        pieces = _piece_strings(toks, bpe)
+        words = []
+        for a, b in merge_generated(pieces):
+            words.append({'tokens': _text(pieces[a:b], bpe), 'log_prob': float(sum(mlp[i][a:b])),
+                          'entropy': float(max(ent[i][a:b])), 'rank': int(rank[i][a]),
+                          'alternatives': [_text(_piece_strings([t], bpe), bpe) for t in alt[i][a] if 0 <= int(t) < len(d)]})
+        out.append(words)
+    return out

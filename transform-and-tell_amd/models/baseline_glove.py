@@ -131,7 +131,10 @@ class BaselineGloveModel(Model):
 
     def generate(self, image, caption, metadata=None, context_vectors=None, attention=False, n_best=1, prefix=None,
                  n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None,
-                 guidance_drop=None):
+                 guidance_drop=None, token_stats=0):
+        if token_stats:
+            from .stepper import TOKEN_STATS_REFUSALS
+            raise ValueError('token_stats=%r: %s' % (token_stats, TOKEN_STATS_REFUSALS['lstm']))
         _refuse_search_options(self, n_best=n_best)
         _refuse_mask_options(self, banned=banned, ground=ground)
         _refuse_guidance(self, getattr(self, 'guidance_scale', 1.0) if guidance is None else guidance,
@@ -281,7 +284,7 @@ class TransformerGloveModel(CaptionModel):
 
     def generate(self, image, caption, metadata=None, context_vectors=None, beam_size=1, attention=False, n_best=1,
                  prefix=None, n_samples=1, rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None,
-                 guidance_drop=None):
+                 guidance_drop=None, token_stats=0):
         if attention:
             self._check_attention(beam_size)
         self._check_grounding(ground)
@@ -289,6 +292,7 @@ class TransformerGloveModel(CaptionModel):
         guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
         self._check_options(beam_size, attention, n_best)
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
+        ts = self._check_token_stats(token_stats, beam_size, n_best, guide)
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
@@ -297,7 +301,8 @@ class TransformerGloveModel(CaptionModel):
                                                    **({'prefix': pfx} if pfx is not None else {}),
                                                    **({'samples': ns} if ns is not None else {}),
                                                    **({'vmask': vm} if vm is not None else {}),
-                                                   **({'guide': guide} if guide is not None else {}))
+                                                   **({'guide': guide} if guide is not None else {}),
+                                                   **({'token_stats': ts} if ts else {}))
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
         if pfx is not None:
             out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)

@@ -181,7 +181,8 @@ class PointerModelBase(CaptionModel):
     # ------------------------------------------------------------------ :397-426, :427-696
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None, cached=None):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None, cached=None,
+                 token_stats=0):
         """cached (None: the model's `cached_generation` key): the same greedy / nucleus decode through the cached generator -
         projected context K/V, a batch that keeps its shape, one captured step per token (_pointer_steps).  Everything refused
         below is refused on both paths.
@@ -192,6 +193,9 @@ class PointerModelBase(CaptionModel):
         'sample_index' [B, n], 'duplicate' [B, n], 'scores' [B], 'should_copy_samples' [B, n, L] bool, 'copy_probs_samples'
         [B, n, L - 1] and 'generations_samples' / 'copied_texts_samples' (n strings per image), all in rank order.  On the eager
         path, or for a greedy model, n > 1 is refused as before.  n_samples = 1: exactly the call of before."""
+        if token_stats:                                               # (refused on both paths: the copy decision is out of scope)
+            from .stepper import TOKEN_STATS_REFUSALS
+            raise ValueError('token_stats=%r: %s' % (token_stats, TOKEN_STATS_REFUSALS['copy']))
         if attention:
             self._check_attention(beam_size)
         self._check_mask_options(banned, ground, attention)           # (refused: the copy decision is out of scope)

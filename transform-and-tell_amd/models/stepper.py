@@ -16,6 +16,18 @@ def sub_table(alpha, beta, L):
     t[1:] = (np.float64(alpha) + np.float64(beta) * np.arange(1, int(L) + 1, dtype=np.float64)).astype(np.float32)
     return torch.from_numpy(t)
 
+# why generate(token_stats=n) / DecodeStepper(stats=n) is refused - one wording wherever two paths refuse the same thing
+TOKEN_STATS_REFUSALS = {
+    'beam': 'token_stats does not combine with beam search (beam_size > 1, n_best): the rows of a beam move between steps, '
+            'per-hypothesis statistics would have to follow the ancestor table',
+    'guide': 'token_stats does not combine with guidance: a guided step decodes paired rows and picks from a combined score, '
+             'not from one row\'s distribution',
+    'lanes': 'token_stats is not supported by generate_lanes / generate_stream (out of scope): use generate()',
+    'copy': 'token_stats is not supported by the copy models (pointer, pointer_2): their step mixes a copy distribution into '
+            'the pick',
+    'lstm': 'token_stats is not supported by the LSTM baseline: it has no cached decode step',
+}
+
 # decode steps per graph replay once a generation loop is past its first all-finished test (DecodeStepper.multi)
 MULTI_STEP_GRAPHS = os.environ.get('TELL_MULTI_STEP_GRAPHS', '1') != '0'
 
@@ -85,11 +97,26 @@ class DecodeStepper:
     hidden=True (the copy models): the step hands out the decoder's last hidden row next to the pick -
     (token, log-prob, x [B, 1, E]) - so that the caller's `post` can run its own tail on it (entity attention, copy decision, then
     the bookkeeping launch); `post` is recorded into the captured single-step and multi-step graphs as ever, however many
-    launches it issues.  ('hidden',) joins the signature only when set."""
+    launches it issues.  ('hidden',) joins the signature only when set.
+
+    stats = n in 1..8 (per-token statistics): the stepper owns a decode.StatsSink - static buffers
+    [gen_len, B(, n)] in the cache entry, handed out as step.stats, slot = step index (from the host in an eager step, from
+    the device counter in a captured one, as the attention sink) - and every head ends in tell_adaptive_logprob_stats, behind
+    the pick and the forced pick.  step.stats_source(finished uint8 [B]) hands in the caller's finished flags (static ones of
+    the caller's book when the step is captured), as ban_source does.  ('stats', n) joins the signature only when set; it
+    combines with greedy, every sampling rule, ban, pen, mask, prefix, hyp and attention, and is refused for topk and guide."""
 
     def __init__(self, model, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                 prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False):
+                 prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False, stats=0):
         self.hidden = bool(hidden)
+        self.n_stats = int(stats)
+        if self.n_stats:
+            if not 1 <= self.n_stats <= 8:
+                raise ValueError('stats: 1..8 alternatives per token, got %r' % (stats,))
+            if topk:
+                raise ValueError('topk: ' + TOKEN_STATS_REFUSALS['beam'])
+            if guide is not None:
+                raise ValueError('guide: ' + TOKEN_STATS_REFUSALS['guide'])
         if guide is not None:
             for on, what in ((sample is not None, 'sampling (sampling_topk / sampling_topp / sampling_minp / sampling_typical)'),
                              (ban is not None, 'no_repeat_ngram_size / min_len'),
@@ -132,6 +159,7 @@ class DecodeStepper:
             self.pfx = self._make_prefix(dev) if prefix else {}
             self.ban_src, self.pen_src = {}, {}
             self.attn = self._make_sink(kv, dev) if attention else None
+            self.stats = self._make_stats(dev) if self.n_stats else None
             self.cur = self.counter_out = self.back = None
             return
         h = self.h = self._entry(model, names, kv, contexts, sample, attention, opts, prefix)
@@ -141,6 +169,9 @@ class DecodeStepper:
         self.pfx, self.ban_src, self.attn = h.get('pfx', {}), h['ban_src'], h.get('attn')
         self.pen_src = h.setdefault('pen_src', {}) if self.pen is not None else {}
         self.vmask = h.get('vmask')
+        self.stats = h.get('stats')
+        if self.stats is not None:                                # (slots of steps this caption batch never reaches stay neutral)
+            self.stats.reset()
         self.gamma = h.get('gamma')
         self.seed, self.cur = h['seed'], h['cur']
         self.c_cur, self.c_next = h['counter'][0:1], h['counter'][1:2]
@@ -157,6 +188,9 @@ class DecodeStepper:
     def _make_mask(self, device):
         words = (int(self.dec.adaptive_softmax.vocab_size) + 31) // 32
         return torch.zeros(self.B // self.per_sample, words, dtype=torch.int32, device=device)
+
+    def _make_stats(self, device):
+        return decode.StatsSink(self.n_stats, self.gen_len, self.B, self.pad, device)
 
     def _make_sink(self, kv, device):
         return decode.AttnSink([{n: torch.zeros(self.gen_len, self.B, int(pair[0].shape[0]) + 2, dtype=torch.float32,
@@ -190,6 +224,8 @@ class DecodeStepper:
             sig = sig + (('guide', self.guide),)
         if self.hidden:                                           # (... and every one that keeps its hidden row to itself)
             sig = sig + (('hidden',),)
+        if self.n_stats:                                          # (... and every one without per-token statistics)
+            sig = sig + (('stats', self.n_stats),)
         cache = model.__dict__.setdefault('_decode_graphs', {})
         # A captured step bakes in the addresses of the working weights (weight-normalised copies, the concatenated
         # softmax head) that ops._cached rebuilds - at NEW addresses - whenever the weights change (optimizer step,
@@ -257,6 +293,8 @@ class DecodeStepper:
             h['vmask'] = self._make_mask(dev)
         if self.guide is not None:
             h['gamma'] = torch.ones(1, dtype=torch.float32, device=dev)
+        if self.n_stats:
+            h['stats'] = self._make_stats(dev)
         return h
 
     def _fill(self, kv, contexts):
@@ -321,6 +359,15 @@ class DecodeStepper:
             ban_src['ban'] = torch.zeros(B, hist.shape[1] + 1, dtype=torch.int32, device=hist.device)
             ban_src['n_ban'] = torch.zeros(B, dtype=torch.int32, device=hist.device)
 
+    def stats_source(self, fin):
+        """The finished flags the statistics launch reads (before every eager step; once when the buffer is static): a finished
+        row writes the neutral values and requests no logit."""
+        if self.stats is None:
+            raise ValueError('stats_source: the stepper was built without stats=n')
+        if fin.dtype != torch.uint8 or fin.numel() != self.B or not fin.is_contiguous():
+            raise ValueError('stats_source: finished uint8 [%d] expected' % self.B)
+        self.stats.fin = fin
+
     def pen_source(self, hist, fin):
         """The histories the penalty lists are counted from (before every eager step; once when the buffers are static).  The
         list buffers and the `sub` table (fp32 [L + 1]: sub[0] = 0, sub[c] = float32(alpha + beta * c) formed in fp64) are kept
@@ -367,6 +414,7 @@ class DecodeStepper:
         forcing table every one of them ends in the forced pick."""
         soft, pfx = self.dec.adaptive_softmax, self.pfx
         force = (pfx['tab'], pfx['plen'], None, self.per_sample, sidx, self.pad) if pfx else None
+        skw = {'stats': self.stats.at(sidx)} if self.stats is not None else {}     # (without it every call is the call it was)
         if self.guide is not None:                                    # row r and its twin r + B / 2: one pick for both
             tok, lp = soft.topk(x, self.n_hyp, guide=(self.B // 2, self.gamma))
             return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
@@ -383,8 +431,8 @@ class DecodeStepper:
                          int(self.ban[2]), src['ban'], src['ban'].stride(0), src['n_ban'])
                 ban = (src['ban'], src['n_ban'])
             if self.sample is not None:
-                return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, mask=mask)
-            tok, lp = soft.topk(x, self.n_hyp, ban=ban, force=force, mask=mask)
+                return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, mask=mask, **skw)
+            tok, lp = soft.topk(x, self.n_hyp, ban=ban, force=force, mask=mask, **skw)
             return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
         if self.ban is not None:
             ban, src = self.ban, self.ban_src
@@ -393,7 +441,7 @@ class DecodeStepper:
             ops.call('tell_decode_ban_list', hist, hist.stride(0), hist.shape[1], src['fin'], self.B,
                      0 if step_dev is not None else int(sidx), step_dev, int(ban[0]), int(ban[1]), int(ban[2]),
                      src['ban'], src['ban'].stride(0), src['n_ban'])
-            tok, lp = soft.topk(x, self.n_hyp, ban=(src['ban'], src['n_ban']), force=force)
+            tok, lp = soft.topk(x, self.n_hyp, ban=(src['ban'], src['n_ban']), force=force, **skw)
             return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
         pen = None
         if self.pen is not None:
@@ -405,16 +453,16 @@ class DecodeStepper:
                      src['n_pen'])
             pen = (self.pen[0], src['sub'], src['tok'], src['cnt'], src['n_pen'])
             if self.sample is None:
-                tok, lp = soft.topk(x, self.n_hyp, force=force, pen=pen)
+                tok, lp = soft.topk(x, self.n_hyp, force=force, pen=pen, **skw)
                 return (tok, lp) if self.topk else (tok.view(tok.shape[0], tok.shape[1]), lp.view(lp.shape[0], lp.shape[1]))
-            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, pen=pen)
+            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, force=force, pen=pen, **skw)
         if self.sample is not None:
             topp = self.sample[2] if len(self.sample) > 2 else None      # nucleus: p is a launch argument, like the temperature
             rule = self.sample[3] if len(self.sample) > 3 else None      # 'minp' / 'typical': topp is m / tau
-            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, topp=topp, force=force, rule=rule)
+            return soft.sample(x, self.sample[0], self.sample[1], self.seed, sidx, topp=topp, force=force, rule=rule, **skw)
         if self.topk:
             return soft.topk(x, self.topk, force=force)
-        return soft.greedy(x, force=force)
+        return soft.greedy(x, force=force, **skw)
 
     def _run(self, sidx, cur):
         """sidx: the step index for a sampling head - the host's int, or c_cur inside a captured step (i - 1 there)."""

@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from .. import graphs, ops, streams
 from ..common.registrable import Registrable
-from .stepper import DecodeStepper
+from .stepper import TOKEN_STATS_REFUSALS, DecodeStepper
 
 _OVERLAP = os.environ.get('TELL_ENCODER_OVERLAP', '1') != '0'
 # where the PREFETCHED ResNet pass of the next batch is enqueued: 'own' = its side stream (three streams share the chip),
@@ -381,6 +381,7 @@ class DecodeInfo(list):
     scores = None
     nbest = None
     samples = None
+    token_stats = None             # generate(token_stats=n): the five per-token arrays of the output dict (first rank)
 
 
 def nucleus_definition(lp, temp, topp, topk=0, u=None):
@@ -411,6 +412,52 @@ def nucleus_definition(lp, temp, topp, topk=0, u=None):
         hit = np.nonzero(run > float(u) * run[-1])[0]
         out['token'] = int(members[hit[0]] if hit.size else members[-1])
     return out
+
+
+TOKEN_STATS_KEYS = ('alt_ids', 'alt_log_probs', 'token_rank', 'token_entropy', 'token_model_lp')
+
+
+def check_token_stats(token_stats=0):
+    """generate(token_stats=n): n alternatives per token, 0 (off) .. 8 (the K of the top-k kernels) -> int."""
+    if isinstance(token_stats, bool) or not isinstance(token_stats, int) or not 0 <= token_stats <= 8:
+        raise ValueError('token_stats must be an integer in 0..8 (alternatives per token; 0: off), got %r' % (token_stats,))
+    return token_stats
+
+
+def token_stats_neutral(B, steps, n, pad, device=None):
+    """What positions behind a row's </s> hold: alt_ids = pad, alt_log_probs = 0, token_rank = -1, token_entropy = 0,
+    token_model_lp = 0 - the five arrays of generate(token_stats=n) filled with them."""
+    return {'alt_ids': torch.full((B, steps, n), int(pad), dtype=torch.long, device=device),
+            'alt_log_probs': torch.zeros(B, steps, n, dtype=torch.float32, device=device),
+            'token_rank': torch.full((B, steps), -1, dtype=torch.long, device=device),
+            'token_entropy': torch.zeros(B, steps, dtype=torch.float32, device=device),
+            'token_model_lp': torch.zeros(B, steps, dtype=torch.float32, device=device)}
+
+
+def token_stats_definition(lp_full, chosen, n):
+    """The definition of the per-token statistics (include/tell_hip.h tell_adaptive_logprob_stats) on
+    one full row of log-probs, in torch on the CPU and in the row's own dtype - what the kernel and the generators are tested
+    against.  lp_full: [V] log-probs of the model's own distribution; chosen: the token the step took; n alternatives.
+    -> dict: alt_ids int64 [n] / alt_log_probs [n] (value descending, lower id first on ties; (0x7fffffff, -inf) past the
+    vocabulary), token_rank (#{t: lp_t > lp_c or (lp_t == lp_c and t < c)}; -1 for a token outside the vocabulary),
+    token_entropy (-sum p log p in nats, terms with p = 0 dropped), token_model_lp (lp_c; 0 outside the vocabulary)."""
+    lp = torch.as_tensor(lp_full).detach().cpu().reshape(-1)
+    V, n, c = lp.numel(), int(n), int(chosen)
+    order = torch.sort(-lp, stable=True).indices               # (stable: equal values keep id order)
+    alt = order[:n]
+    alt_ids = torch.full((n,), 0x7fffffff, dtype=torch.long)
+    alt_lp = torch.full((n,), float('-inf'), dtype=lp.dtype)
+    alt_ids[:alt.numel()] = alt
+    alt_lp[:alt.numel()] = lp[alt]
+    p = lp.exp()
+    ent = -(torch.where(p > 0, p * lp, torch.zeros_like(lp))).sum()
+    if 0 <= c < V:
+        ids = torch.arange(V)
+        rank = int(((lp > lp[c]) | ((lp == lp[c]) & (ids < c))).sum())
+        lp_c = lp[c].clone()
+    else:
+        rank, lp_c = -1, lp.new_zeros(())
+    return {'alt_ids': alt_ids, 'alt_log_probs': alt_lp, 'token_rank': rank, 'token_entropy': ent, 'token_model_lp': lp_c}
 
 
 def _id_order_draw(out, members, wm, u):
@@ -493,6 +540,11 @@ class AttnMaps(namedtuple('AttnMaps', 'maps steps')):
     maps: {context name: fp32 [B, steps, n_layers, S + 2]} on the device; steps: [B] long, the row's `done_step` - the
     number of decode steps it took part in, the one that produced its </s> included."""
     __slots__ = ()
+
+
+class AttnMapsStats(AttnMaps):
+    """AttnMaps of a generation that also kept per-token statistics (attention=True, token_stats=n): .token_stats as DecodeInfo's."""
+    token_stats = None
 
 
 class CaptionModel(Model):
@@ -802,6 +854,20 @@ class CaptionModel(Model):
                              'sampling_typical): the arg-max decode (sampling_topk 1) would give %d identical captions' % (n, n))
         return n, rule, alpha
 
+    def _check_token_stats(self, token_stats=0, beam_size=1, n_best=1, guide=None):
+        """generate(token_stats=n): check_token_stats, and for n > 0 what it combines with - the greedy
+        and sampling decodes of the cached DynamicConv generator; no beam search, no guidance, no LSTM decoder.  -> n."""
+        n = check_token_stats(token_stats)
+        if not n:
+            return 0
+        if int(beam_size) > 1 or int(n_best) > 1:
+            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['beam']))
+        if guide is not None:
+            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['guide']))
+        if not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
+            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['lstm']))
+        return n
+
     def _check_attention(self, beam_size=1):
         """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
         sample (greedy, top-k, nucleus)."""
@@ -828,6 +894,8 @@ class CaptionModel(Model):
                 out['gen_ids_nbest'], out['log_probs_nbest'], out['scores_nbest'] = info.nbest
             if info is not None and info.samples is not None:
                 out.update(info.samples)
+        if getattr(attns, 'token_stats', None) is not None:
+            out.update(attns.token_stats)
         return out
 
     def reset_graphs(self):
@@ -1068,8 +1136,17 @@ class CaptionModel(Model):
 
     def generate(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
                  attn_idx=None, beam_size=1, encoded=None, attention=False, n_best=1, prefix=None, n_samples=1,
-                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
+                 rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None,
+                 token_stats=0):
         """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        token_stats = n (0..8; per-token statistics): every step of the cached generator also leaves, for
+        the token it took, the n best tokens of the MODEL'S OWN distribution (no temperature, penalty, mask), the token's rank in
+        it (0 = the arg-max), its log-prob and the distribution's entropy in nats - one more launch behind the pick, inside the
+        captured step.  Adds, with steps = gen_ids.shape[1] - 1: 'alt_ids' int64 [B, steps, n], 'alt_log_probs' fp32 [B, steps,
+        n], 'token_rank' int64 [B, steps], 'token_entropy' fp32 [B, steps], 'token_model_lp' fp32 [B, steps]; positions behind a
+        row's </s> hold pad, 0, -1, 0, 0.  With n_samples > 1 also their '_samples' forms [B, n_samples, steps, ...] in rank
+        order (the plain keys are the first rank).  Greedy and every sampling rule, with the search options, penalties, masks,
+        a prefix and attention maps; refused for beam search / n_best and guidance.  0: exactly the call of before.
         guidance = gamma / guidance_drop = names (context guidance; None: the model's `guidance_scale` /
         `guidance_drop`): every step is decoded twice in one static batch - with all contexts, and with the contexts in
         `guidance_drop` (out of image / article / faces / obj) fully masked - and the pick follows
@@ -1121,9 +1198,11 @@ class CaptionModel(Model):
         pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
         vm = self._vocab_mask(context, banned, ground, attention)
         guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
+        ts = self._check_token_stats(token_stats, beam_size, n_best, guide)
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
         log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
                                                    **({'n_best': n_best} if n_best != 1 else {}),
+                                                   **({'token_stats': ts} if ts else {}),
                                                    **({'guide': guide} if guide is not None else {}),
                                                    **({'samples': ns} if ns is not None else {}),
                                                    **({'vmask': vm} if vm is not None else {}),
@@ -1134,8 +1213,12 @@ class CaptionModel(Model):
         return out
 
     @torch.no_grad()
-    def score_captions(self, batch):
-        """How likely the model finds the batch's OWN captions: the caption after <s>, its </s> included, is forced token by
+    def score_captions(self, batch, token_stats=0):
+        """token_stats = n (1..8): also the five per-token arrays of generate(token_stats=n) for the batch's own captions -
+        'alt_ids' / 'alt_log_probs' [B, T - 1, n], 'token_rank' / 'token_entropy' / 'token_model_lp' [B, T - 1]: where the model
+        ranks every reference token, what it would have preferred and how flat its distribution was; neutral values (pad, 0,
+        -1, 0, 0) behind a row's </s>.  They come from the same launch as generate's (the forced-prefix path).
+        How likely the model finds the batch's OWN captions: the caption after <s>, its </s> included, is forced token by
         token through the greedy cached generator (generate(prefix=...)).  -> {'log_probs' [B, T - 1]: the teacher-forced
         log-prob of every caption token (0 behind a row's </s>), 'scores' [B]: their sum, 'prefix_len' [B]: tokens scored}.
         The captions may be at most gen_len (100) tokens long."""
@@ -1143,15 +1226,30 @@ class CaptionModel(Model):
         prefix = cap[:, 1:].contiguous()
         f = {k: (dict(v) if isinstance(v, dict) else v) for k, v in batch.items()
              if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds', 'encoded')}
-        out = self.generate(**f, prefix=prefix)
+        n_ts = check_token_stats(token_stats)
+        out = self.generate(**f, prefix=prefix, **({'token_stats': n_ts} if n_ts else {}))
         plen = out['prefix_len']
         lp = out['log_probs']
         T = prefix.shape[1]
         full = lp.new_zeros(lp.shape[0], T)
         n = min(T, lp.shape[1])
         full[:, :n] = lp[:, :n]
-        full = full * (torch.arange(T, device=lp.device).unsqueeze(0) < plen.unsqueeze(1))
-        return {'log_probs': full, 'scores': full.sum(1), 'prefix_len': plen}
+        live = torch.arange(T, device=lp.device).unsqueeze(0) < plen.unsqueeze(1)
+        full = full * live
+        res = {'log_probs': full, 'scores': full.sum(1), 'prefix_len': plen}
+        if n_ts:
+            neutral = token_stats_neutral(lp.shape[0], T, n_ts, self.padding_idx, lp.device)
+            for k_ in TOKEN_STATS_KEYS:
+                t = neutral[k_]
+                t[:, :n] = out[k_][:, :n]
+                keep = live if t.dim() == 2 else live.unsqueeze(-1)
+                res[k_] = torch.where(keep, t, token_stats_neutral(1, 1, n_ts, self.padding_idx, lp.device)[k_])
+        return res
+
+    def caption_confidence(self, batch, gen, bpe=None):
+        """The word-level view of `gen = generate(**batch, token_stats=n)` (attention_maps.caption_confidence)."""
+        from .attention_maps import caption_confidence
+        return caption_confidence(self, batch, gen, bpe=bpe)
 
     def caption_attention(self, batch, gen, bpe=None):
         """The reference's per-word attention view of `gen = generate(**batch, attention=True)` (attention_maps.py)."""
@@ -1165,7 +1263,8 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def generate_lanes(self, batches, beam_size=1, lanes=2, forward=False, attention=False, n_best=1, n_samples=1,
-                       rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None):
+                       rank_by='score', rank_len_penalty=0.0, banned=None, ground=None, guidance=None, guidance_drop=None,
+                       token_stats=0):
         """Captions for a sequence of batches with `lanes` decode loops IN FLIGHT TOGETHER, each on its own stream with its
         own DecodeStepper - captured step, static buffers and counters (_decode_stepper(lane=)): a decode step is a chain of ~40 dependent
         launches that each fill the chip for a few microseconds and then wait on memory - at 12-27 % of the HBM roofline a second
@@ -1176,7 +1275,10 @@ class CaptionModel(Model):
         n_samples / rank_by / rank_len_penalty: as `generate` - every lane decodes the n hypotheses of its batch's images.
         banned (bool [V]) / ground (bool [V] or True): the shared forms of `generate`'s vocabulary masks, applied to every batch
         (each row grounded in its own article).
-        guidance / guidance_drop: as `generate` - every lane decodes its batch and the batch's unconditional twin."""
+        guidance / guidance_drop: as `generate` - every lane decodes its batch and the batch's unconditional twin.
+        token_stats: refused here (0 only); `generate` keeps the per-token statistics."""
+        if check_token_stats(token_stats):
+            raise ValueError('token_stats=%d: %s' % (token_stats, TOKEN_STATS_REFUSALS['lanes']))
         if banned is not None and (not torch.is_tensor(banned) or banned.dim() != 1):
             raise ValueError('generate_lanes takes the shared form of banned: a bool tensor [V]')
         ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
@@ -1263,7 +1365,7 @@ class CaptionModel(Model):
                     o = od
                 yield b, o
 
-    def generate_stream(self, batches, beam_size=1, forward=False, attention=False, n_best=1):
+    def generate_stream(self, batches, beam_size=1, forward=False, attention=False, n_best=1, token_stats=0):
         """Captions for a sequence of batches (the test-set loop of tell/commands/evaluate.py:118-160) with the frozen
         encoders of batch N+1 launched on their own streams BEFORE the decode loop of batch N is issued - the trainer's
         schedule applied to generation.  Numerics are those of `generate` / `forward` batch by batch: the encoders read
@@ -1280,7 +1382,10 @@ class CaptionModel(Model):
         32 / 64 / 128 captions per batch.
 
         batches: any iterable of batch dicts (keys of `forward`); forward=True yields `self(**batch)` (evaluate mode:
-        loss + generation + metrics) instead of `generate(**batch)`.  Yields (batch, output_dict) in order."""
+        loss + generation + metrics) instead of `generate(**batch)`.  Yields (batch, output_dict) in order.
+        token_stats: refused here (0 only); `generate` keeps the per-token statistics."""
+        if check_token_stats(token_stats):
+            raise ValueError('token_stats=%d: %s' % (token_stats, TOKEN_STATS_REFUSALS['lanes']))
         if attention:
             if forward:
                 raise ValueError('attention=True goes with generate, not with forward=True')
@@ -1314,8 +1419,10 @@ class CaptionModel(Model):
     fast_generation = True      # projected-K/V cache + static batch; False = the reference's control flow
 
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
-                  prefix=None, samples=None, vmask=None, guide=None):
+                  prefix=None, samples=None, vmask=None, guide=None, token_stats=0):
         opts = self._check_options(beam_size, attention, n_best, gen_len)
+        # (n, as checked by _check_token_stats: lives in the cached greedy / sampling generator, like `opts`)
+        skw = {'stats': self._check_token_stats(token_stats, beam_size, n_best, guide)} if token_stats else {}
         if guide is not None:                 # (drop, gamma) of _check_guidance: lives in the cached generators, like `opts`
             self._check_guidance(guide[1], guide[0], attention, prefix, samples[0] if samples is not None else 1,
                                  True if vmask is not None else None)
@@ -1335,12 +1442,12 @@ class CaptionModel(Model):
             vkw = {'vmask': vmask}
             if beam_size > 1:
                 return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix, **vkw)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **vkw)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **vkw, **skw)
         if attention:
             # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
             # flow with the legacy need_attn export, which stays what it is)
             self._check_attention(beam_size)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, prefix=prefix)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, prefix=prefix, **skw)
         if not hasattr(self.decoder, 'project_contexts'):
             # a recurrent decoder behind this model class (expt/*/3_lstm_roberta: `lstm_decoder_flattened`): greedy
             # decode that carries the LSTM state.  (The reference's loop feeds such a decoder only the last token with
@@ -1353,9 +1460,9 @@ class CaptionModel(Model):
         if beam_size > 1:
             return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix)
         if samples is not None:
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples)
-        if self.fast_generation or opts is not None or prefix is not None:  # (the search options live in the cached generator)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **skw)
+        if self.fast_generation or opts is not None or prefix is not None or skw:  # (the search options live in the cached generator)
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, **skw)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
 
     @staticmethod
@@ -1369,16 +1476,17 @@ class CaptionModel(Model):
 
     @torch.no_grad()
     def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None,
-                         samples=None, vmask=None, guide=None):
+                         samples=None, vmask=None, guide=None, stats=0):
         # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
         return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
                                               **({'prefix': prefix} if prefix is not None else {}),
                                               **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {}),
                                               **({'vmask': vmask} if vmask is not None else {}),
-                                              **({'guide': guide} if guide is not None else {})))
+                                              **({'guide': guide} if guide is not None else {}),
+                                              **({'stats': stats} if stats else {})))
 
     def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
-                      prefix=None, n=1, rank=('score', 0.0), vmask=None, guide=None):
+                      prefix=None, n=1, rank=('score', 0.0), vmask=None, guide=None, stats=0):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
         (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
@@ -1404,9 +1512,16 @@ class CaptionModel(Model):
         step (step.set_mask) and every pick is the masked one; the bookkeeping is untouched.
         guide = (drop, gamma) of _check_guidance: the batch is decoded with its unconditional twin behind
         it (guided_batch: 2 * images rows), every pick is the guided arg-max - one token and one normalised log-prob for both
-        rows of a pair - the bookkeeping runs over all rows unchanged and the results are the first half."""
+        rows of a pair - the bookkeeping runs over all rows unchanged and the results are the first half.
+        stats = n_alt in 1..8 (generate(token_stats=)): every head ends in tell_adaptive_logprob_stats,
+        which reads the finished flags as they stand BEFORE the step's bookkeeping (step.stats_source) and writes slot = step of
+        the stepper's sink; behind the loop the slots become the five [rows, steps(, n_alt)] arrays, carried as .token_stats of
+        the third result (a DecodeInfo, or an AttnMapsStats with attention=True)."""
         dec = self.decoder
         n = int(n)
+        stats = int(stats)
+        if stats and guide is not None:
+            raise ValueError('token_stats=%d: %s' % (stats, TOKEN_STATS_REFUSALS['guide']))
         if guide is not None:
             self._check_guidance(guide[1], guide[0], attention, prefix, n, True if vmask is not None else None)
             cond = caption_ids.shape[0]
@@ -1423,7 +1538,7 @@ class CaptionModel(Model):
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
                                     prefix=prefix is not None, **({'pen': pen} if pen is not None else {}),
                                     **({'hyp': n} if n > 1 else {}), **({'mask': True} if vmask is not None else {}),
-                                    **({'guide': guide[0]} if guide is not None else {}))
+                                    **({'guide': guide[0]} if guide is not None else {}), **({'stats': stats} if stats else {}))
         if guide is not None:
             step.set_guidance(guide[1])
         if prefix is not None:
@@ -1449,6 +1564,8 @@ class CaptionModel(Model):
                 step.ban_source(ids, fin8)
             if pen is not None:
                 step.pen_source(ids, fin8)
+            if stats:
+                step.stats_source(fin8)
         else:
             ids = torch.full((B, gen_len + 1), self.padding_idx, dtype=torch.long, device=dev)
             lps = torch.zeros(B, gen_len, dtype=torch.float32, device=dev)
@@ -1473,6 +1590,8 @@ class CaptionModel(Model):
                 step.ban_source(ids, finished.to(torch.uint8))
             if pen is not None:
                 step.pen_source(ids, finished.to(torch.uint8))
+            if stats:
+                step.stats_source(finished.to(torch.uint8))
             tok, lp = step(i, cur)
             yield i
             tok = tok.long().view(B)
@@ -1487,21 +1606,39 @@ class CaptionModel(Model):
                 break
         steps = int(done_step.max())                                          # one sync at the end
         steps = max(steps, 1)
+        ts = self._token_stats_arrays(step.stats, steps) if stats else None
         if n > 1:
-            return self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank)
+            return self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank,
+                                      **({'stats': ts} if ts is not None else {}))
         attns = []
+        if ts is not None:
+            attns = DecodeInfo()
+            attns.token_stats = ts
         if attention:
             # slot i of a layer's buffer = step i (the token at ids[:, i + 1]); copied out: the buffers belong to the stepper
             bufs = step.attn.bufs
-            attns = AttnMaps({n: torch.stack([lb[n][:steps] for lb in bufs], 0).permute(2, 1, 0, 3).contiguous()
-                              for n in bufs[0]}, done_step.clamp(max=steps).clone())
+            attns = (AttnMapsStats if ts is not None else AttnMaps)(
+                {n: torch.stack([lb[n][:steps] for lb in bufs], 0).permute(2, 1, 0, 3).contiguous() for n in bufs[0]},
+                done_step.clamp(max=steps).clone())
+            if ts is not None:
+                attns.token_stats = ts
         if guide is not None:                                                 # (the unconditional twins took the same decisions)
             return lps[:cond, :steps].clone(), ids[:cond, :steps + 1].clone(), attns
         if fused:                                                             # (the static buffers belong to the stepper)
             return lps[:, :steps].clone(), ids[:, :steps + 1].clone(), attns
         return lps[:, :steps], ids[:, :steps + 1], attns
 
-    def _rank_samples(self, ids, lps, done_step, B, n, steps, gen_len, eos, rank):
+    @staticmethod
+    def _token_stats_arrays(sink, steps):
+        """The first `steps` slots of a decode.StatsSink [slots, rows(, n)] -> the five arrays of generate(token_stats=n),
+        [rows, steps(, n)] (copies: the buffers belong to the stepper)."""
+        return {'alt_ids': sink.alt_tok[:steps].permute(1, 0, 2).long().contiguous(),
+                'alt_log_probs': sink.alt_lp[:steps].permute(1, 0, 2).contiguous(),
+                'token_rank': sink.rank[:steps].t().long().contiguous(),
+                'token_entropy': sink.entropy[:steps].t().contiguous(),
+                'token_model_lp': sink.chosen_lp[:steps].t().contiguous()}
+
+    def _rank_samples(self, ids, lps, done_step, B, n, steps, gen_len, eos, rank, stats=None):
         """The end of _greedy_steps with n > 1 hypotheses per image: ids [B * n, gen_len + 1], lps [B * n, gen_len], done_step
         [B * n] of the decode loop -> (log_probs [B, steps], ids [B, steps + 1] of the first rank, DecodeInfo).  One launch
         (tell_sample_rank; hypotheses on the CPU: its host definition), then the gathers by its order."""
@@ -1523,16 +1660,21 @@ class CaptionModel(Model):
                         'scores_samples': score.gather(1, order), 'sample_index': order,
                         'duplicate': dup.gather(1, order).bool()}
         info.scores = info.samples['scores_samples'][:, 0].contiguous()
+        if stats is not None:                                     # the per-token statistics of every draw, in rank order too
+            for k_, t in stats.items():
+                t = t.reshape(B, n, *t.shape[1:])
+                info.samples[k_ + '_samples'] = t.gather(1, order.view(B, n, *([1] * (t.dim() - 2))).expand_as(t))
+            info.token_stats = {k_: info.samples[k_ + '_samples'][:, 0].contiguous() for k_ in stats}
         return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
 
     def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False):
+                        prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False, stats=0):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
         return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
                              opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}),
                              **({'mask': True} if mask else {}), **({'guide': guide} if guide is not None else {}),
-                             **({'hidden': True} if hidden else {}))
+                             **({'hidden': True} if hidden else {}), **({'stats': stats} if stats else {}))
 
     @torch.no_grad()
     def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,

@@ -74,7 +74,7 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), want_full=True)
         return full.view(B, T, self.vocab_size)
 
-    def topk(self, X, k, ban=None, force=None, pen=None, mask=None, guide=None):
+    def topk(self, X, k, ban=None, force=None, pen=None, mask=None, guide=None, stats=None):
         """The k best (token, log-prob) of every position, best first, fused like `greedy` (beam search).
         ban = (ban int32 [B * T, ld], n_ban int32 [B * T]): the row's banned tokens never enter its list
         (tell_adaptive_logprob_topk_banned; k = 1 is the greedy decode under bans).
@@ -85,18 +85,23 @@ class AdaptiveSoftmax(nn.Module):
         log-prob is the unmasked one (tell_adaptive_logprob_topk_masked; a ban list may join it).
         guide = (pair_offset, gamma fp32 [1] on the device): position r < pair_offset and its partner r + pair_offset get the
         same k candidates, ranked by s = lp_c + (gamma - 1) * (lp_c - lp_u) and reported as s - logsumexp(s) (DESIGN.md section 24,
-        tell_adaptive_logprob_topk_guided); on its own - no ban list, penalties, mask or forcing table."""
+        tell_adaptive_logprob_topk_guided); on its own - no ban list, penalties, mask or forcing table.
+        stats (here, in `sample` and in `greedy`): a decode.StatsSink - the head ends in tell_adaptive_logprob_stats, which
+        leaves the step's alternatives, rank, entropy and model log-prob in the sink's slot."""
         B, T, E = X.shape
         kw = {'pen': pen} if pen is not None else {}
         if mask is not None:
             kw['mask'] = mask
         if guide is not None:
             kw['guide'] = guide
+        if stats is not None:
+            kw['stats'] = stats
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
                                             self.head.class_proj.weight, self._tails(), topk=k, ban=ban, force=force, **kw)
         return tok.view(B, T, k), lp.view(B, T, k)
 
-    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None, pen=None, mask=None):
+    def sample(self, X, k, temp, seed_dev, step, row_ids=None, topp=None, force=None, rule=None, pen=None, mask=None,
+               stats=None):
         """One top-k draw with temperature per position (transformer_faces_objects.py:443-470: lprobs.topk(k), / temp,
         multinomial), fused like `greedy`: -> (token [B, T], log-prob [B, T] WITHOUT the temperature).  seed_dev: int32 [1]
         device word holding the seed; step: host step index or the int32 [1] device counter of a captured step (step - 1);
@@ -117,6 +122,8 @@ class AdaptiveSoftmax(nn.Module):
         kw = {'pen': pen} if pen is not None else {}
         if mask is not None:
             kw['mask'] = mask
+        if stats is not None:
+            kw['stats'] = stats
         sample = (int(k), 1.0 / float(temp), seed_dev, row_ids, step)
         if topp is not None:
             sample = sample + (float(topp),)
@@ -126,16 +133,17 @@ class AdaptiveSoftmax(nn.Module):
                                             self.head.class_proj.weight, self._tails(), sample=sample, force=force, **kw)
         return tok.view(B, T), lp.view(B, T)
 
-    def greedy(self, X, force=None, mask=None):
+    def greedy(self, X, force=None, mask=None, stats=None):
         """Fused arg-max over the full vocabulary (get_log_prob + topk(1),
         transformer_faces_objects.py:443-464) without materialising [N, vocab].
         force (here, in `topk` and in `sample`): the forcing table of a caption completion (ops.logprob_forced) - rows with
         prefix left take the prefix token and its log-prob instead of the pick.
         mask (as in `topk`): the arg-max over the tokens that are not masked - `topk` with k = 1."""
         B, T, E = X.shape
+        skw = {'stats': stats} if stats is not None else {}
         if mask is not None:
-            tok, lp = self.topk(X, 1, force=force, mask=mask)
+            tok, lp = self.topk(X, 1, force=force, mask=mask, **skw)
             return tok.view(B, T), lp.view(B, T)
         tok, lp, _ = ops.adaptive_log_probs(ops.as2dc(X), self.cutoff, self.head.word_proj.weight,
-                                            self.head.class_proj.weight, self._tails(), force=force)
+                                            self.head.class_proj.weight, self._tails(), force=force, **skw)
         return tok.view(B, T), lp.view(B, T)

@@ -1935,8 +1935,27 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
     return picked
 
 
+def logprob_stats(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, stats):
+    """Per-token statistics: tell_adaptive_logprob_stats behind the pick (and the forced pick) over
+    picked = (tokens int32 [N] or [N, k], ...) and the logits that pick was taken from.  stats: a decode.StatsSink - static
+    buffers [slots, N(, n)], .step the host step index or an int32 [1] device counter holding step - 1 (a captured decode
+    step's), .fin uint8 [N] or None.  -> picked."""
+    tokens = picked[0]
+    k = tokens.numel() // max(N, 1)
+    fin, step = stats.fin, stats.step
+    if stats.rows != N or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.numel() != N * k or \
+            (fin is not None and (fin.dtype != torch.uint8 or fin.numel() != N or not fin.is_contiguous())):
+        raise ValueError('logprob_stats: a sink of %d rows, contiguous int32 tokens [%d, k] and finished uint8 [%d] expected'
+                         % (N, N, N))
+    step_dev = step if torch.is_tensor(step) else None
+    call('tell_adaptive_logprob_stats', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
+         ns[2], N, tokens, int(k), fin, int(stats.n), int(stats.slots), 0 if step_dev is not None else int(step), step_dev,
+         int(stats.pad), stats.alt_tok, stats.alt_lp, stats.rank, stats.entropy, stats.chosen_lp)
+    return picked
+
+
 def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, topk=0, sample=None, ban=None, force=None,
-                       pen=None, mask=None, guide=None):
+                       pen=None, mask=None, guide=None, stats=None):
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
@@ -1954,6 +1973,9 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
                               pen is not None or mask is not None):
         raise ValueError('adaptive_log_probs: guidance goes with topk = k >= 1 alone (no draw, ban list, forcing table, '
                          'penalties or vocabulary mask)')
+    if stats is not None and (want_full or guide is not None):
+        raise ValueError('adaptive_log_probs: token statistics go with a pick, not with the full log-prob rows or guidance')
+    skw = {'stats': stats} if stats is not None else {}      # (a call without statistics is the call it was)
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
@@ -1966,10 +1988,11 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
         if guide is not None:    # (a call without guidance is the call it was: stand-ins for head_step keep working)
             return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, guide=guide)
         if mask is not None:     # (a call without a mask is the call it was: stand-ins for head_step keep working)
-            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask)
+            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask,
+                                    **skw)
         if pen is not None:      # (a call without penalties is the call it was: stand-ins for head_step keep working)
-            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen)
-        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force)
+            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, **skw)
+        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, **skw)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
     def logits(a, w):                    # fp32 rows start on 16 bytes (see AdaptiveLossFn): vector stores in the epilogue
@@ -1985,7 +2008,9 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     vocab = c0 + sum(nn_)
 
     def forced(picked):
-        return picked if force is None else logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
+        if force is not None:
+            logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
+        return picked if stats is None else logprob_stats(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, stats)
     if sample is not None and not want_full:
         return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample, pen=pen,
                                      **({'mask': mask} if mask is not None else {})))
