@@ -1471,6 +1471,9 @@ static int fill_args(AttnArgs& a, const void* q, const void* k, const void* v, v
                v_ss % vec == 0 && v_sb % vec == 0, "attention: strides must be multiples of a 16-byte chunk");
   TELL_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0,
                "attention: q/k/v must be 16-byte aligned");
+  // out is stored in 8-byte pieces by the bf16 forward and read back (with dout) as 16-byte chunks by the backward
+  TELL_REQUIRE(o_st % vec == 0 && o_sb % vec == 0, "attention: out strides must be multiples of a 16-byte chunk");
+  TELL_REQUIRE(out != nullptr && ((uintptr_t)out & 15) == 0, "attention: out must be given and 16-byte aligned");
   a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.mask = mask; a.bias_k = bias_k; a.bias_v = bias_v;
   a.q_st = q_st; a.q_sb = q_sb; a.k_ss = k_ss; a.k_sb = k_sb; a.v_ss = v_ss; a.v_sb = v_sb;
   a.o_st = o_st; a.o_sb = o_sb; a.B = B; a.H = H; a.Tq = Tq; a.S = S;
@@ -1551,6 +1554,9 @@ extern "C" int tell_attn_bwd(const void* q, const void* k, const void* v, const 
                      dtype);
   if (rc) return rc;
   TELL_REQUIRE(!bias_k || (dbias_k && dbias_v), "attention bwd: dbias buffers required with bias rows");
+  TELL_REQUIRE(dout != nullptr && lse != nullptr, "attention bwd: dout and lse (the forward's) must be given");
+  TELL_REQUIRE(((uintptr_t)dout & 15) == 0, "attention bwd: dout must be 16-byte aligned");
+  TELL_REQUIRE(dq != nullptr && dk != nullptr && dv != nullptr, "attention bwd: dq, dk and dv must be given");
   a.dout = dout; a.o = out; a.dq = dq; a.dk = dk; a.dv = dv; a.dbias_k = dbias_k; a.dbias_v = dbias_v;
   // the two partial buffers may be the halves of ONE [B, 2 H D] buffer (dbias_v == dbias_k + H D): one column-sum
   // launch then folds both bias gradients
