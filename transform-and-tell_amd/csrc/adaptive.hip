@@ -9,6 +9,7 @@
 // whole step has no data-dependent launch and no host synchronisation.
 #include "common.h"
 #include "options.h"
+#include "logits_args.h"
 
 #define MAX_BANDS 4
 
@@ -397,6 +398,10 @@ __global__ __launch_bounds__(1024) void logprob_argmax_kernel(LogProbArgs p) {
 // on 16 bytes.  64 of the 128 registers a 1024-thread workgroup leaves each thread.
 __device__ constexpr int LPF_CAP[4] = {2, 4, 8, 2};
 __device__ constexpr int LPF_OFF[4] = {0, 2, 6, 14};
+// (the launchers' side of the capacity, logits_regs() in logits_args.h: LPF_CAP[i] * 1024 threads * 4 floats)
+static_assert(LOGITS_REGS_CAP[0] == LPF_CAP[0] * 1024 * 4 && LOGITS_REGS_CAP[1] == LPF_CAP[1] * 1024 * 4 &&
+              LOGITS_REGS_CAP[2] == LPF_CAP[2] * 1024 * 4 && LOGITS_REGS_CAP[3] == LPF_CAP[3] * 1024 * 4,
+              "LOGITS_REGS_CAP (logits_args.h) must follow LPF_CAP");
 // K = 1: arg-max (token, token_lp); K = 4 / 8: every thread keeps its K best while scanning its registers, the block pops
 // the global best k times (beam search: tokens / lps [rows, k], best first).
 // BAN (tell_adaptive_logprob_topk_banned): the row's ban list (ban[i][0 .. n_ban[i])) becomes a bitmap over the vocabulary
@@ -883,6 +888,17 @@ __global__ __launch_bounds__(256) void logprob_topk_masked_kernel(LogProbArgs p,
                                                                   float* __restrict__ lps, MaskArgs ma) {
   logprob_topk_body<K, false, false, true>(p, k, tokens, lps, ma);
 }
+// What every launcher below builds from its Logits (logits_args.h): the kernels' view of them ...
+static LogProbArgs logprob_args(const Logits& lg, float* log_probs = nullptr, long ld_lp = 0, int* token = nullptr,
+                                float* token_lp = nullptr) {
+  LogProbArgs p;
+  p.head = lg.head; p.ld_head = lg.ld_head; p.head_n = lg.c0 + lg.n_tails; p.c0 = lg.c0; p.n_tails = lg.n_tails; p.rows = lg.rows;
+  for (int i = 0; i < 3; ++i) { p.tail[i] = lg.tail[i]; p.ld_tail[i] = lg.ld[i]; p.tail_n[i] = lg.n[i]; }
+  p.log_probs = log_probs; p.ld_lp = ld_lp; p.token = token; p.token_lp = token_lp;
+  return p;
+}
+// ... and the LDS bytes of the bitmap over the vocabulary (ban_bits).
+static size_t bitmap_lds(int vocab) { return (size_t)((vocab + 31) >> 5) * sizeof(unsigned); }
 extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c0, int n_tails,
                                           const float* tail0, long ld0, int n0, const float* tail1, long ld1,
                                           int n1, const float* tail2, long ld2, int n2, int rows, int k,
@@ -890,19 +906,9 @@ extern "C" int tell_adaptive_logprob_topk(const float* head, long ld_head, int c
   TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk: up to 3 tails");
   TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk: 1 <= k <= 8");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const LogProbArgs p = logprob_args(lg);
+  if (logits_regs(lg)) {
     if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps, BanArgs{});
     else hipLaunchKernelGGL((logprob_regs_kernel<8, false>), dim3(rows), dim3(1024), 0, stream, p, k, tokens, lps, BanArgs{});
     return tell_check_launch("logprob_topk (registers)");
@@ -922,24 +928,12 @@ extern "C" int tell_adaptive_logprob_topk_banned(const float* head, long ld_head
   TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_banned: 1 <= k <= 8");
   TELL_REQUIRE(ban && n_ban && ld_ban >= 1, "logprob_topk_banned: ban [rows, ld_ban] and n_ban [rows]");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  BanArgs ba;
-  ba.ban = ban; ba.ld_ban = ld_ban; ba.n_ban = n_ban;
-  ba.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const LogProbArgs p = logprob_args(lg);
+  const BanArgs ba{ban, ld_ban, n_ban, (int)logits_vocab(lg)};
   TELL_REQUIRE(ba.vocab > 0 && ba.vocab <= (1 << 18), "logprob_topk_banned: vocab <= 2^18 (the ban bitmap: 32 KB of LDS)");
-  const size_t lds = (size_t)((ba.vocab + 31) >> 5) * sizeof(unsigned);
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  const size_t lds = bitmap_lds(ba.vocab);
+  if (logits_regs(lg)) {
     if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ba);
     else hipLaunchKernelGGL((logprob_regs_kernel<8, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ba);
     return tell_check_launch("logprob_topk_banned (registers)");
@@ -951,17 +945,17 @@ extern "C" int tell_adaptive_logprob_topk_banned(const float* head, long ld_head
 
 // tell_adaptive_logprob_topk over penalised scores (include/tell_hip.h): pen_tok / pen_cnt int32 [rows, ld_pen], n_pen int32
 // [rows] (tell_decode_token_counts), sub fp32 [n_sub] on the device.
-static int pen_args(PenArgs& pa, int c0, int n_tails, int n0, int n1, int n2, const int* pen_tok, const int* pen_cnt,
-                    long ld_pen, const int* n_pen, float theta, const float* sub, int n_sub) {
+static int pen_args(PenArgs& pa, const Logits& lg, const int* pen_tok, const int* pen_cnt, long ld_pen, const int* n_pen,
+                    float theta, const float* sub, int n_sub) {
   TELL_REQUIRE(pen_tok && pen_cnt && n_pen && ld_pen >= 1, "logprob penalised: pen_tok / pen_cnt [rows, ld_pen] and n_pen [rows]");
   TELL_REQUIRE(sub && n_sub >= 1, "logprob penalised: sub fp32 [n_sub >= 1]");
   TELL_REQUIRE(theta >= 1.f && theta < INFINITY, "logprob penalised: theta finite and >= 1");
   pa.tok = pen_tok; pa.cnt = pen_cnt; pa.ld = ld_pen; pa.n_pen = n_pen; pa.sub = sub; pa.n_sub = n_sub; pa.theta = theta;
-  pa.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  pa.vocab = (int)logits_vocab(lg);
   TELL_REQUIRE(pa.vocab > 0 && pa.vocab <= (1 << 18), "logprob penalised: vocab <= 2^18 (the bitmap: 32 KB of LDS)");
   return TELL_OK;
 }
-static size_t pen_lds(const PenArgs& pa) { return (size_t)(((pa.vocab + 31) >> 5) + 2 * PEN_MAX_LIST) * sizeof(unsigned); }
+static size_t pen_lds(const PenArgs& pa) { return bitmap_lds(pa.vocab) + 2 * PEN_MAX_LIST * sizeof(unsigned); }
 extern "C" int tell_adaptive_logprob_topk_penalised(const float* head, long ld_head, int c0, int n_tails,
                                                     const float* tail0, long ld0, int n0, const float* tail1, long ld1,
                                                     int n1, const float* tail2, long ld2, int n2, int rows, int k,
@@ -971,27 +965,17 @@ extern "C" int tell_adaptive_logprob_topk_penalised(const float* head, long ld_h
   TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk_penalised: up to 3 tails");
   TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_penalised: 1 <= k <= 8");
   TELL_REQUIRE(tokens && lps, "logprob_topk_penalised: tokens and lps [rows, k]");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
   PenArgs pa;
-  const int rc = pen_args(pa, c0, n_tails, n0, n1, n2, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
+  const int rc = pen_args(pa, lg, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
   if (rc != TELL_OK) return rc;
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  const LogProbArgs p = logprob_args(lg);
   const size_t lds = pen_lds(pa);
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
-    if (k == 1) {                                            // the arg-max form: its winner goes to p.token / p.token_lp
-      p.token = tokens; p.token_lp = lps;
-      hipLaunchKernelGGL((logprob_regs_kernel<1, false, true>), dim3(rows), dim3(1024), lds, stream, p, 1, tokens, lps, pa);
+  if (logits_regs(lg)) {
+    if (k == 1) {                                            // the arg-max form: its winner goes to token / token_lp
+      hipLaunchKernelGGL((logprob_regs_kernel<1, false, true>), dim3(rows), dim3(1024), lds, stream,
+                         logprob_args(lg, nullptr, 0, tokens, lps), 1, tokens, lps, pa);
     } else if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, pa);
     else hipLaunchKernelGGL((logprob_regs_kernel<8, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, pa);
     return tell_check_launch("logprob_topk_penalised (registers)");
@@ -1003,12 +987,12 @@ extern "C" int tell_adaptive_logprob_topk_penalised(const float* head, long ld_h
 
 // tell_adaptive_logprob_topk under a vocabulary mask (include/tell_hip.h): mask uint32 [rows / per, ld_mask >= words], row r
 // reads mask row r / per; ban / n_ban as tell_adaptive_logprob_topk_banned or NULL.
-static int mask_args(MaskArgs& ma, int c0, int n_tails, int n0, int n1, int n2, int rows, const uint32_t* mask, long ld_mask,
-                     int per, const int* ban, long ld_ban, const int* n_ban) {
-  ma.vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+static int mask_args(MaskArgs& ma, const Logits& lg, const uint32_t* mask, long ld_mask, int per, const int* ban, long ld_ban,
+                     const int* n_ban) {
+  ma.vocab = (int)logits_vocab(lg);
   TELL_REQUIRE(ma.vocab > 0 && ma.vocab <= (1 << 18), "logprob masked: vocab <= 2^18 (the bitmap: 32 KB of LDS)");
   TELL_REQUIRE(mask && ld_mask >= (ma.vocab + 31) / 32, "logprob masked: mask uint32 [rows / per, ld_mask >= words]");
-  TELL_REQUIRE(per >= 1 && rows % per == 0, "logprob masked: rows must be a multiple of per >= 1");
+  TELL_REQUIRE(per >= 1 && lg.rows % per == 0, "logprob masked: rows must be a multiple of per >= 1");
   TELL_REQUIRE(!ban || ld_ban >= 1, "logprob masked: ban [rows, ld_ban >= 1]");
   ma.mask = mask; ma.ld_mask = ld_mask; ma.per = per; ma.ban = ban; ma.ld_ban = ld_ban; ma.n_ban = n_ban;
   return TELL_OK;
@@ -1021,24 +1005,14 @@ extern "C" int tell_adaptive_logprob_topk_masked(const float* head, long ld_head
   TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_topk_masked: up to 3 tails");
   TELL_REQUIRE(k >= 1 && k <= 8, "logprob_topk_masked: 1 <= k <= 8");
   TELL_REQUIRE(tokens && lps, "logprob_topk_masked: tokens and lps [rows, k]");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
   MaskArgs ma;
-  const int rc = mask_args(ma, c0, n_tails, n0, n1, n2, rows, mask, ld_mask, per, ban, ld_ban, n_ban);
+  const int rc = mask_args(ma, lg, mask, ld_mask, per, ban, ld_ban, n_ban);
   if (rc != TELL_OK) return rc;
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  const size_t lds = (size_t)((ma.vocab + 31) >> 5) * sizeof(unsigned);
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  const LogProbArgs p = logprob_args(lg);
+  const size_t lds = bitmap_lds(ma.vocab);
+  if (logits_regs(lg)) {
     if (k <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ma);
     else hipLaunchKernelGGL((logprob_regs_kernel<8, false, false, true>), dim3(rows), dim3(1024), lds, stream, p, k, tokens, lps, ma);
     return tell_check_launch("logprob_topk_masked (registers)");
@@ -1055,19 +1029,9 @@ extern "C" int tell_adaptive_logprob_argmax(const float* head, long ld_head, int
                                             float* token_lp, hipStream_t stream) {
   TELL_REQUIRE(n_tails >= 0 && n_tails <= 3, "logprob_argmax: up to 3 tails");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = log_probs; p.ld_lp = ld_lp; p.token = token; p.token_lp = token_lp;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (!log_probs && regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
-      (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096)) {
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const LogProbArgs p = logprob_args(lg, log_probs, ld_lp, token, token_lp);
+  if (!log_probs && logits_regs(lg)) {                       // (the register form does not write the full rows)
     hipLaunchKernelGGL((logprob_regs_kernel<1, false>), dim3(rows), dim3(1024), 0, stream, p, 1, (int*)nullptr, (float*)nullptr,
                        BanArgs{});
     return tell_check_launch("logprob_argmax (registers)");
@@ -1203,25 +1167,14 @@ extern "C" int tell_adaptive_logprob_forced(const float* head, long ld_head, int
   TELL_REQUIRE(beams >= 1 && (row_ids || (long)n_samples * beams >= rows), "logprob_forced: rows / beams exceeds n_samples");
   TELL_REQUIRE(step_dev || step >= 0, "logprob_forced: step >= 0");
   TELL_REQUIRE(tokens && lps, "logprob_forced: tokens and lps [rows, k]");
-  const int vocab = c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
-  TELL_REQUIRE(pad >= 0 && pad < vocab, "logprob_forced: pad must be a token of the vocabulary (it is the next step's input of a filler hypothesis)");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  TELL_REQUIRE(pad >= 0 && pad < (int)logits_vocab(lg), "logprob_forced: pad must be a token of the vocabulary (it is the next step's input of a filler hypothesis)");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n_tails > 0 ? n0 : 0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n_tails > 1 ? n1 : 0;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n_tails > 2 ? n2 : 0;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  const LogProbArgs p = logprob_args(lg);
   ForcedArgs a;
   a.prefix = prefix; a.ld_prefix = ld_prefix; a.P = P; a.plen = plen; a.n_samples = n_samples; a.row_ids = row_ids;
   a.beams = beams; a.step = step; a.step_dev = step_dev; a.pad = pad; a.k = k; a.tokens = tokens; a.lps = lps;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  if (logits_regs(lg)) {
     hipLaunchKernelGGL((logprob_forced_kernel<true>), dim3(rows), dim3(1024), 0, stream, p, a);
     return tell_check_launch("logprob_forced (registers)");
   }
@@ -1310,23 +1263,13 @@ extern "C" int tell_adaptive_logprob_stats(const float* head, long ld_head, int 
   TELL_REQUIRE(slots >= 1 && (step_dev || (step >= 0 && step < slots)), "logprob_stats: 0 <= step < slots");
   TELL_REQUIRE(alt_tok && alt_lp && rank && entropy && chosen_lp,
                "logprob_stats: alt_tok / alt_lp [slots, rows, n] and rank / entropy / chosen_lp [slots, rows]");
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n_tails > 0 ? n0 : 0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n_tails > 1 ? n1 : 0;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n_tails > 2 ? n2 : 0;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const LogProbArgs p = logprob_args(lg);
   StatsArgs a;
   a.chosen = chosen; a.ld_chosen = ld_chosen; a.finished = finished; a.n = n; a.slots = slots; a.step = step;
   a.step_dev = step_dev; a.pad = pad; a.alt_tok = alt_tok; a.alt_lp = alt_lp; a.rank = rank; a.entropy = entropy;
   a.chosen_lp = chosen_lp;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  if (logits_regs(lg)) {
     // (K as tell_adaptive_logprob_topk picks it for k = n: the alternatives come from the same instantiation's code)
     if (n <= 4) hipLaunchKernelGGL((logprob_regs_kernel<4, false, false, false, true>), dim3(rows), dim3(1024), 0, stream, p, n,
                                    (int*)nullptr, (float*)nullptr, a);
@@ -1785,6 +1728,15 @@ __global__ __launch_bounds__(1024) void logprob_sample_stream_kernel(LogProbArgs
     sample_row<NUC>(each, each, tmax, i, a, sm);
   }
 }
+// The draw's arguments with every rule's field defined (topp = 0, nuc_size / nuc_key / typ_c = NULL): a launcher sets the
+// fields of its own rule only.
+static SampleArgs sample_args(int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids, int step, const int* step_dev,
+                              int* tokens, float* lps) {
+  SampleArgs a{};
+  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
+  a.tokens = tokens; a.lps = lps;
+  return a;
+}
 extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
                                             int rows, int k, float inv_temp, const uint32_t* seed_dev, const int* row_ids,
@@ -1793,25 +1745,13 @@ extern "C" int tell_adaptive_logprob_sample(const float* head, long ld_head, int
   TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample: 1 <= k <= 64");
   TELL_REQUIRE(inv_temp > 0.f, "logprob_sample: inv_temp > 0");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample: seed_dev, tokens and lps are required");
-  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const long vocab = logits_vocab(lg);
   TELL_REQUIRE(vocab >= k && vocab < (1L << 24), "logprob_sample: k <= vocab < 2^24");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  SampleArgs a;
-  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  const LogProbArgs p = logprob_args(lg);
+  const SampleArgs a = sample_args(k, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
+  if (logits_regs(lg)) {
     hipLaunchKernelGGL(logprob_sample_regs_kernel<false>, dim3(rows), dim3(1024), 0, stream, p, a);
     return tell_check_launch("logprob_sample (registers)");
   }
@@ -1831,28 +1771,16 @@ extern "C" int tell_adaptive_logprob_sample_penalised(const float* head, long ld
   TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample_penalised: 1 <= k <= 64");
   TELL_REQUIRE(inv_temp > 0.f, "logprob_sample_penalised: inv_temp > 0");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample_penalised: seed_dev, tokens and lps are required");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
   PenArgs pa;
-  const int rc = pen_args(pa, c0, n_tails, n0, n1, n2, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
+  const int rc = pen_args(pa, lg, pen_tok, pen_cnt, ld_pen, n_pen, theta, sub, n_sub);
   if (rc != TELL_OK) return rc;
   TELL_REQUIRE(pa.vocab >= k, "logprob_sample_penalised: k <= vocab");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  SampleArgs a;
-  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr; a.typ_c = nullptr;
+  const LogProbArgs p = logprob_args(lg);
+  const SampleArgs a = sample_args(k, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
   const size_t lds = pen_lds(pa);
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  if (logits_regs(lg)) {
     hipLaunchKernelGGL((logprob_sample_regs_kernel<false, true>), dim3(rows), dim3(1024), lds, stream, p, a, pa);
     return tell_check_launch("logprob_sample_penalised (registers)");
   }
@@ -1871,28 +1799,16 @@ extern "C" int tell_adaptive_logprob_sample_masked(const float* head, long ld_he
   TELL_REQUIRE(k >= 1 && k <= 64, "logprob_sample_masked: 1 <= k <= 64");
   TELL_REQUIRE(inv_temp > 0.f, "logprob_sample_masked: inv_temp > 0");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_sample_masked: seed_dev, tokens and lps are required");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
   MaskArgs ma;
-  const int rc = mask_args(ma, c0, n_tails, n0, n1, n2, rows, mask, ld_mask, per, nullptr, 0, nullptr);
+  const int rc = mask_args(ma, lg, mask, ld_mask, per, nullptr, 0, nullptr);
   if (rc != TELL_OK) return rc;
   TELL_REQUIRE(ma.vocab >= k, "logprob_sample_masked: k <= vocab");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs p;
-  p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n1;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n2;
-  p.log_probs = nullptr; p.ld_lp = 0; p.token = nullptr; p.token_lp = nullptr;
-  SampleArgs a;
-  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = 0.f; a.nuc_size = nullptr; a.nuc_key = nullptr; a.typ_c = nullptr;
-  const size_t lds = (size_t)((ma.vocab + 31) >> 5) * sizeof(unsigned);
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs_env = tell_opt(OPT_ARGMAX_REGS) != 0;      // A/B aid (and the tests' way to the streaming form)
-  if (regs_env && aligned && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) && (n_tails < 2 || n1 <= 8 * 4096) &&
-      (n_tails < 3 || n2 <= 2 * 4096)) {
+  const LogProbArgs p = logprob_args(lg);
+  const SampleArgs a = sample_args(k, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
+  const size_t lds = bitmap_lds(ma.vocab);
+  if (logits_regs(lg)) {
     hipLaunchKernelGGL((logprob_sample_regs_kernel<false, false>), dim3(rows), dim3(1024), lds, stream, p, a, ma);
     return tell_check_launch("logprob_sample_masked (registers)");
   }
@@ -2554,24 +2470,14 @@ extern "C" int tell_adaptive_logprob_nucleus(const float* head, long ld_head, in
   TELL_REQUIRE(inv_temp > 0.f, "logprob_nucleus: inv_temp > 0");
   TELL_REQUIRE(p > 0.f && p <= 1.f, "logprob_nucleus: 0 < p <= 1");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_nucleus: seed_dev, tokens and lps are required");
-  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const long vocab = logits_vocab(lg);
   TELL_REQUIRE(vocab >= 1 && vocab >= k && vocab < (1L << 19), "logprob_nucleus: k <= vocab < 2^19");
   if (rows <= 0) return TELL_OK;
-  LogProbArgs q;
-  q.head = head; q.ld_head = ld_head; q.head_n = c0 + n_tails; q.c0 = c0; q.n_tails = n_tails; q.rows = rows;
-  q.tail[0] = tail0; q.ld_tail[0] = ld0; q.tail_n[0] = n0;
-  q.tail[1] = tail1; q.ld_tail[1] = ld1; q.tail_n[1] = n1;
-  q.tail[2] = tail2; q.ld_tail[2] = ld2; q.tail_n[2] = n2;
-  q.log_probs = nullptr; q.ld_lp = 0; q.token = nullptr; q.token_lp = nullptr;
-  SampleArgs a;
-  a.k = k; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = p; a.nuc_size = nuc_size; a.nuc_key = nuc_key;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs = tell_opt(OPT_ARGMAX_REGS) != 0 && aligned && q.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
-                    (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096);
+  const LogProbArgs q = logprob_args(lg);
+  SampleArgs a = sample_args(k, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
+  a.topp = p; a.nuc_size = nuc_size; a.nuc_key = nuc_key;
+  const bool regs = logits_regs(lg);
   if (k > 0) {                                                // the top-k sampler's selection, then the nucleus of the k
     if (regs) hipLaunchKernelGGL(logprob_sample_regs_kernel<true>, dim3(rows), dim3(1024), 0, stream, q, a);
     else hipLaunchKernelGGL(logprob_sample_stream_kernel<true>, dim3(rows), dim3(1024), 0, stream, q, a);
@@ -2585,23 +2491,10 @@ extern "C" int tell_adaptive_logprob_nucleus(const float* head, long ld_head, in
 // ------------------------------------------------------------------ min-p and locally typical sampling
 // include/tell_hip.h tell_adaptive_logprob_minp / _typical: the nucleus kernels under another rule (RULE 2 / 1 above).
 template <int RULE>
-static int truncation_launch(const char* what, const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
-                             int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2, int rows,
-                             SampleArgs a, hipStream_t stream) {
-  LogProbArgs q;
-  q.head = head; q.ld_head = ld_head; q.head_n = c0 + n_tails; q.c0 = c0; q.n_tails = n_tails; q.rows = rows;
-  q.tail[0] = tail0; q.ld_tail[0] = ld0; q.tail_n[0] = n0;
-  q.tail[1] = tail1; q.ld_tail[1] = ld1; q.tail_n[1] = n1;
-  q.tail[2] = tail2; q.ld_tail[2] = ld2; q.tail_n[2] = n2;
-  q.log_probs = nullptr; q.ld_lp = 0; q.token = nullptr; q.token_lp = nullptr;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  const bool regs = tell_opt(OPT_ARGMAX_REGS) != 0 && aligned && q.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
-                    (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096);
-  if (regs) hipLaunchKernelGGL(logprob_nucleus_regs_kernel<RULE>, dim3(rows), dim3(1024), 0, stream, q, a);
-  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel<RULE>, dim3(rows), dim3(1024), 0, stream, q, a);
+static int truncation_launch(const char* what, const Logits& lg, SampleArgs a, hipStream_t stream) {
+  const LogProbArgs q = logprob_args(lg);
+  if (logits_regs(lg)) hipLaunchKernelGGL(logprob_nucleus_regs_kernel<RULE>, dim3(lg.rows), dim3(1024), 0, stream, q, a);
+  else hipLaunchKernelGGL(logprob_nucleus_stream_kernel<RULE>, dim3(lg.rows), dim3(1024), 0, stream, q, a);
   return tell_check_launch(what);
 }
 extern "C" int tell_adaptive_logprob_minp(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
@@ -2613,14 +2506,13 @@ extern "C" int tell_adaptive_logprob_minp(const float* head, long ld_head, int c
   TELL_REQUIRE(inv_temp > 0.f, "logprob_minp: inv_temp > 0");
   TELL_REQUIRE(log_minp <= 0.f, "logprob_minp: log_minp = log(m) with 0 < m <= 1");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_minp: seed_dev, tokens and lps are required");
-  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const long vocab = logits_vocab(lg);
   TELL_REQUIRE(vocab >= 1 && vocab < (1L << 19), "logprob_minp: 1 <= vocab < 2^19");
   if (rows <= 0) return TELL_OK;
-  SampleArgs a;
-  a.k = 0; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = log_minp; a.nuc_size = nuc_size; a.nuc_key = nullptr; a.typ_c = nullptr;
-  return truncation_launch<2>("logprob_minp", head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows,
-                              a, stream);
+  SampleArgs a = sample_args(0, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
+  a.topp = log_minp; a.nuc_size = nuc_size;
+  return truncation_launch<2>("logprob_minp", lg, a, stream);
 }
 extern "C" int tell_adaptive_logprob_typical(const float* head, long ld_head, int c0, int n_tails, const float* tail0, long ld0,
                                              int n0, const float* tail1, long ld1, int n1, const float* tail2, long ld2, int n2,
@@ -2631,14 +2523,13 @@ extern "C" int tell_adaptive_logprob_typical(const float* head, long ld_head, in
   TELL_REQUIRE(inv_temp > 0.f, "logprob_typical: inv_temp > 0");
   TELL_REQUIRE(tau > 0.f && tau <= 1.f, "logprob_typical: 0 < tau <= 1");
   TELL_REQUIRE(seed_dev && tokens && lps, "logprob_typical: seed_dev, tokens and lps are required");
-  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  const long vocab = logits_vocab(lg);
   TELL_REQUIRE(vocab >= 1 && vocab < (1L << 19), "logprob_typical: 1 <= vocab < 2^19");
   if (rows <= 0) return TELL_OK;
-  SampleArgs a;
-  a.k = 0; a.inv_temp = inv_temp; a.seed_dev = seed_dev; a.row_ids = row_ids; a.step = step; a.step_dev = step_dev;
-  a.tokens = tokens; a.lps = lps; a.topp = tau; a.nuc_size = nuc_size; a.nuc_key = nuc_key; a.typ_c = typ_c;
-  return truncation_launch<1>("logprob_typical", head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2,
-                              rows, a, stream);
+  SampleArgs a = sample_args(0, inv_temp, seed_dev, row_ids, step, step_dev, tokens, lps);
+  a.topp = tau; a.nuc_size = nuc_size; a.nuc_key = nuc_key; a.typ_c = typ_c;
+  return truncation_launch<1>("logprob_typical", lg, a, stream);
 }
 
 // the nucleus of given candidates (sorted best first, as tell_sample_candidates takes them): one thread per row

@@ -14,7 +14,7 @@ mkdir -p $OBJ
 pids=""
 for s in $SRCS; do
   o=$OBJ/$s.o
-  if [ ! -f $o ] || [ $s.hip -nt $o ] || [ common.h -nt $o ] || [ options.h -nt $o ] || [ gemm_common.h -nt $o ] || [ gemm_epi.h -nt $o -a "${s#gemm}" != "$s" ] || [ gemm_q4_loop.inc -nt $o -a "${s#gemm_q4}" != "$s" ] || [ gemm_q4e_loop.inc -nt $o -a "$s" = gemm_q4e ] || [ ../../include/tell_hip.h -nt $o ]; then
+  if [ ! -f $o ] || [ $s.hip -nt $o ] || [ common.h -nt $o ] || [ options.h -nt $o ] || [ gemm_common.h -nt $o ] || [ logits_args.h -nt $o -a \( $s = adaptive -o $s = guidance \) ] || [ gemm_epi.h -nt $o -a "${s#gemm}" != "$s" ] || [ gemm_q4_loop.inc -nt $o -a "${s#gemm_q4}" != "$s" ] || [ gemm_q4e_loop.inc -nt $o -a "$s" = gemm_q4e ] || [ ../../include/tell_hip.h -nt $o ]; then
     hipcc $FLAGS -c $s.hip -o $o &
     pids="$pids $!"
   fi

@@ -13,6 +13,7 @@
 // gamma is read from device memory: a captured step serves every gamma.
 #include "common.h"
 #include "options.h"
+#include "logits_args.h"
 
 namespace {
 
@@ -29,6 +30,10 @@ struct GuideArgs {
 typedef float f4 __attribute__((ext_vector_type(4)));
 __device__ constexpr int G_CAP[4] = {2, 4, 8, 2};      // float4 per thread and segment: the capacity of logprob_regs_kernel
 __device__ constexpr int G_OFF[4] = {0, 2, 6, 14};
+// (so the launcher asks logits_regs() of logits_args.h, the plain launchers' own predicate, whether a row fits)
+static_assert(LOGITS_REGS_CAP[0] == G_CAP[0] * 1024 * 4 && LOGITS_REGS_CAP[1] == G_CAP[1] * 1024 * 4 &&
+              LOGITS_REGS_CAP[2] == G_CAP[2] * 1024 * 4 && LOGITS_REGS_CAP[3] == G_CAP[3] * 1024 * 4,
+              "LOGITS_REGS_CAP (logits_args.h) must follow G_CAP");
 __device__ constexpr int G_SEG[16] = {0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 3, 3};   // the segment of register chunk c
 
 // The thread index as a value the compiler knows nothing about: every phase of the register form derives its element
@@ -401,25 +406,17 @@ extern "C" int tell_adaptive_logprob_topk_guided(const float* head, long ld_head
   TELL_REQUIRE(pair_offset >= rows && pair_offset >= 1, "logprob_topk_guided: pair_offset >= rows (the partners lie behind the conditional rows)");
   TELL_REQUIRE(c0 >= 1 && (n_tails < 1 || (tail0 && n0 >= 1)) && (n_tails < 2 || (tail1 && n1 >= 1)) &&
                (n_tails < 3 || (tail2 && n2 >= 1)), "logprob_topk_guided: c0 >= 1 and every tail non-empty");
-  const long vocab = (long)c0 + (n_tails > 0 ? n0 : 0) + (n_tails > 1 ? n1 : 0) + (n_tails > 2 ? n2 : 0);
-  TELL_REQUIRE(!s_rows || ld_s >= vocab, "logprob_topk_guided: s_rows fp32 [rows, ld_s >= vocab]");
+  const Logits lg = logits_of(head, ld_head, c0, n_tails, tail0, ld0, n0, tail1, ld1, n1, tail2, ld2, n2, rows);
+  TELL_REQUIRE(!s_rows || ld_s >= logits_vocab(lg), "logprob_topk_guided: s_rows fp32 [rows, ld_s >= vocab]");
   if (rows <= 0) return TELL_OK;
   GuideArgs p;
   p.head = head; p.ld_head = ld_head; p.head_n = c0 + n_tails; p.c0 = c0; p.n_tails = n_tails; p.rows = rows; p.k = k;
-  p.tail[0] = tail0; p.ld_tail[0] = ld0; p.tail_n[0] = n_tails > 0 ? n0 : 0;
-  p.tail[1] = tail1; p.ld_tail[1] = ld1; p.tail_n[1] = n_tails > 1 ? n1 : 0;
-  p.tail[2] = tail2; p.ld_tail[2] = ld2; p.tail_n[2] = n_tails > 2 ? n2 : 0;
+  for (int i = 0; i < 3; ++i) { p.tail[i] = lg.tail[i]; p.ld_tail[i] = lg.ld[i]; p.tail_n[i] = lg.n[i]; }
   p.pair_offset = pair_offset; p.gamma = gamma_dev; p.s_rows = s_rows; p.ld_s = ld_s; p.tokens = tokens; p.lps = lps;
-  const bool aligned = ld_head % 4 == 0 && ((uintptr_t)head % 16) == 0 &&
-                       (n_tails < 1 || (ld0 % 4 == 0 && ((uintptr_t)tail0 % 16) == 0)) &&
-                       (n_tails < 2 || (ld1 % 4 == 0 && ((uintptr_t)tail1 % 16) == 0)) &&
-                       (n_tails < 3 || (ld2 % 4 == 0 && ((uintptr_t)tail2 % 16) == 0));
-  // (... and whole float4 of a row are readable: the last one may reach into the row's padding)
-  const bool whole = ld_head >= ((p.head_n + 3) & ~3) && (n_tails < 1 || ld0 >= ((n0 + 3) & ~3)) &&
-                     (n_tails < 2 || ld1 >= ((n1 + 3) & ~3)) && (n_tails < 3 || ld2 >= ((n2 + 3) & ~3));
-  const bool regs = tell_opt(OPT_ARGMAX_REGS) != 0 && aligned && whole && p.head_n <= 2 * 4096 && (n_tails < 1 || n0 <= 4 * 4096) &&
-                    (n_tails < 2 || n1 <= 8 * 4096) && (n_tails < 3 || n2 <= 2 * 4096);
-  if (regs) {
+  // (the register form reads whole float4 of a row: the last one may reach into the row's padding)
+  bool whole = ld_head >= ((p.head_n + 3) & ~3);
+  for (int i = 0; i < n_tails; ++i) whole = whole && lg.ld[i] >= ((lg.n[i] + 3) & ~3);
+  if (logits_regs(lg) && whole) {
     if (k == 1) hipLaunchKernelGGL((guided_regs_kernel<1>), dim3(rows), dim3(1024), 0, stream, p);
     else if (k <= 4) hipLaunchKernelGGL((guided_regs_kernel<4>), dim3(rows), dim3(1024), 0, stream, p);
     else hipLaunchKernelGGL((guided_regs_kernel<8>), dim3(rows), dim3(1024), 0, stream, p);

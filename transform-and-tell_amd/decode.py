@@ -7,6 +7,7 @@ launch normalises it for the consumers, the DynamicConv step is one kernel (tell
 attentions are one launch against the projected K/V cache (tell_attn_decode).  Same arithmetic as the layer-by-layer
 path up to bf16 rounding points (pre-norm sums stay fp32 here); tests/test_gpu_fullsize.py bounds the difference.
 """
+import contextlib
 import ctypes
 import os
 import weakref
@@ -214,29 +215,16 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
     the tails' projected inputs from ONE skinny linear over [emb_0; class_proj; proj_1; proj_2] (logits fp32, the
     projections once more in bf16), one skinny linear per tail table, the register-resident arg-max.
     -> (token int32 [N], log-prob fp32 [N], None); topk = k > 0 (beam search): the k best of every row, best first,
-    (tokens int32 [N,k], log-probs fp32 [N,k], None); sample = (k, inv_temp, seed_dev, row_ids, step): the last launch is
-    the top-k draw instead of the arg-max (ops.logprob_sample); ban = (ban, n_ban) with topk: the last launch is
-    tell_adaptive_logprob_topk_banned (ops.logprob_topk); force (caption completion): one more launch behind that pick,
-    tell_adaptive_logprob_forced over the same logits (ops.logprob_forced) - without it the launches are what they were.
-    pen (ops._pen_args; with topk or sample): the last launch is tell_adaptive_logprob_topk_penalised / _sample_penalised.
-    mask (ops._mask_args; with topk - a ban list may join it - or a top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked.
-    guide = (pair_offset, gamma_dev) (context guidance; with topk alone): the last launch is
-    tell_adaptive_logprob_topk_guided over the N / 2 pairs of rows (r, r + pair_offset).
-    stats (a StatsSink; per-token statistics): one more launch behind the pick and the forced pick,
-    tell_adaptive_logprob_stats over the same logits and the tokens as they then stand (ops.logprob_stats) - on both layouts."""
-    if stats is not None and guide is not None:
-        raise ValueError('head_step: token statistics do not combine with guidance (paired rows)')
-    if guide is not None and (not topk or sample is not None or ban is not None or force is not None or pen is not None or
-                              mask is not None):
-        raise ValueError('head_step: guidance goes with topk = k >= 1 alone')
-    mk_g = {'guide': guide} if guide is not None else {}
-    if mask is not None and ((not topk and sample is None) or pen is not None):
-        raise ValueError('head_step: a vocabulary mask goes with topk = k >= 1 or a top-k draw, without penalties')
-    mk = {'mask': mask} if mask is not None else {}
-    if pen is not None and not topk and sample is None:
-        raise ValueError('head_step: penalties go with topk = k >= 1 or a top-k draw')
-    if ban is not None and (not topk or sample is not None):
-        raise ValueError('head_step: a ban list goes with topk = k >= 1')
+    (tokens int32 [N,k], log-probs fp32 [N,k], None).  Everything behind the logits is ops.logprob_pick's, on both layouts:
+    sample = (k, inv_temp, seed_dev, row_ids, step): the last launch is the top-k draw instead of the arg-max; ban = (ban,
+    n_ban) with topk: tell_adaptive_logprob_topk_banned; pen (ops._pen_args; with topk or sample):
+    tell_adaptive_logprob_topk_penalised / _sample_penalised; mask (ops._mask_args; with topk - a ban list may join it - or a
+    top-k draw): tell_adaptive_logprob_topk_masked / _sample_masked; guide = (pair_offset, gamma_dev) (context guidance,
+    DESIGN.md section 24; with topk alone): tell_adaptive_logprob_topk_guided over the N / 2 pairs of rows (r, r + pair_offset);
+    force (caption completion): one more launch behind that pick, tell_adaptive_logprob_forced over the same logits; stats (a
+    StatsSink; per-token statistics): one more behind the pick and the forced pick,
+    tell_adaptive_logprob_stats over the tokens as they then stand.  ops.check_pick says what combines."""
+    ops.check_pick('head_step', False, topk, sample, ban, force, pen, mask, guide, stats)
     N, E = x2.shape
     dev = x2.device
     c0, n_tails = cutoffs[0], len(tails) // 2
@@ -267,30 +255,15 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         w_big, offs = ops._cached(emb0, ('whead_composed',) + tuple((p._version, p.data_ptr()) for p in prm[1:]), make_big)
         LD = w_big.shape[0]
         logits = torch.empty(N, LD, dtype=torch.float32, device=dev)
-        if N >= 128 and HEAD_TILE128:
-            # 128 rows and more: 128-row tiles, so that the 100 MB table is streamed once, not once per 64-row tile (the
-            # launcher's own rule keeps 64x64 tiles below 512 tiles of 128x128; the choice is recorded with the captured launch)
-            with hip_mod.options(group_tile=128):
-                ops.gemm_grouped([dict(a=x2, b=w_big, out=logits, form='nt')])
-        else:
+        # 128 rows and more: 128-row tiles, so that the 100 MB table is streamed once, not once per 64-row tile (the
+        # launcher's own rule keeps 64x64 tiles below 512 tiles of 128x128; the choice is recorded with the captured launch)
+        with hip_mod.options(group_tile=128) if N >= 128 and HEAD_TILE128 else contextlib.nullcontext():
             ops.gemm_grouped([dict(a=x2, b=w_big, out=logits, form='nt')])
         ns = [e.shape[0] for e in embs] + [0] * (3 - n_tails)
         tl = [logits[:, offs[1 + i]:] if i < n_tails else None for i in range(3)]
         lds = [LD if i < n_tails else 0 for i in range(3)]
-
-        def forced(picked):
-            if force is not None:
-                ops.logprob_forced(logits, LD, c0, n_tails, tl, lds, ns, N, picked, force)
-            return picked if stats is None else ops.logprob_stats(logits, LD, c0, n_tails, tl, lds, ns, N, picked, stats)
-        if sample is not None:
-            return forced(ops.logprob_sample(logits, LD, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
-        if topk:
-            return forced(ops.logprob_topk(logits, LD, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk, **mk_g))
-        token = torch.empty(N, dtype=torch.int32, device=dev)
-        token_lp = torch.empty(N, dtype=torch.float32, device=dev)
-        call('tell_adaptive_logprob_argmax', logits, LD, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-             ns[2], N, None, 0, token, token_lp)
-        return forced((token, token_lp, None))
+        return ops.logprob_pick(ops.HeadLogits(logits, LD, c0, n_tails, tl, lds, ns, N), topk, sample, ban, force, pen, mask,
+                                guide, stats)
     w_all = ops._cached(emb0, ('whead_all', class_proj._version, class_proj.data_ptr()) +
                         tuple((p._version, p.data_ptr()) for p in projs),
                         lambda: torch.cat([ops.weight(emb0), ops.weight(class_proj)] + [ops.weight(p) for p in projs],
@@ -321,20 +294,8 @@ def head_step(x2, cutoffs, emb0, class_proj, tails, topk=0, sample=None, ban=Non
         ops.gemm(big[0]['a'], big[0]['b'], out=big[0]['out'])
     elif big:       # two dependent launches of 235 / 473 column tiles (12 + 16 us) -> one launch of 708
         ops.gemm_grouped(big)
-
-    def forced(picked):
-        if force is not None:
-            ops.logprob_forced(head, ld, c0, n_tails, tl, lds, ns, N, picked, force)
-        return picked if stats is None else ops.logprob_stats(head, ld, c0, n_tails, tl, lds, ns, N, picked, stats)
-    if sample is not None:
-        return forced(ops.logprob_sample(head, ld, c0, n_tails, tl, lds, ns, N, sample, pen=pen, **mk))
-    if topk:
-        return forced(ops.logprob_topk(head, ld, c0, n_tails, tl, lds, ns, N, int(topk), ban, pen=pen, **mk, **mk_g))
-    token = torch.empty(N, dtype=torch.int32, device=dev)
-    token_lp = torch.empty(N, dtype=torch.float32, device=dev)
-    call('tell_adaptive_logprob_argmax', head, ld, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-         ns[2], N, None, 0, token, token_lp)
-    return forced((token, token_lp, None))
+    return ops.logprob_pick(ops.HeadLogits(head, ld, c0, n_tails, tl, lds, ns, N), topk, sample, ban, force, pen, mask, guide,
+                            stats)
 
 
 class PackedKV:

@@ -8,6 +8,7 @@ weight gradients *directly* into the parameter's fp32 gradient buffer
 (`grad_buffer(p)`, which is `p.grad`), the way fused wgrad accumulation works in
 large-model trainers; the Functions therefore return None for parameters.
 """
+import collections
 import ctypes
 import math
 import os
@@ -1821,106 +1822,124 @@ def vocab_mask(ctx_ids, vocab, cls_bits=None, deny8=None, eos=2, pad=1, out=None
     return out
 
 
-def logprob_sample(head, ld_head, c0, n_tails, tl, lds, ns, N, sample, pen=None, mask=None):
-    """The sampling head's last launch (tell_adaptive_logprob_sample) over the fp32 logits of the head and the tails.
+class HeadLogits(collections.namedtuple('HeadLogits', 'head ld_head c0 n_tails tails lds ns rows')):
+    """The fp32 logits a generation head has computed, as every tell_adaptive_logprob_* entry point takes them: head [rows,
+    >= c0 + n_tails] with the row pitch ld_head and, three entries each, the tails' logits tails[i] [rows, ns[i]] with the
+    pitch lds[i] (None, 0, 0 behind n_tails)."""
+    __slots__ = ()
+
+    def abi(self):
+        """The fourteen leading arguments of those entry points (include/tell_hip.h), head .. rows."""
+        tl, lds, ns = self.tails, self.lds, self.ns
+        return (self.head, self.ld_head, self.c0, self.n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2], ns[2],
+                self.rows)
+
+    @property
+    def vocab(self):
+        return self.c0 + sum(self.ns[:self.n_tails])
+
+
+def check_pick(who, want_full, topk, sample, ban, force, pen, mask, guide, stats):
+    """What one pick of a generation head combines (logprob_pick, adaptive_log_probs, decode.head_step): ValueError('<who>: ...')
+    for everything else.  Only looks at which arguments are given, so it runs before any weight is touched."""
+    rule = sample is not None and len(sample) > 5           # nucleus / min-p / typical instead of the top-k draw
+    no_list = want_full or (not topk and sample is None)    # the plain arg-max, or the full log-prob rows
+    refusals = (
+        (guide is not None and (want_full or not topk or sample is not None or ban is not None or force is not None or
+                                pen is not None or mask is not None or stats is not None),
+         'guidance goes with topk = k >= 1 alone (no draw, ban list, forcing table, penalties, vocabulary mask or token '
+         'statistics: paired rows)'),
+        (stats is not None and want_full, 'token statistics go with a pick, not with the full log-prob rows'),
+        (force is not None and want_full, 'forced tokens go with a pick, not with the full log-prob rows'),
+        (mask is not None and (no_list or rule or pen is not None),
+         'a vocabulary mask goes with topk = k >= 1 or a top-k draw, not with a truncation rule or penalties'),
+        (pen is not None and (no_list or rule or ban is not None),
+         'penalties go with topk = k >= 1 or a top-k draw, not with a truncation rule or a ban list'),
+        (ban is not None and (not topk or sample is not None), 'a ban list goes with topk = k >= 1'),
+    )
+    for refused, why in refusals:
+        if refused:
+            raise ValueError('%s: %s' % (who, why))
+
+
+def _step_of(step):
+    """step: the host step index, or an int32 [1] device counter holding step - 1 (a captured decode step's) -> (step, step_dev)"""
+    return _step_args(step, step if torch.is_tensor(step) else None)
+
+
+def logprob_sample(lg, sample, pen=None, mask=None):
+    """The sampling head's last launch (tell_adaptive_logprob_sample) over the logits lg.
     sample = (k, inv_temp, seed_dev, row_ids, step): seed_dev an int32 [1] device word holding the seed; row_ids None or
-    int32 [N] device rows (the original batch rows of compacted rows); step the host step index, or an int32 [1] device
-    counter holding step - 1 (a captured decode step's).  -> (token int32 [N], log-prob fp32 [N] without the temperature, None).
+    int32 [N] device rows (the original batch rows of compacted rows); step as _step_of takes it.
+    -> (token int32 [N], log-prob fp32 [N] without the temperature, None).
     A sixth entry p makes it the nucleus draw (tell_adaptive_logprob_nucleus; k = 0: no top-k cut); a seventh names another
     rule for the sixth: 'minp' (m: tell_adaptive_logprob_minp, log(m) formed here in fp64) or 'typical' (tau:
     tell_adaptive_logprob_typical) - both over the whole row, k = 0.  pen (see _pen_args; the top-k draw only): the draw runs
     over the penalised scores (tell_adaptive_logprob_sample_penalised) and the second result is the token's score.
-    mask (see _mask_args; the top-k draw only): masked tokens are never candidates (tell_adaptive_logprob_sample_masked)."""
+    mask (see _mask_args; the top-k draw only): masked tokens are never candidates (tell_adaptive_logprob_sample_masked).
+    A part of logprob_pick: the combination must have passed check_pick - a rule beside pen or mask, or both of them,
+    is not looked for here and the first branch below that fits would run."""
+    N = lg.rows
     k, inv_temp, seed_dev, row_ids, step = sample[:5]
-    if pen is not None and len(sample) > 5:
-        raise ValueError('logprob_sample: penalties go with the top-k draw, not with a truncation rule')
-    if mask is not None and (len(sample) > 5 or pen is not None):
-        raise ValueError('logprob_sample: a vocabulary mask goes with the top-k draw, not with a truncation rule or penalties')
-    step_dev = step if torch.is_tensor(step) else None
-    token = torch.empty(N, dtype=torch.int32, device=head.device)
-    token_lp = torch.empty(N, dtype=torch.float32, device=head.device)
+    token = torch.empty(N, dtype=torch.int32, device=lg.head.device)
+    token_lp = torch.empty(N, dtype=torch.float32, device=lg.head.device)
+    rng, out = (seed_dev, row_ids, *_step_of(step)), (token, token_lp)
     if len(sample) > 6:
         rule, value = sample[6], float(sample[5])
         if rule not in ('minp', 'typical') or int(k) != 0:
             raise ValueError('logprob_sample: rule %r with k = %r (minp / typical take no top-k cut)' % (rule, k))
-        rows = (head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2], ns[2], N)
-        draw = (seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token, token_lp)
         if rule == 'minp':
-            call('tell_adaptive_logprob_minp', *rows, float(inv_temp), math.log(value), *draw, None)
+            call('tell_adaptive_logprob_minp', *lg.abi(), float(inv_temp), math.log(value), *rng, *out, None)
         else:
-            call('tell_adaptive_logprob_typical', *rows, float(inv_temp), value, *draw, None, None, None)
-        return token, token_lp, None
-    if len(sample) > 5:
-        call('tell_adaptive_logprob_nucleus', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
-             lds[2], ns[2], N, int(k), float(inv_temp), float(sample[5]), seed_dev, row_ids,
-             0 if step_dev is not None else int(step), step_dev, token, token_lp, None, None)
-        return token, token_lp, None
-    if pen is not None:
-        call('tell_adaptive_logprob_sample_penalised', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
-             tl[2], lds[2], ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step),
-             step_dev, *_pen_args(pen, N), token, token_lp)
-        return token, token_lp, None
-    if mask is not None:
-        call('tell_adaptive_logprob_sample_masked', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
-             tl[2], lds[2], ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step),
-             step_dev, *_mask_args(mask, N, c0 + sum(ns[:n_tails])), token, token_lp)
-        return token, token_lp, None
-    call('tell_adaptive_logprob_sample', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-         ns[2], N, int(k), float(inv_temp), seed_dev, row_ids, 0 if step_dev is not None else int(step), step_dev, token,
-         token_lp)
+            call('tell_adaptive_logprob_typical', *lg.abi(), float(inv_temp), value, *rng, *out, None, None, None)
+    elif len(sample) > 5:
+        call('tell_adaptive_logprob_nucleus', *lg.abi(), int(k), float(inv_temp), float(sample[5]), *rng, *out, None, None)
+    elif pen is not None:
+        call('tell_adaptive_logprob_sample_penalised', *lg.abi(), int(k), float(inv_temp), *rng, *_pen_args(pen, N), *out)
+    elif mask is not None:
+        call('tell_adaptive_logprob_sample_masked', *lg.abi(), int(k), float(inv_temp), *rng, *_mask_args(mask, N, lg.vocab), *out)
+    else:
+        call('tell_adaptive_logprob_sample', *lg.abi(), int(k), float(inv_temp), *rng, *out)
     return token, token_lp, None
 
 
-def logprob_topk(head, ld_head, c0, n_tails, tl, lds, ns, N, k, ban=None, pen=None, mask=None, guide=None):
+def logprob_topk(lg, k, ban=None, pen=None, mask=None, guide=None):
     """The top-k head's last launch: tell_adaptive_logprob_topk, or - ban = (ban int32 [N, ld_ban], n_ban int32 [N]) -
     tell_adaptive_logprob_topk_banned, or - pen (see _pen_args) - tell_adaptive_logprob_topk_penalised, whose second result
     holds the penalised scores, or - mask (see _mask_args), with or without a ban list - tell_adaptive_logprob_topk_masked.
     guide = (pair_offset, gamma fp32 [1] on the device) - tell_adaptive_logprob_topk_guided: rows 0 .. N - pair_offset - 1 are
     conditional, row r's partner is r + pair_offset, both get the pair's k guided candidates.
-    -> (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
-    tokens = torch.empty(N, k, dtype=torch.int32, device=head.device)
-    lps = torch.empty(N, k, dtype=torch.float32, device=head.device)
+    -> (tokens int32 [N, k], log-probs fp32 [N, k], None).
+    A part of logprob_pick: the combination must have passed check_pick - guidance beside a list, a mask or a ban list
+    beside penalties are not looked for here and the first branch below that fits would run."""
+    N = lg.rows
+    tokens = torch.empty(N, k, dtype=torch.int32, device=lg.head.device)
+    lps = torch.empty(N, k, dtype=torch.float32, device=lg.head.device)
+    bans, n_ban = ban if ban is not None else (None, None)
+    if ban is not None and (bans.shape[0] != N or n_ban.shape[0] != N or bans.dtype != torch.int32 or n_ban.dtype != torch.int32):
+        raise ValueError('logprob_topk: ban int32 [%d, ld] and n_ban int32 [%d] expected' % (N, N))
     if guide is not None:
         off, gamma = int(guide[0]), guide[1]
-        if ban is not None or pen is not None or mask is not None:
-            raise ValueError('logprob_topk: guidance does not combine with a ban list, penalties or a vocabulary mask')
-        if 2 * off != N or gamma.dtype != torch.float32 or gamma.numel() != 1 or gamma.device != head.device:
+        if 2 * off != N or gamma.dtype != torch.float32 or gamma.numel() != 1 or gamma.device != lg.head.device:
             raise ValueError('logprob_topk: guide = (pair_offset = %d / 2, gamma fp32 [1] on the device) expected' % N)
-        call('tell_adaptive_logprob_topk_guided', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
-             lds[2], ns[2], N - off, off, int(k), gamma, None, 0, tokens, lps)
-        return tokens, lps, None
-    if mask is not None:
-        if pen is not None:
-            raise ValueError('logprob_topk: a vocabulary mask and penalties do not combine')
-        bans, n_ban = ban if ban is not None else (None, None)
-        if ban is not None and (bans.shape[0] != N or n_ban.shape[0] != N or bans.dtype != torch.int32 or
-                                n_ban.dtype != torch.int32):
-            raise ValueError('logprob_topk: ban int32 [%d, ld] and n_ban int32 [%d] expected' % (N, N))
-        call('tell_adaptive_logprob_topk_masked', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
-             tl[2], lds[2], ns[2], N, int(k), *_mask_args(mask, N, c0 + sum(ns[:n_tails])), bans,
+        call('tell_adaptive_logprob_topk_guided', *lg._replace(rows=N - off).abi(), off, k, gamma, None, 0, tokens, lps)
+    elif mask is not None:
+        call('tell_adaptive_logprob_topk_masked', *lg.abi(), k, *_mask_args(mask, N, lg.vocab), bans,
              bans.stride(0) if ban is not None else 0, n_ban, tokens, lps)
     elif pen is not None:
-        if ban is not None:
-            raise ValueError('logprob_topk: a ban list and penalties do not combine')
-        call('tell_adaptive_logprob_topk_penalised', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
-             tl[2], lds[2], ns[2], N, int(k), *_pen_args(pen, N), tokens, lps)
-    elif ban is None:
-        call('tell_adaptive_logprob_topk', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2],
-             lds[2], ns[2], N, int(k), tokens, lps)
+        call('tell_adaptive_logprob_topk_penalised', *lg.abi(), k, *_pen_args(pen, N), tokens, lps)
+    elif ban is not None:
+        call('tell_adaptive_logprob_topk_banned', *lg.abi(), k, bans, bans.stride(0), n_ban, tokens, lps)
     else:
-        bans, n_ban = ban
-        if bans.shape[0] != N or n_ban.shape[0] != N or bans.dtype != torch.int32 or n_ban.dtype != torch.int32:
-            raise ValueError('logprob_topk: ban int32 [%d, ld] and n_ban int32 [%d] expected' % (N, N))
-        call('tell_adaptive_logprob_topk_banned', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1],
-             tl[2], lds[2], ns[2], N, int(k), bans, bans.stride(0), n_ban, tokens, lps)
+        call('tell_adaptive_logprob_topk', *lg.abi(), k, tokens, lps)
     return tokens, lps, None
 
 
-def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
+def logprob_forced(lg, picked, force):
     """Caption completion: tell_adaptive_logprob_forced behind the pick kernel, in place over picked = (tokens int32 [N] or
     [N, k], log-probs fp32 alike, None) and the logits that pick was taken from.  force = (prefix int64 [n_samples, P], plen
-    int32 [n_samples], row_ids None or int32 [N], beams, step, pad): step the host step index, or an int32 [1] device
-    counter holding step - 1 (a captured decode step's).  -> picked."""
+    int32 [n_samples], row_ids None or int32 [N], beams, step, pad); step as _step_of takes it."""
+    N = lg.rows
     prefix, plen, row_ids, beams, step, pad = force
     tokens, lps = picked[0], picked[1]
     k = tokens.numel() // max(N, 1)
@@ -1928,29 +1947,44 @@ def logprob_forced(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, force):
             plen.numel() != prefix.shape[0] or not plen.is_contiguous() or not tokens.is_contiguous() or \
             not lps.is_contiguous() or tokens.numel() != N * k or lps.numel() != N * k:
         raise ValueError('logprob_forced: prefix int64 [n, P], plen int32 [n] and contiguous tokens / lps [%d, k] expected' % N)
-    step_dev = step if torch.is_tensor(step) else None
-    call('tell_adaptive_logprob_forced', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-         ns[2], N, int(k), prefix, prefix.stride(0), prefix.shape[1], plen, prefix.shape[0], row_ids, int(beams),
-         0 if step_dev is not None else int(step), step_dev, int(pad), tokens, lps)
-    return picked
+    call('tell_adaptive_logprob_forced', *lg.abi(), int(k), prefix, prefix.stride(0), prefix.shape[1], plen, prefix.shape[0], row_ids,
+         int(beams), *_step_of(step), int(pad), tokens, lps)
 
 
-def logprob_stats(head, ld_head, c0, n_tails, tl, lds, ns, N, picked, stats):
+def logprob_stats(lg, picked, stats):
     """Per-token statistics: tell_adaptive_logprob_stats behind the pick (and the forced pick) over
     picked = (tokens int32 [N] or [N, k], ...) and the logits that pick was taken from.  stats: a decode.StatsSink - static
-    buffers [slots, N(, n)], .step the host step index or an int32 [1] device counter holding step - 1 (a captured decode
-    step's), .fin uint8 [N] or None.  -> picked."""
-    tokens = picked[0]
+    buffers [slots, N(, n)], .step as _step_of takes it, .fin uint8 [N] or None."""
+    N = lg.rows
+    tokens, fin = picked[0], stats.fin
     k = tokens.numel() // max(N, 1)
-    fin, step = stats.fin, stats.step
     if stats.rows != N or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.numel() != N * k or \
             (fin is not None and (fin.dtype != torch.uint8 or fin.numel() != N or not fin.is_contiguous())):
         raise ValueError('logprob_stats: a sink of %d rows, contiguous int32 tokens [%d, k] and finished uint8 [%d] expected'
                          % (N, N, N))
-    step_dev = step if torch.is_tensor(step) else None
-    call('tell_adaptive_logprob_stats', head, ld_head, c0, n_tails, tl[0], lds[0], ns[0], tl[1], lds[1], ns[1], tl[2], lds[2],
-         ns[2], N, tokens, int(k), fin, int(stats.n), int(stats.slots), 0 if step_dev is not None else int(step), step_dev,
+    call('tell_adaptive_logprob_stats', *lg.abi(), tokens, int(k), fin, int(stats.n), int(stats.slots), *_step_of(stats.step),
          int(stats.pad), stats.alt_tok, stats.alt_lp, stats.rank, stats.entropy, stats.chosen_lp)
+
+
+def logprob_pick(lg, topk=0, sample=None, ban=None, force=None, pen=None, mask=None, guide=None, stats=None, full=None):
+    """The tail of a generation head over its logits lg (a HeadLogits), for a combination that has passed check_pick: the
+    pick - one draw per row (sample, logprob_sample), the k best of every row (topk = k >= 1, logprob_topk) or the arg-max, which
+    also fills full (fp32 [N, vocab]) when given -, then with force one more launch that overrides the rows with prefix left
+    (logprob_forced), then with stats the launch that leaves the step's statistics in the sink (logprob_stats).
+    -> (token int32 [N], log-prob fp32 [N], full or None), or (tokens int32 [N, k], log-probs fp32 [N, k], None)."""
+    if sample is not None:
+        picked = logprob_sample(lg, sample, pen, mask)
+    elif topk:
+        picked = logprob_topk(lg, int(topk), ban, pen, mask, guide)
+    else:
+        token = torch.empty(lg.rows, dtype=torch.int32, device=lg.head.device)
+        token_lp = torch.empty(lg.rows, dtype=torch.float32, device=lg.head.device)
+        call('tell_adaptive_logprob_argmax', *lg.abi(), full, lg.vocab if full is not None else 0, token, token_lp)
+        picked = (token, token_lp, full)
+    if force is not None:
+        logprob_forced(lg, picked, force)
+    if stats is not None:
+        logprob_stats(lg, picked, stats)
     return picked
 
 
@@ -1959,23 +1993,11 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     """Generation head (softmax.py:193-222 + topk(1)): -> (token int32 [N], logprob fp32 [N], full or None);
     topk = k > 0: -> (tokens int32 [N,k], logprobs fp32 [N,k], None), best first (beam search);
     sample = (k, inv_temp, seed_dev, row_ids, step[, p[, rule]]): one top-k (with p: nucleus; with a rule: min-p / typical)
-    draw per row instead of the arg-max
-    (logprob_sample); force: one more launch behind the pick that overrides the rows with prefix left (logprob_forced);
-    pen (see _pen_args; with topk = k >= 1 or a top-k draw): the pick runs over the penalised scores;
-    mask (see _mask_args; with topk = k >= 1 or a top-k draw): masked tokens are never picked."""
-    if pen is not None and (want_full or (not topk and sample is None)):
-        raise ValueError('adaptive_log_probs: penalties go with topk = k >= 1 or a top-k draw')
-    if mask is not None and (want_full or (not topk and sample is None)):
-        raise ValueError('adaptive_log_probs: a vocabulary mask goes with topk = k >= 1 or a top-k draw')
-    if force is not None and want_full:
-        raise ValueError('adaptive_log_probs: forced tokens go with a pick, not with the full log-prob rows')
-    if guide is not None and (want_full or not topk or sample is not None or ban is not None or force is not None or
-                              pen is not None or mask is not None):
-        raise ValueError('adaptive_log_probs: guidance goes with topk = k >= 1 alone (no draw, ban list, forcing table, '
-                         'penalties or vocabulary mask)')
-    if stats is not None and (want_full or guide is not None):
-        raise ValueError('adaptive_log_probs: token statistics go with a pick, not with the full log-prob rows or guidance')
-    skw = {'stats': stats} if stats is not None else {}      # (a call without statistics is the call it was)
+    draw per row instead of the arg-max; ban, force, pen, mask, guide, stats: as logprob_pick takes them (check_pick says
+    what combines; DESIGN.md sections 17, 20, 22, 24 and 37)."""
+    if want_full:
+        sample = None                    # (the full rows come with the arg-max or the k best, never with a draw)
+    check_pick('adaptive_log_probs', want_full, topk, sample, ban, force, pen, mask, guide, stats)
     N, E = x2.shape
     dev = x2.device
     c0 = cutoffs[0]
@@ -1985,14 +2007,8 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
     if (not want_full and decode.ENABLED and N <= (decode.MAX_ROWS_WIDE if wide else decode.MAX_ROWS) and
             x2.dtype == torch.bfloat16 and
             E % 1024 == 0 and 1 <= n_tails <= 3 and all(tails[2 * i].shape[0] % 8 == 0 for i in range(n_tails))):
-        if guide is not None:    # (a call without guidance is the call it was: stand-ins for head_step keep working)
-            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, guide=guide)
-        if mask is not None:     # (a call without a mask is the call it was: stand-ins for head_step keep working)
-            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask,
-                                    **skw)
-        if pen is not None:      # (a call without penalties is the call it was: stand-ins for head_step keep working)
-            return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, **skw)
-        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, **skw)
+        return decode.head_step(x2, cutoffs, emb0, class_proj, tails, topk, sample, ban=ban, force=force, pen=pen, mask=mask,
+                                guide=guide, stats=stats)
     w_head = _cached(emb0, ('whead', class_proj._version, class_proj.data_ptr()), lambda: torch.cat(
         [weight(emb0), weight(class_proj)], dim=0).contiguous())
     def logits(a, w):                    # fp32 rows start on 16 bytes (see AdaptiveLossFn): vector stores in the epilogue
@@ -2005,27 +2021,9 @@ def adaptive_log_probs(x2, cutoffs, emb0, class_proj, tails, want_full=False, to
         h = gemm(x2, weight(proj))
         tl[i] = logits(h, weight(emb))
         ld[i], nn_[i] = tl[i].stride(0), tl[i].shape[1]
-    vocab = c0 + sum(nn_)
-
-    def forced(picked):
-        if force is not None:
-            logprob_forced(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, force)
-        return picked if stats is None else logprob_stats(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, picked, stats)
-    if sample is not None and not want_full:
-        return forced(logprob_sample(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, sample, pen=pen,
-                                     **({'mask': mask} if mask is not None else {})))
-    if topk:
-        return forced(logprob_topk(head, head.stride(0), c0, n_tails, tl, ld, nn_, N, int(topk), ban, pen=pen,
-                                   **({'mask': mask} if mask is not None else {}),
-                                   **({'guide': guide} if guide is not None else {})))
-    if ban is not None:
-        raise ValueError('adaptive_log_probs: a ban list goes with topk = k >= 1')
-    full = torch.empty(N, vocab, dtype=torch.float32, device=dev) if want_full else None
-    token = torch.empty(N, dtype=torch.int32, device=dev)
-    token_lp = torch.empty(N, dtype=torch.float32, device=dev)
-    call('tell_adaptive_logprob_argmax', head, head.stride(0), c0, n_tails, tl[0], ld[0], nn_[0], tl[1], ld[1],
-         nn_[1], tl[2], ld[2], nn_[2], N, full, vocab if want_full else 0, token, token_lp)
-    return forced((token, token_lp, full))
+    lg = HeadLogits(head, head.stride(0), c0, n_tails, tl, ld, nn_, N)
+    full = torch.empty(N, lg.vocab, dtype=torch.float32, device=dev) if want_full and not topk else None
+    return logprob_pick(lg, topk, sample, ban, force, pen, mask, guide, stats, full)
 
 
 LN2 = math.log(2.0)
