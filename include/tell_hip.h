@@ -345,6 +345,24 @@ int tell_reorder_rows(int n, void* const* bufs, const int* planes, const long* r
 int tell_sample_rank(const long* ids, long ld_ids, const float* lps, long ld_lps, const long* done_step,
                      const float* inv_norm, int B, int n, int steps, int pad, int eos, int rule, int* order, float* score,
                      uint8_t* dup, float* cons, int* len, tell_stream_t stream);
+/* Reward and advantage of the n sampled hypotheses of every image against its reference caption, in one launch (self-critical
+ * sequence training).  Hypothesis j of image b is row r = b * n + j of ids int64 [B * n, ld_ids >= steps
+ * + 1] (tell_sample_rank's convention), the references are ref int64 [B, ld_ref >= ref_steps + 1]; column 0 of both is <s>.
+ * 1 <= n <= 16, 1 <= steps, ref_steps <= 256, n-gram orders 1 .. max_order with max_order in 1 .. 4.
+ *   hyp(r)    = ids[r][1 ..] up to, and excluding, the first `eos` or `pad`, at most `steps` tokens; ref(b) alike over ref_steps;
+ *   match     = sum over k of |H_k n R_k|, H_k / R_k the MULTISETS of k-grams of hyp(r) / ref(b), counts clipped to the smaller;
+ *   th        = sum over k of max(|hyp| - k + 1, 0), tr the same sum for the reference;
+ *   reward[r] = float(match) / float(max(th, tr)), 0 when both are 0: the sentence-level GLEU of GNMT, the quotient of two
+ *               exact fp32 integers;
+ *   adv[r]    = reward[r] - baseline[b] with baseline fp32 [B] given (the reward of the greedy caption, from a call with
+ *               n = 1); with baseline == NULL and n > 1 leave-one-out: reward[r] - s / (n - 1), s the sum of the image's OTHER
+ *               rewards in ascending j in ONE fp32 accumulator (a sequential fp32 loop on the host gives the same bits); with
+ *               baseline == NULL and n == 1 the reward itself.
+ * out: reward, adv fp32 [B, n]; counts int32 [B * n, 3] = (match, th, tr), may be NULL.  No float atomics, no scratch in global
+ * memory; at most 17 x 256 tokens in LDS. */
+int tell_caption_reward(const long* ids, long ld_ids, const long* ref, long ld_ref, const float* baseline, int B, int n,
+                        int steps, int ref_steps, int pad, int eos, int max_order, float* reward, float* adv, int* counts,
+                        tell_stream_t stream);
 
 /* ---- LayerNorm: y = LN(res + dropout(x)), decoder_faces_objects.py:263-266,367-372 */
 int tell_layernorm_fwd(const void* x, long ld_x, const void* res, long ld_r, const float* gamma,
@@ -576,6 +594,17 @@ int tell_ce_fwd(const float* logits, long ld, int M, int V, const int* targets, 
 int tell_ce_bwd(const float* logits, long ld, int M, int V, const int* targets, const int* row_idx,
                 const int* m_dev, int ignore_index, const float* lse, const float* gscale_dev, void* dlogits,
                 long ld_d, int dtype, tell_stream_t stream);
+/* The two calls above with one weight per row: w fp32 indexed by UNCOMPACTED row, w_idx int32 or NULL - the weight of
+ * compacted row i is w[w_idx ? w_idx[i] : i] (the head passes NULL, a tail the row list tell_gather_rows compacted with).
+ * Forward: lse[i] is tell_ce_fwd's value bit for bit, loss[i] ONE fp32 multiply of the weight with the value tell_ce_fwd
+ * writes; ignored rows and rows >= *m_dev get 0.  Backward: row i is bit for bit what tell_ce_bwd writes with *gscale
+ * replaced by the fp32 product *gscale * weight, formed once per row; ignored rows and rows past *m_dev as in tell_ce_bwd. */
+int tell_ce_fwd_weighted(const float* logits, long ld, int M, int V, const int* targets, const int* row_idx,
+                         const int* m_dev, int ignore_index, const float* w, const int* w_idx, float* lse, float* loss,
+                         tell_stream_t stream);
+int tell_ce_bwd_weighted(const float* logits, long ld, int M, int V, const int* targets, const int* row_idx,
+                         const int* m_dev, int ignore_index, const float* w, const int* w_idx, const float* lse,
+                         const float* gscale_dev, void* dlogits, long ld_d, int dtype, tell_stream_t stream);
 /* get_log_prob + topk(1), softmax.py:193-222, transformer_faces_objects.py:443-464 */
 /* the k (<= 8) best (token, log-prob) pairs per row, best first - what a beam of k needs from each hypothesis;
  * `tokens`, `lps`: [rows, k] */

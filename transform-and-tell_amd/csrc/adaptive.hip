@@ -296,6 +296,81 @@ extern "C" int tell_ce_bwd(const float* logits, long ld, int M, int V, const int
   return tell_check_launch("ce_bwd");
 }
 
+// ---- per-row weights (tell_ce_fwd_weighted / tell_ce_bwd_weighted, include/tell_hip.h): the weight of compacted row i is
+// w[w_idx ? w_idx[i] : i].  The reductions are those of ce_fwd_kernel statement for statement, so lse keeps its bits and
+// loss is one fp32 multiply away; backward forms *gscale * weight once per row and then is ce_bwd_kernel's loop.
+__global__ __launch_bounds__(256) void ce_fwd_weighted_kernel(const float* __restrict__ logits, long ld, int M, int V,
+                                                              const int* __restrict__ targets,
+                                                              const int* __restrict__ row_idx,
+                                                              const int* __restrict__ m_dev, int ignore_index,
+                                                              const float* __restrict__ w,
+                                                              const int* __restrict__ w_idx,
+                                                              float* __restrict__ lse, float* __restrict__ loss) {
+  __shared__ float red[4];
+  int Me = M;
+  if (m_dev) { int md = *m_dev; Me = md < M ? md : M; }
+  const int i = blockIdx.x;
+  if (i >= Me) { if (threadIdx.x == 0) { loss[i] = 0.f; lse[i] = 0.f; } return; }
+  const float* row = logits + (long)i * ld;
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < V; j += 256) mx = fmaxf(mx, row[j]);
+  mx = block_max(mx, red);
+  float s = 0.f;
+  for (int j = threadIdx.x; j < V; j += 256) s += __expf(row[j] - mx);
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) {
+    const float l = mx + __logf(s);
+    const int tg = targets[row_idx ? row_idx[i] : i];
+    lse[i] = l;
+    if (tg == ignore_index) {
+      loss[i] = 0.f;
+    } else {
+      const float nll = l - row[tg];
+      loss[i] = w[w_idx ? w_idx[i] : i] * nll;
+    }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void ce_bwd_weighted_kernel(const float* __restrict__ logits, long ld, int M, int V,
+                                                              const int* __restrict__ targets,
+                                                              const int* __restrict__ row_idx,
+                                                              const int* __restrict__ m_dev, int ignore_index,
+                                                              const float* __restrict__ w,
+                                                              const int* __restrict__ w_idx,
+                                                              const float* __restrict__ lse,
+                                                              const float* __restrict__ gscale, T* __restrict__ dlogits,
+                                                              long ld_d) {
+  int Me = M;
+  if (m_dev) { int md = *m_dev; Me = md < M ? md : M; }
+  const int i = blockIdx.x;
+  if (i >= Me) return;
+  const int tg = targets[row_idx ? row_idx[i] : i];
+  const float g = tg == ignore_index ? 0.f : *gscale * w[w_idx ? w_idx[i] : i];
+  const float l = lse[i];
+  const float* row = logits + (long)i * ld;
+  T* d = dlogits + (long)i * ld_d;
+  for (int j = threadIdx.x; j < V; j += 256)
+    Elem<T>::st(d + j, (__expf(row[j] - l) - (j == tg ? 1.f : 0.f)) * g);
+}
+extern "C" int tell_ce_fwd_weighted(const float* logits, long ld, int M, int V, const int* targets, const int* row_idx,
+                                    const int* m_dev, int ignore_index, const float* w, const int* w_idx, float* lse,
+                                    float* loss, hipStream_t stream) {
+  TELL_REQUIRE(w, "ce_fwd_weighted: w fp32 [rows] expected (tell_ce_fwd is the call without weights)");
+  if (M <= 0) return TELL_OK;
+  hipLaunchKernelGGL(ce_fwd_weighted_kernel, dim3(M), dim3(256), 0, stream, logits, ld, M, V, targets, row_idx, m_dev, ignore_index, w, w_idx, lse, loss);
+  return tell_check_launch("ce_fwd_weighted");
+}
+extern "C" int tell_ce_bwd_weighted(const float* logits, long ld, int M, int V, const int* targets, const int* row_idx,
+                                    const int* m_dev, int ignore_index, const float* w, const int* w_idx,
+                                    const float* lse, const float* gscale, void* dlogits, long ld_d, int dtype,
+                                    hipStream_t stream) {
+  TELL_REQUIRE(w, "ce_bwd_weighted: w fp32 [rows] expected (tell_ce_bwd is the call without weights)");
+  if (M <= 0) return TELL_OK;
+  if (dtype == TELL_BF16) hipLaunchKernelGGL((ce_bwd_weighted_kernel<uint16_t>), dim3(M), dim3(256), 0, stream, logits, ld, M, V, targets, row_idx, m_dev, ignore_index, w, w_idx, lse, gscale, (uint16_t*)dlogits, ld_d);
+  else hipLaunchKernelGGL((ce_bwd_weighted_kernel<float>), dim3(M), dim3(256), 0, stream, logits, ld, M, V, targets, row_idx, m_dev, ignore_index, w, w_idx, lse, gscale, (float*)dlogits, ld_d);
+  return tell_check_launch("ce_bwd_weighted");
+}
+
 // deterministic sum of n (< = *m_dev if given) floats -> out[0] (+= if accumulate)
 __global__ __launch_bounds__(1024) void sum_kernel(const float* __restrict__ x, int n,
                                                    const int* __restrict__ m_dev, float* __restrict__ out,

@@ -2160,3 +2160,108 @@ extern "C" int tell_sample_rank(const long* ids, long ld_ids, const float* lps, 
                      eos, rule, order, score, dup, cons, len);
   return tell_check_launch("sample_rank");
 }
+
+// ------------------------------------------------------------------ sampled captions against the reference: reward, advantage
+// tell_caption_reward (include/tell_hip.h): one workgroup of four waves per image.  The reference and the n hypotheses are cut
+// at their first eos / pad while they are copied into LDS; wave w then owns hypotheses w, w + 4, ..: its lanes stripe the
+// k-gram positions of the hypothesis, and a position that is the FIRST occurrence of its k-gram inside the hypothesis adds
+// min(count in the hypothesis, count in the reference).  Integers up to the quotient; thread j < n finishes hypothesis j.
+constexpr int CR_WAVES = 4;
+__device__ __forceinline__ bool cr_same(const int* a, const int* b, int k) {
+  bool same = a[0] == b[0];
+  for (int q = 1; q < k; ++q) same = same && a[q] == b[q];
+  return same;
+}
+__global__ __launch_bounds__(64 * CR_WAVES) void caption_reward_kernel(const long* __restrict__ ids, long ld_ids,
+                                                                       const long* __restrict__ ref, long ld_ref,
+                                                                       const float* __restrict__ baseline, int n, int steps,
+                                                                       int ref_steps, int pad, int eos, int K,
+                                                                       float* __restrict__ reward, float* __restrict__ adv,
+                                                                       int* __restrict__ counts) {
+  __shared__ int tok[SR_N][SR_L];
+  __shared__ int rtok[SR_L];
+  __shared__ int len_s[SR_N + 1];                              // [SR_N]: the reference
+  __shared__ float rew_s[SR_N];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long r0 = (long)b * n;
+  // rows -> LDS, length = the first position holding eos or pad (row n stands for the reference)
+  for (int j = wave; j <= n; j += CR_WAVES) {
+    const bool is_ref = j == n;
+    const long* h = is_ref ? ref + (long)b * ld_ref + 1 : ids + (r0 + j) * ld_ids + 1;
+    int* dst = is_ref ? rtok : tok[j];
+    const int L = is_ref ? ref_steps : steps;
+    int first = L;
+    for (int p = lane; p < L; p += 64) {
+      const long t = h[p];
+      dst[p] = (int)t;
+      if ((t == eos || t == pad) && p < first) first = p;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(first, o); first = v < first ? v : first; }
+    if (lane == 0) len_s[is_ref ? SR_N : j] = first;
+  }
+  __syncthreads();
+  const int lr = len_s[SR_N];
+  int tr = 0;
+  for (int k = 1; k <= K; ++k) tr += lr - k + 1 > 0 ? lr - k + 1 : 0;
+  for (int j = wave; j < n; j += CR_WAVES) {
+    const int lh = len_s[j];
+    const int* hj = tok[j];
+    int match = 0, th = 0;
+    for (int k = 1; k <= K; ++k) {
+      const int nh = lh - k + 1, nr = lr - k + 1;                // k-gram positions (<= 0: none)
+      th += nh > 0 ? nh : 0;
+      for (int p = lane; p < nh; p += 64) {
+        int ch = 0, cr = 0;
+        bool first = true;
+        for (int q = 0; q < nh; ++q) {
+          const bool same = cr_same(hj + q, hj + p, k);
+          ch += same ? 1 : 0;
+          if (same && q < p) first = false;
+        }
+        if (!first) continue;
+        for (int q = 0; q < nr; ++q) cr += cr_same(rtok + q, hj + p, k) ? 1 : 0;
+        match += ch < cr ? ch : cr;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) match += __shfl_xor(match, o);
+    if (lane == 0) {
+      const int den = th > tr ? th : tr;
+      const float v = den > 0 ? (float)match / (float)den : 0.f;
+      rew_s[j] = v;
+      reward[r0 + j] = v;
+      if (counts) {
+        counts[(r0 + j) * 3 + 0] = match;
+        counts[(r0 + j) * 3 + 1] = th;
+        counts[(r0 + j) * 3 + 2] = tr;
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < n) {
+    const int j = threadIdx.x;
+    float base = 0.f;
+    if (baseline) {
+      base = baseline[b];
+    } else if (n > 1) {
+      float s = 0.f;
+      for (int e = 0; e < n; ++e)
+        if (e != j) s += rew_s[e];
+      base = s / (float)(n - 1);
+    }
+    adv[r0 + j] = rew_s[j] - base;
+  }
+}
+extern "C" int tell_caption_reward(const long* ids, long ld_ids, const long* ref, long ld_ref, const float* baseline, int B,
+                                   int n, int steps, int ref_steps, int pad, int eos, int max_order, float* reward,
+                                   float* adv, int* counts, hipStream_t stream) {
+  TELL_REQUIRE(B > 0 && n >= 1 && n <= SR_N && steps >= 1 && steps <= SR_L && ref_steps >= 1 && ref_steps <= SR_L,
+               "caption_reward: 1 <= n <= 16, 1 <= steps, ref_steps <= 256");
+  TELL_REQUIRE(max_order >= 1 && max_order <= 4, "caption_reward: n-gram orders 1 .. max_order, max_order in 1 .. 4");
+  TELL_REQUIRE(ids && ref && ld_ids >= steps + 1 && ld_ref >= ref_steps + 1, "caption_reward: ids [B n, > steps], ref [B, > ref_steps]");
+  TELL_REQUIRE(reward && adv, "caption_reward: reward and adv fp32 [B, n] expected");
+  hipLaunchKernelGGL(caption_reward_kernel, dim3(B), dim3(64 * CR_WAVES), 0, stream, ids, ld_ids, ref, ld_ref, baseline, n,
+                     steps, ref_steps, pad, eos, max_order, reward, adv, counts);
+  return tell_check_launch("caption_reward");
+}

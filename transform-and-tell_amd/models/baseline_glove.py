@@ -10,7 +10,7 @@ import torch
 
 from .. import ops
 from .transformer import (PENALTY_KEYS, CaptionModel, Model, check_beam_options, check_guidance, check_mask_keys,
-                          check_penalties, check_sampling, draw_seed, set_sampling)
+                          check_penalties, check_sampling, draw_seed, refuse_weighted_forward, set_sampling)
 
 
 def _refuse_mask_options(model, suppress_tokens=(), ground_names=False, banned=None, ground=None):
@@ -114,7 +114,8 @@ class BaselineGloveModel(Model):
                     'sections': None, 'sections_mask': None}
         return caption_ids, target_ids, contexts
 
-    def forward(self, image, caption, metadata=None, context_vectors=None):    # :71-162
+    def forward(self, image, caption, metadata=None, context_vectors=None, caption_weights=None, per_image=1):    # :71-162
+        refuse_weighted_forward(self, caption_weights, per_image)
         ops.hip.require_gpu()
         caption_ids, target_ids, contexts = self._forward(self._vectors(context_vectors, metadata), image, caption)
         ops.rt.wait_weight_update()
@@ -263,7 +264,8 @@ class TransformerGloveModel(CaptionModel):
     _vectors = staticmethod(BaselineGloveModel._vectors)
     _glove_forward = BaselineGloveModel._forward
 
-    def forward(self, image, caption, metadata=None, context_vectors=None):
+    def forward(self, image, caption, metadata=None, context_vectors=None, caption_weights=None, per_image=1):
+        refuse_weighted_forward(self, caption_weights, per_image)
         ops.hip.require_gpu()
         caption_ids, target_ids, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}

@@ -25,7 +25,7 @@ from torch.nn.init import constant_, xavier_normal_, xavier_uniform_
 from .. import ops
 from ..modules.linear import GehringLinear
 from ..modules.self_attention import SelfAttention
-from .transformer import CaptionModel, Model, draw_seed
+from .transformer import CaptionModel, Model, draw_seed, refuse_weighted_forward
 
 logger = logging.getLogger(__name__)
 
@@ -133,7 +133,8 @@ class PointerModelBase(CaptionModel):
 
     # ------------------------------------------------------------------ :103-178
     def forward(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                attn_idx=None, encoded=None):
+                attn_idx=None, encoded=None, caption_weights=None, per_image=1):
+        refuse_weighted_forward(self, caption_weights, per_image)
         self._require_masks(context, caption)
         copy_masks = caption[self.index + '_copy_masks'][:, 1:]
         enc = encoded if encoded is not None else self.encode(context, image)

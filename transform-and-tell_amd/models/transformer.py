@@ -315,6 +315,99 @@ def check_n_samples(n_samples=1, rank_by='score', rank_len_penalty=0.0):
     return n, rank_by, float(a)
 
 
+def check_per_image(per_image, caption_rows, images):
+    """forward(per_image=n): n a positive integer with caption_rows == images * n -> n; ValueError otherwise."""
+    n = per_image
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError('per_image must be a positive integer (got %r)' % (n,))
+    if caption_rows != images * n:
+        raise ValueError('per_image=%d: %d images need %d captions (got %d)' % (n, images, images * n, caption_rows))
+    return n
+
+
+def check_caption_weights(w, target_ids):
+    """forward(caption_weights=w): fp32 [rows] or [rows, T] on the device of the targets [rows, T] -> fp32 [rows, T]
+    contiguous and detached; ValueError otherwise."""
+    rows, T = target_ids.shape
+    if not torch.is_tensor(w) or w.dtype != torch.float32 or w.device != target_ids.device or \
+            tuple(w.shape) not in ((rows,), (rows, T)):
+        raise ValueError('caption_weights must be an fp32 tensor [%d] or [%d, %d] on the device of the captions (got %s)'
+                         % (rows, rows, T, (tuple(w.shape), w.dtype, str(w.device)) if torch.is_tensor(w)
+                            else type(w).__name__))
+    w = w.detach()
+    return (w.unsqueeze(1).expand(rows, T) if w.dim() == 1 else w).contiguous()
+
+
+def refuse_weighted_forward(model, caption_weights=None, per_image=1):
+    """The models outside the weighted / per-image training pass (copy, GloVe, LSTM) say so by name."""
+    if caption_weights is not None or per_image != 1:
+        raise ValueError('%s does not take caption_weights / per_image: the weighted training pass (self-critical '
+                         'training) covers the transformer_faces_objects family only' % type(model).__name__)
+
+
+def caption_reward_definition(ids, ref, n, steps, ref_steps, pad, eos, max_order=4, baseline=None):
+    """The contract of tell_caption_reward (include/tell_hip.h) in numpy on the host - what the kernel is tested against and
+    what scores hypotheses that live on the CPU.  ids [B * n, > steps], ref [B, > ref_steps], baseline fp32 [B] or None.
+    -> dict: reward, adv fp32 [B, n]; counts int32 [B * n, 3] = (match, th, tr)."""
+    from collections import Counter
+    import numpy as np
+    ids, ref = np.asarray(ids), np.asarray(ref)
+    n, steps, ref_steps, K = int(n), int(steps), int(ref_steps), int(max_order)
+    R = ids.shape[0]
+    B = R // n
+
+    def cut(row, L):
+        out = []
+        for t in row[1:1 + L]:
+            if int(t) == int(eos) or int(t) == int(pad):
+                break
+            out.append(int(t))
+        return tuple(out)
+
+    def grams(t):
+        return [Counter(zip(*[t[i:] for i in range(k)])) for k in range(1, K + 1)]
+
+    def total(t):
+        return sum(max(len(t) - k + 1, 0) for k in range(1, K + 1))
+    reward, counts = np.zeros(R, dtype=np.float32), np.zeros((R, 3), dtype=np.int32)
+    for b in range(B):
+        rt_ = cut(ref[b], ref_steps)
+        rg, tr = grams(rt_), total(rt_)
+        for j in range(n):
+            h = cut(ids[b * n + j], steps)
+            match = sum(sum((a & c).values()) for a, c in zip(grams(h), rg))
+            th = total(h)
+            den = max(th, tr)
+            counts[b * n + j] = (match, th, tr)
+            reward[b * n + j] = np.float32(match) / np.float32(den) if den else np.float32(0.0)
+    reward = reward.reshape(B, n)
+    return {'reward': reward, 'adv': advantage_definition(reward, baseline), 'counts': counts}
+
+
+def advantage_definition(reward, baseline=None):
+    """reward fp32 [B, n] -> adv fp32 [B, n] by tell_caption_reward's rule: minus baseline[b] when given; else, for n > 1,
+    minus the leave-one-out mean s / (n - 1), s summed over the OTHER rewards in ascending j in one fp32 accumulator; else
+    the reward itself."""
+    import numpy as np
+    reward = np.asarray(reward, dtype=np.float32)
+    B, n = reward.shape
+    adv = np.zeros((B, n), dtype=np.float32)
+    for b in range(B):
+        for j in range(n):
+            if baseline is not None:
+                base = np.float32(np.asarray(baseline, dtype=np.float32).reshape(-1)[b])
+            elif n > 1:
+                s = np.float32(0.0)
+                for e in range(n):
+                    if e != j:
+                        s = np.float32(s + reward[b, e])
+                base = np.float32(s / np.float32(n - 1))
+            else:
+                base = np.float32(0.0)
+            adv[b, j] = np.float32(reward[b, j] - base)
+    return adv
+
+
 def sample_rank_definition(ids, lps, done_step, n, steps, eos, rule, inv_norm=None):
     """The contract of tell_sample_rank (include/tell_hip.h) in numpy on the host - what the kernel is tested against and what
     ranks hypotheses that live on the CPU.  ids [B * n, > steps], lps [B * n, >= steps], done_step [B * n]; rule 'draw' /
@@ -1025,9 +1118,14 @@ class CaptionModel(Model):
         return cache[key]
 
     # ---- :311-397 -----------------------------------------------------------------
-    def _forward(self, context, image, caption, face_embeds=None, obj_embeds=None, encoded=None):
+    def _forward(self, context, image, caption, face_embeds=None, obj_embeds=None, encoded=None, per_image=1):
+        """per_image = n: `caption` holds n captions for each of the B images (caption b * n + j belongs to image b); every
+        context and its mask is repeated n times along the batch axis AFTER the encoders and the layer mix - one encode for
+        the n captions, and autograd sums the mix's gradient over them."""
         dtype = ops.rt.compute_dtype()
         cap = caption[self.index]
+        plain = type(per_image) is int and per_image == 1                  # (the default reads nothing more of the batch)
+        n_per = 1 if plain else check_per_image(per_image, cap.shape[0], image.shape[0])
         target_ids = cap[:, 1:].contiguous()                               # :321-328
         caption_ids = cap[:, :-1].contiguous()
         caption[self.index] = caption_ids                                  # :329
@@ -1041,6 +1139,11 @@ class CaptionModel(Model):
             x_article = ops.mix_layers(stack, self.bert_weight)            # :355-364
         else:
             x_article = stack[-1]
+        if n_per > 1:
+            B = B * n_per
+            x_image, x_article, article_mask = (t.repeat_interleave(n_per, dim=0) for t in (x_image, x_article, article_mask))
+            face_embeds, obj_embeds = (None if t is None else t.repeat_interleave(n_per, dim=0)
+                                       for t in (face_embeds, obj_embeds))
         contexts = {
             'image': x_image.transpose(0, 1),
             'image_mask': self._no_mask(B, P, image.device),                  # :371
@@ -1065,9 +1168,18 @@ class CaptionModel(Model):
 
     # ---- :67-140 ------------------------------------------------------------------
     def forward(self, context, image, caption, face_embeds=None, obj_embeds=None, metadata=None, names=None,
-                attn_idx=None, encoded=None):
-        """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`."""
-        output_dict, caption_ids, contexts = self._forward_loss(context, image, caption, face_embeds, obj_embeds, encoded)
+                attn_idx=None, encoded=None, caption_weights=None, per_image=1):
+        """encoded: optional EncodedBatch of THIS batch produced earlier by `encode(..., ahead=True)`.
+        caption_weights: fp32 [rows] or [rows, T] on the captions' device, T = caption length - 1 - the
+        loss becomes sum_r sum_t w_rt * -log p(y_rt) over the number of non-pad targets (still bits per token) and every
+        token's gradient carries its weight; not differentiated.  A per-row advantage (Trainer.train_self_critical), a mask
+        that keeps a forced prefix out of the loss, a weight on entity tokens.  None: exactly the call of before.
+        per_image = n: the batch holds B images and B * n captions, caption b * n + j for image b: one pass of the encoders
+        and of the layer mix, their outputs repeated n times for the decoder.  1: exactly the call of before."""
+        if not hasattr(getattr(self, 'decoder', None), 'project_contexts'):          # an LSTM decoder behind this class
+            refuse_weighted_forward(self, caption_weights, per_image)
+        output_dict, caption_ids, contexts = self._forward_loss(context, image, caption, face_embeds, obj_embeds, encoded,
+                                                                caption_weights, per_image)
         if not self.training and self.evaluate_mode:                       # :92-116
             # (eval_attention: commands/evaluate.py's opt-in - the captions come with their attention maps)
             vm = self._vocab_mask(context, attention=bool(getattr(self, 'eval_attention', False)))
@@ -1081,11 +1193,17 @@ class CaptionModel(Model):
         self.n_batches += 1
         return output_dict
 
-    def _forward_loss(self, context, image, caption, face_embeds=None, obj_embeds=None, encoded=None):
+    def _forward_loss(self, context, image, caption, face_embeds=None, obj_embeds=None, encoded=None, caption_weights=None,
+                      per_image=1):
         """:67-88 - encoders, teacher-forced decoder pass, loss in bits per token -> (output_dict, caption_ids, contexts)."""
-        caption_ids, target_ids, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
+        caption_ids, target_ids, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded,
+                                                          per_image)
         decoder_out = self.decoder(caption, contexts)
-        loss_sum, sample_size = self.criterion(self.decoder.adaptive_softmax, decoder_out, target_ids)
+        if caption_weights is None:
+            loss_sum, sample_size = self.criterion(self.decoder.adaptive_softmax, decoder_out, target_ids)
+        else:
+            loss_sum, sample_size = self.criterion(self.decoder.adaptive_softmax, decoder_out, target_ids,
+                                                   row_weight=check_caption_weights(caption_weights, target_ids))
         loss = ops.loss_bits(loss_sum, sample_size)                        # :85-88, bits per token
         return {'loss': loss, 'sample_size': sample_size.reshape(())}, caption_ids, contexts
 

@@ -18,6 +18,7 @@ class AdaptiveLoss(Criterion):
         super().__init__()
         self.padding_idx = padding_idx
 
-    def forward(self, adaptive_softmax, net_output, decoder_target, reduction='sum'):
+    def forward(self, adaptive_softmax, net_output, decoder_target, reduction='sum', row_weight=None):
+        """row_weight: fp32 [B, T] like decoder_target, one weight per target token, or None (ops.adaptive_loss)."""
         assert reduction == 'sum'
-        return adaptive_softmax.loss(net_output[0], decoder_target, self.padding_idx)
+        return adaptive_softmax.loss(net_output[0], decoder_target, self.padding_idx, row_weight=row_weight)

@@ -58,14 +58,19 @@ class AdaptiveSoftmax(nn.Module):
             out += [t[0].weight, t[2].weight]
         return out
 
-    def loss(self, x, target, padding_idx):
-        """-> (loss_sum in nats [1], sample_size [1] int32), both on the device."""
+    def loss(self, x, target, padding_idx, row_weight=None):
+        """-> (loss_sum in nats [1], sample_size [1] int32), both on the device.
+        row_weight: fp32 in the layout of `target` or None (ops.adaptive_loss)."""
+        if row_weight is not None and (not torch.is_tensor(row_weight) or row_weight.shape != target.shape):
+            raise ValueError('AdaptiveSoftmax.loss: row_weight must have the shape %s of target' % (tuple(target.shape),))
         if x.dim() == 3 and not x.is_contiguous() and x.transpose(0, 1).is_contiguous():
             # the decoder hands its T x B x C buffer over as a [B,T,C] view: the summed loss does not care about the row
             # order, so the (tiny) target is transposed instead of the activations (and of their gradient)
             x, target = x.transpose(0, 1), target.t().contiguous()
+            if row_weight is not None:
+                row_weight = row_weight.t().contiguous()
         return ops.adaptive_loss(x, target, self.cutoff, padding_idx, self.head.word_proj.weight,
-                                 self.head.class_proj.weight, self._tails())
+                                 self.head.class_proj.weight, self._tails(), row_weight=row_weight)
 
     def get_log_prob(self, X, target=None):
         assert target is None

@@ -1621,8 +1621,10 @@ class AdaptiveLossFn(Function):
     tail rows are compacted on the device, tail GEMMs run with a device row count."""
 
     @staticmethod
-    def forward(ctx, x, target, cutoffs, pad_idx, emb0, class_proj, *tails):
+    def forward(ctx, x, target, cutoffs, pad_idx, row_weight, emb0, class_proj, *tails):
         # tails = proj_0, emb_1, proj_1, emb_2, ...   (tail i: logits = emb_{i+1} (proj_i x))
+        # row_weight: None, or fp32 [N] in the row order of `target` - every row's loss and gradient times its weight
+        # (tell_ce_fwd_weighted / tell_ce_bwd_weighted; a tail's compacted row i reads the weight of row part['rows'][band][i])
         N, E = x.shape[0] * x.shape[1], x.shape[2]
         dtype = x.dtype
         dev = x.device
@@ -1646,8 +1648,12 @@ class AdaptiveLossFn(Function):
         gemm(x2, w_head, out=head_logits)
         lse_h = torch.empty(N, dtype=torch.float32, device=dev)
         loss_rows = torch.empty(N, dtype=torch.float32, device=dev)
-        call('tell_ce_fwd', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
-             int(pad_idx), lse_h, loss_rows)
+        if row_weight is None:
+            call('tell_ce_fwd', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
+                 int(pad_idx), lse_h, loss_rows)
+        else:
+            call('tell_ce_fwd_weighted', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
+                 int(pad_idx), row_weight, None, lse_h, loss_rows)
         zs = zeros_group([((1,), torch.float32)] +
                          [spec for i in range(n_tails) for spec in (((N, E), dtype), ((N, tails[2 * i].shape[0]), dtype))],
                          dev)
@@ -1668,12 +1674,17 @@ class AdaptiveLossFn(Function):
             lse_t = torch.empty(N, dtype=torch.float32, device=dev)
             lrow = torch.empty(N, dtype=torch.float32, device=dev)
             # target of compacted row j is local[band][j]; quirk: ignore_index also applies here
-            call('tell_ce_fwd', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
-                 lse_t, lrow)
+            if row_weight is None:
+                call('tell_ce_fwd', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
+                     lse_t, lrow)
+            else:
+                call('tell_ce_fwd_weighted', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
+                     row_weight, part['rows'][band], lse_t, lrow)
             call('tell_sum_f32', lrow, N, cnt, total, 1)
             saved_tails.append((xg, h, logits, lse_t))
         ctx.saved = (x2, w_head, head_logits, lse_h, part, saved_tails)
         ctx.params = (emb0, class_proj, tails, cutoffs, pad_idx)
+        ctx.row_weight = row_weight
         ctx.xshape = x.shape
         ctx.mark_non_differentiable(part['n_valid'])
         ctx.set_materialize_grads(False)
@@ -1683,8 +1694,9 @@ class AdaptiveLossFn(Function):
     def backward(ctx, gtotal, _gn):
         x2, w_head, head_logits, lse_h, part, saved_tails = ctx.saved
         emb0, class_proj, tails, cutoffs, pad_idx = ctx.params
+        row_weight = ctx.row_weight
         if gtotal is None:
-            return (None,) * (6 + len(tails))
+            return (None,) * (7 + len(tails))
         N, E = x2.shape
         dtype, dev = x2.dtype, x2.device
         c0 = cutoffs[0]
@@ -1697,8 +1709,12 @@ class AdaptiveLossFn(Function):
                           (((N, _round_up(tails[2 * i + 1].shape[0], _vec(dtype))), dtype), ((N, tails[2 * i].shape[0]), dtype))],
                          dev)
         dl = zs[0]
-        call('tell_ce_bwd', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
-             int(pad_idx), lse_h, gscale, dl, dl.stride(0), hip.dt(dtype))
+        if row_weight is None:
+            call('tell_ce_bwd', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
+                 int(pad_idx), lse_h, gscale, dl, dl.stride(0), hip.dt(dtype))
+        else:
+            call('tell_ce_bwd_weighted', head_logits, head_logits.stride(0), N, n_head, part['head_target'], None, None,
+                 int(pad_idx), row_weight, None, lse_h, gscale, dl, dl.stride(0), hip.dt(dtype))
         dx = gemm_nn(dl, w_head)                                  # [N, E]; dl's padding columns are zero
         if not dx.is_contiguous():
             dx = dx.contiguous()
@@ -1714,8 +1730,12 @@ class AdaptiveLossFn(Function):
             xg, h, logits, lse_t = saved_tails[i]
             V = emb.shape[0]
             dlt = zs[1 + 2 * i]
-            call('tell_ce_bwd', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
-                 lse_t, gscale, dlt, dlt.stride(0), hip.dt(dtype))
+            if row_weight is None:
+                call('tell_ce_bwd', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
+                     lse_t, gscale, dlt, dlt.stride(0), hip.dt(dtype))
+            else:
+                call('tell_ce_bwd_weighted', logits, logits.stride(0), N, V, part['local'][band], None, cnt, int(pad_idx),
+                     row_weight, part['rows'][band], lse_t, gscale, dlt, dlt.stride(0), hip.dt(dtype))
             dh = zs[2 + 2 * i]
             gemm_nn(dlt, weight(emb), b_t=lambda emb=emb: weight_t(emb), out=dh, m_dev=cnt, zero_rows=True)
             if emb.requires_grad:                                  # rows >= count of dlt are zero: not read (k_dev)
@@ -1727,7 +1747,7 @@ class AdaptiveLossFn(Function):
                 dxg = dxg.contiguous()
             call('tell_scatter_add_rows', dxg, dxg.stride(0), part['rows'][band], cnt, N, dx, dx.stride(0), E,
                  hip.dt(dtype))
-        return (dx.view(ctx.xshape),) + (None,) * (5 + len(tails))
+        return (dx.view(ctx.xshape),) + (None,) * (6 + len(tails))
 
 
 class LossBitsFn(Function):
@@ -1754,9 +1774,19 @@ def loss_bits(total, n_valid):
     return (total / math.log(2) / n_valid.to(torch.float32)).reshape(())
 
 
-def adaptive_loss(x, target, cutoffs, pad_idx, emb0, class_proj, tails):
-    """-> (loss_sum_nats [1] fp32 device tensor, n_valid [1] int32 device tensor)."""
-    return AdaptiveLossFn.apply(x, target, tuple(cutoffs), pad_idx, emb0, class_proj, *tails)
+def adaptive_loss(x, target, cutoffs, pad_idx, emb0, class_proj, tails, row_weight=None):
+    """-> (loss_sum_nats [1] fp32 device tensor, n_valid [1] int32 device tensor).
+    row_weight: fp32 device tensor in the layout of `target`, one weight per target token - the sum becomes
+    sum_r w_r * NLL_r and every row's gradient is scaled by its weight.  Not differentiated; n_valid
+    stays the number of non-pad targets whatever the weights.  None: exactly the launches of before."""
+    if row_weight is not None:
+        if not torch.is_tensor(row_weight) or row_weight.dtype != torch.float32 or row_weight.shape != target.shape or \
+                row_weight.device != target.device:
+            raise ValueError('adaptive_loss: row_weight must be an fp32 tensor of the shape %s of target on its device '
+                             '(got %s)' % (tuple(target.shape), (tuple(row_weight.shape), row_weight.dtype)
+                                           if torch.is_tensor(row_weight) else type(row_weight).__name__))
+        row_weight = row_weight.detach().reshape(-1).contiguous()
+    return AdaptiveLossFn.apply(x, target, tuple(cutoffs), pad_idx, row_weight, emb0, class_proj, *tails)
 
 
 def _pen_args(pen, N):
@@ -2348,3 +2378,33 @@ def sample_rank(ids, lps, done_step, B, n, steps, pad, eos, rule, inv_norm=None,
     call('tell_sample_rank', ids, ids.stride(0), lps, lps.stride(0), done_step, inv_norm, int(B), int(n), int(steps), int(pad),
          int(eos), rule, order, score, dup, cons, length)
     return order, score, dup, cons, length
+
+
+def caption_reward(ids, ref, B, n, steps, ref_steps, pad, eos, max_order=4, baseline=None, want_counts=False):
+    """Reward and advantage of n sampled captions per image against the reference caption in one launch (include/tell_hip.h
+    tell_caption_reward): ids int64 [B * n, > steps] - hypothesis j of image b in row b * n + j -, ref int64
+    [B, > ref_steps], column 0 of both <s>; baseline fp32 [B] (the greedy caption's reward) or None (leave-one-out for n > 1,
+    no baseline for n = 1).  -> (reward fp32 [B, n], adv fp32 [B, n], counts int32 [B * n, 3] = (match, th, tr) or None)."""
+    for name, v, lo, hi in (('n', n, 1, 16), ('steps', steps, 1, 256), ('ref_steps', ref_steps, 1, 256),
+                            ('max_order', max_order, 1, 4)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError('caption_reward: %s must be an integer in %d..%d (got %r)' % (name, lo, hi, v))
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise ValueError('caption_reward: B must be a positive integer (got %r)' % (B,))
+    R = B * n
+    if not torch.is_tensor(ids) or ids.dtype != torch.long or ids.dim() != 2 or ids.shape[0] != R or ids.stride(1) != 1 or \
+            ids.shape[1] < steps + 1:
+        raise ValueError('caption_reward: ids int64 [%d, > %d] expected' % (R, steps))
+    if not torch.is_tensor(ref) or ref.dtype != torch.long or ref.dim() != 2 or ref.shape[0] != B or ref.stride(1) != 1 or \
+            ref.shape[1] < ref_steps + 1 or ref.device != ids.device:
+        raise ValueError('caption_reward: ref int64 [%d, > %d] on the device of ids expected' % (B, ref_steps))
+    if baseline is not None and (not torch.is_tensor(baseline) or baseline.dtype != torch.float32 or baseline.numel() != B or
+                                 not baseline.is_contiguous() or baseline.device != ids.device):
+        raise ValueError('caption_reward: baseline fp32 [%d] on the device of ids expected' % B)
+    dev = ids.device
+    reward = torch.empty(B, n, dtype=torch.float32, device=dev)
+    adv = torch.empty(B, n, dtype=torch.float32, device=dev)
+    counts = torch.empty(R, 3, dtype=torch.int32, device=dev) if want_counts else None
+    call('tell_caption_reward', ids, ids.stride(0), ref, ref.stride(0), baseline, B, n, steps, ref_steps, int(pad), int(eos),
+         max_order, reward, adv, counts)
+    return reward, adv, counts

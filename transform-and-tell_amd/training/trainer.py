@@ -396,7 +396,10 @@ class Trainer:
 
     def _eager_step(self, batch, enc=None):
         extra = {'encoded': enc} if enc is not None else {}
-        out = self.model(**batch, **extra)                               # :220 / :194
+        return self._finish_step(self.model(**batch, **extra))           # :220 / :194
+
+    def _finish_step(self, out):
+        """Everything of the eager step behind the model's forward pass: NaN flag, backward, exchange and update."""
         loss = out['loss']
         if loss is None:             # the pointer models' batches without a copy target: no backward, no update
             return None
@@ -429,6 +432,150 @@ class Trainer:
         else:
             self._update(n_local)
         return loss.detach()
+
+    # ---- self-critical sequence training --------------------------------------------------
+    SCST_BASELINES = ('leave_one_out', 'greedy')
+
+    @staticmethod
+    def check_self_critical(n_samples=4, baseline='leave_one_out', max_order=4, reward=None):
+        """The arguments of train_self_critical / the trainer key `self_critical` -> (n, baseline, max_order)."""
+        n, k = n_samples, max_order
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 16:
+            raise ValueError('self_critical: n_samples must be an integer in 1..16 (got %r)' % (n,))
+        if baseline not in Trainer.SCST_BASELINES:
+            raise ValueError("self_critical: baseline must be 'leave_one_out' or 'greedy' (got %r)" % (baseline,))
+        if baseline == 'leave_one_out' and n == 1:
+            raise ValueError("self_critical: baseline='leave_one_out' needs n_samples >= 2 (one sample has no others)")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 4:
+            raise ValueError('self_critical: max_order must be an integer in 1..4 (got %r)' % (k,))
+        if reward is not None and not callable(reward):
+            raise ValueError('self_critical: reward must be callable(gen_ids_samples, batch) -> fp32 [B, n] or None')
+        return n, baseline, k
+
+    def train_self_critical(self, batch, n_samples=4, baseline='leave_one_out', max_order=4, reward=None):
+        """One self-critical step: n_samples captions per image are drawn from ONE pass of the encoders
+        (generate(n_samples=n, rank_by='draw'), eval mode, no_grad), scored against batch['caption'] on the device
+        (tell_caption_reward: sentence-level GLEU over the n-gram orders 1..max_order) and reinforced by the weighted
+        training pass forward(per_image=n, caption_weights=adv) through the tail of the plain step (_flag_loss, _backward,
+        _update).  baseline: 'leave_one_out' (the mean reward of the image's other samples) or 'greedy' (the reward of one
+        more, arg-max, generate).  reward = callable(gen_ids_samples [B, n, L], batch) -> fp32 [B, n] replaces the kernel's
+        reward; the advantage then follows the same definition in torch.  The step is never captured and runs under the
+        zero + accumulate gradient convention, whichever the plain step uses; it leaves that choice as it found it.
+        -> {'loss' (sum_r adv_r sum_t -log p(y_rt) over the sampled tokens, bits per token), 'reward_mean',
+        'baseline_mean', 'reward' [B, n], 'adv' [B, n], 'baseline' ([B, 1] greedy: what the kernel subtracted; [B, n]
+        leave-one-out: reward - adv), 'gen_ids_samples' [B, n, L] (the captions the rewards belong to)}, all device tensors."""
+        n, baseline, max_order = self.check_self_critical(n_samples, baseline, max_order, reward)
+        sampling = getattr(self.model, '_sampling', None)
+        if not callable(sampling) or sampling() is None:
+            raise ValueError('train_self_critical needs a sampling model (sampling_topk > 1, sampling_topp, sampling_minp '
+                             'or sampling_typical): %s decodes by arg-max' % type(self.model).__name__)
+        if self.optimizer.ema_swapped:
+            raise RuntimeError('train_self_critical inside Trainer.ema_weights(): the masters sit in the EMA buffer')
+        store, self._store = self._store, 'off'      # no store mode and no observing pass here (_grad_store_begin, _backward)
+        try:
+            return self._self_critical_body(batch, n, baseline, max_order, reward)
+        finally:
+            self._store = store
+            ops.grad_store_mode(False)
+
+    @contextlib.contextmanager
+    def _arg_max_decode(self):
+        """Inside, the sampling model decodes by arg-max (the greedy baseline caption)."""
+        m = self.model
+        keys = ('sampling_topk', 'sampling_topp', 'sampling_minp', 'sampling_typical')
+        saved = {k: getattr(m, k, None) for k in keys}
+        m.sampling_topk, m.sampling_topp, m.sampling_minp, m.sampling_typical = 1, None, None, None
+        try:
+            yield
+        finally:
+            for k, v in saved.items():
+                setattr(m, k, v)
+
+    def _self_critical_body(self, batch, n, baseline, max_order, reward_fn):
+        model = self.model
+        idx = model.index
+        pad, eos = int(model.padding_idx), 2
+        if not model.training:
+            model.train()                            # the encoders run as they do for the plain step
+        batch = self._bucketed(batch)
+        self._grad_store_begin(batch)
+        fields = {k: batch[k] for k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds') if k in batch}
+
+        def fresh():                                 # (_forward rewrites caption[index]: never the caller's dict)
+            return {k: (dict(v) if isinstance(v, dict) else v) for k, v in fields.items()}
+        enc = self._encoded_for(batch)
+        if enc is None:
+            with hip.bound_stream():
+                enc = model.encode(batch['context'], batch['image'])
+        ref = batch['caption'][idx][:, :257]         # (the reward reads at most 256 reference tokens behind <s>)
+        B = ref.shape[0]
+        model.eval()
+        try:
+            with torch.no_grad():
+                gen = model.generate(**fresh(), encoded=enc, n_samples=n, rank_by='draw')
+                samples = gen['gen_ids_samples'] if n > 1 else gen['gen_ids'].unsqueeze(1)       # [B, n, L]
+                greedy = None
+                if baseline == 'greedy':
+                    with self._arg_max_decode():
+                        greedy = model.generate(**fresh(), encoded=enc)['gen_ids']
+        finally:
+            model.train()
+        with torch.no_grad(), hip.bound_stream():
+            reward, adv, base = self._caption_rewards(samples, greedy, ref, batch, pad, eos, max_order, reward_fn)
+            # the training captions: <s>, the sample up to and with its </s>; what lies behind a drawn pad id is not a
+            # target (the reward stops there too)
+            cap = samples.reshape(B * n, -1).clone()
+            lead = (cap[:, 1:] != pad).long().cumprod(1).bool()
+            cap[:, 1:] = torch.where(lead, cap[:, 1:], torch.full_like(cap[:, 1:], pad))
+        train = fresh()
+        train['caption'] = {idx: cap}
+        with hip.bound_stream():
+            if enc.stale():                          # a generate that encoded on its own has reused the buffers
+                enc = model.encode(batch['context'], batch['image'])
+            out = model(**train, encoded=enc, per_image=n, caption_weights=adv.reshape(B * n))
+            loss = self._finish_step(out)
+        if loss is None:                             # (nan_check=True: the host-synchronous skip of the plain step)
+            return None
+        self.batch_num_total += 1
+        return {'loss': loss, 'reward_mean': reward.mean(), 'baseline_mean': base.mean(), 'reward': reward,
+                'adv': adv, 'baseline': base, 'gen_ids_samples': samples}
+
+    def _caption_rewards(self, samples, greedy, ref, batch, pad, eos, max_order, reward_fn):
+        """-> (reward [B, n], adv [B, n], baseline [B, 1] (greedy) or [B, n]) of samples int64 [B, n, L] against ref int64 [B, T]."""
+        from ..models.transformer import caption_reward_definition
+        B, n, L = samples.shape
+        ids = samples.reshape(B * n, L).contiguous()
+
+        def kernel(h, per, baseline=None):           # the launch on the device, its numpy definition on the CPU
+            if h.is_cuda:
+                return ops.caption_reward(h, ref, B, per, h.shape[1] - 1, ref.shape[1] - 1, pad, eos, max_order,
+                                          baseline=baseline)[:2]
+            d = caption_reward_definition(h.numpy(), ref.numpy(), per, h.shape[1] - 1, ref.shape[1] - 1, pad, eos, max_order,
+                                          None if baseline is None else baseline.numpy())
+            return torch.from_numpy(d['reward']), torch.from_numpy(d['adv'])
+        base = None
+        if greedy is not None:
+            base = (reward_fn(greedy.unsqueeze(1), batch).reshape(B) if reward_fn is not None
+                    else kernel(greedy.contiguous(), 1)[0].reshape(B)).float().contiguous()
+        if reward_fn is None:
+            reward, adv = kernel(ids, n, base)
+        else:
+            reward = reward_fn(samples, batch)
+            if not torch.is_tensor(reward) or reward.dtype != torch.float32 or tuple(reward.shape) != (B, n):
+                raise ValueError('self_critical: reward(gen_ids_samples, batch) must return fp32 [%d, %d]' % (B, n))
+            if base is not None:
+                adv = reward - base.unsqueeze(1)
+            elif n > 1:
+                # leave-one-out by tell_caption_reward's definition: the others in ascending j, one fp32 accumulator
+                s = torch.zeros_like(reward)
+                for e in range(n):
+                    others = torch.ones(n, dtype=torch.bool, device=reward.device)
+                    others[e] = False
+                    s = torch.where(others, s + reward[:, e:e + 1], s)
+                adv = reward - s / float(n - 1)
+            else:
+                adv = reward.clone()
+        return reward, adv, (reward - adv if base is None else base.unsqueeze(1))
 
     def _update(self, n_local=None):
         """Gradient exchange (data parallel) + BertAdam + gradient zeroing.  n_local: this rank's token count when
@@ -514,12 +661,25 @@ class CallbackApexTrainer(Trainer):
     `apex_opt_level` / `keep_batchnorm_fp32` are accepted and ignored (bf16 + fp32 masters)."""
 
     def __init__(self, model, optimizer=None, no_grad=(r'^resnet', r'^roberta'), apex_opt_level=None,
-                 keep_batchnorm_fp32=None, num_epochs=1, shuffle=True, cuda_device=0, callbacks=None, **kw):
+                 keep_batchnorm_fp32=None, num_epochs=1, shuffle=True, cuda_device=0, callbacks=None, self_critical=None,
+                 **kw):
+        """self_critical: {n_samples, baseline, max_order} - `train` then runs Trainer.train_self_critical on every batch
+        (the second training stage); absent: the plain step."""
         super().__init__(model, optimizer, no_grad, device='cuda' if cuda_device is not None else 'cpu')
         self.num_epochs = num_epochs
+        self.self_critical = None
+        if self_critical is not None:
+            extra = set(self_critical) - {'n_samples', 'baseline', 'max_order'}
+            if extra:
+                raise ValueError('self_critical: unknown keys %s (n_samples, baseline, max_order)' % sorted(extra))
+            n, base, k = self.check_self_critical(**self_critical)
+            self.self_critical = {'n_samples': n, 'baseline': base, 'max_order': k}
 
     def train(self, batches):
         losses = []
         for batch in batches:
-            losses.append(self.train_one_batch(batch))
+            if self.self_critical is not None:
+                losses.append(self.train_self_critical(batch, **self.self_critical)['loss'])
+            else:
+                losses.append(self.train_one_batch(batch))
         return losses
