@@ -251,8 +251,8 @@ def test_generate_with_maps_runs_without_autograd():
     m.decoder, m.sampling_topk, m.sampling_temp, m.sampling_topp, m.index = Conv(), 1, 1.0, None, 'roberta'
     seen = {}
 
-    def steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False):
-        seen['grad'], seen['attention'] = torch.is_grad_enabled(), attention
+    def steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, plan=None):
+        seen['grad'], seen['attention'] = torch.is_grad_enabled(), plan.attention
         return None, None, AttnMaps({}, torch.zeros(1))
         yield                                                               # (a generator, like _greedy_steps)
     m._greedy_steps = steps.__get__(m)

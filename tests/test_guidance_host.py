@@ -358,9 +358,13 @@ def test_constructor_keys_and_defaults():
     assert inspect.signature(DecodeStepper.__init__).parameters['guide'].default is None
     assert hasattr(DecodeStepper, 'set_guidance')
     assert inspect.signature(AdaptiveSoftmax.topk).parameters['guide'].default is None
-    for fn in (CaptionModel._generate, CaptionModel._generate_cached, CaptionModel._generate_beam, CaptionModel._greedy_steps,
-               CaptionModel._beam_steps):
-        assert inspect.signature(fn).parameters['guide'].default is None
+    from tell_amd.models.gen_options import DecodePlan
+    assert inspect.signature(CaptionModel._generate).parameters['guide'].default is None
+    assert DecodePlan().guide is None and DecodePlan._field_defaults['guide'] is None
+    for fn in (CaptionModel._generate_cached, CaptionModel._generate_beam):      # (they take the plan's fields as keywords)
+        assert inspect.signature(fn).parameters['options'].kind is inspect.Parameter.VAR_KEYWORD
+    for fn in (CaptionModel._greedy_steps, CaptionModel._beam_steps):
+        assert inspect.signature(fn).parameters['plan'].default == DecodePlan()
     assert 'guidance' not in inspect.signature(CaptionModel.score_captions).parameters
 
 

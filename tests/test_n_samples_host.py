@@ -45,9 +45,12 @@ def test_the_three_arguments_are_in_every_signature_with_their_defaults():
     for fn in (CaptionModel.generate, CaptionModel.generate_lanes, PointerModelBase.generate):
         p = inspect.signature(fn).parameters
         assert p['n_samples'].default == 1 and p['rank_by'].default == 'score' and p['rank_len_penalty'].default == 0.0, fn
-    assert inspect.signature(CaptionModel._greedy_steps).parameters['n'].default == 1
+    from tell_amd.models.gen_options import DecodePlan
+    assert DecodePlan().samples is None                              # (n, rule, alpha) of _check_n_samples; None: one draw
+    assert inspect.signature(CaptionModel._greedy_steps).parameters['plan'].default == DecodePlan()
     assert inspect.signature(DecodeStepper.__init__).parameters['hyp'].default == 1
-    assert inspect.signature(CaptionModel._decode_stepper).parameters['hyp'].default == 1
+    # (_decode_stepper hands its keywords to the stepper as they are: the stepper's own default is the pin)
+    assert inspect.signature(CaptionModel._decode_stepper).parameters['kw'].kind is inspect.Parameter.VAR_KEYWORD
 
 
 def test_n_samples_refusals():

@@ -163,7 +163,9 @@ def test_token_stats_is_an_argument_with_default_zero_and_zero_touches_nothing(m
     for fn in (CaptionModel.generate, CaptionModel.generate_lanes, CaptionModel.generate_stream, CaptionModel.score_captions,
                TransformerPointerModel.generate, BaselineGloveModel.generate):
         assert inspect.signature(fn).parameters['token_stats'].default == 0, fn
+    from tell_amd.models.gen_options import DecodePlan
     assert inspect.signature(stepper.DecodeStepper.__init__).parameters['stats'].default == 0
+    assert DecodePlan().stats == 0
     m = _shell(CaptionModel, _Dyn())
     m.fast_generation = True
     seen = {}
@@ -179,7 +181,7 @@ def test_token_stats_is_an_argument_with_default_zero_and_zero_touches_nothing(m
     assert 'stats' not in seen                                                # 0: the call of before, no key handed on
     m.generate(None, None, None, token_stats=3)
     assert seen.get('stats') == 3
-    # _generate_cached hands `stats` to _greedy_steps only when set (stand-ins for _greedy_steps keep working)
+    # _generate_cached hands _greedy_steps one plan: the plain one without an option, `stats` in its field when set
     monkeypatch.undo()
     got = {}
 
@@ -189,9 +191,9 @@ def test_token_stats_is_an_argument_with_default_zero_and_zero_touches_nothing(m
         yield
     monkeypatch.setattr(CaptionModel, '_greedy_steps', steps)
     m._generate_cached(None, None)
-    assert 'stats' not in got
+    assert set(got) == {'plan'} and got['plan'] == DecodePlan()
     m._generate_cached(None, None, stats=5)
-    assert got['stats'] == 5
+    assert set(got) == {'plan'} and got['plan'] == DecodePlan(stats=5) and got['plan'].stats == 5
 
 
 def test_stats_sink_layout_and_neutral_reset():

@@ -116,7 +116,8 @@ def evaluate_from_file(archive_path, model_path=None, overrides='', eval_suffix=
     assert archive_path.endswith('yaml'), 'model archives (.tar.gz) are an AllenNLP format; pass the config.yaml'
     params = cfg.yaml_to_params(archive_path, overrides)
     serialization_dir = os.path.join(os.path.dirname(archive_path), 'serialization')
-    reader = cfg.reader_from_params(params['dataset_reader'], **({'shard_dir': shard_dir} if shard_dir else {}))
+    reader_extra = {'shard_dir': shard_dir} if shard_dir else {}     # (an argument overrides the config's own key)
+    reader = cfg.reader_from_params(params['dataset_reader'], **reader_extra)
     vocab = cfg.vocabulary_from_params(params['vocabulary'])
     model = cfg.model_from_params(params['model'], vocab, **model_extra)
     if model_path:

@@ -257,10 +257,10 @@ class TransformerGloveModel(CaptionModel):
             raise ValueError('%s: %s reads GloVe article vectors; its batches hold no article token ids to ground a class in'
                              % ('ground' if ground is not None and ground is not False else 'ground_names', type(self).__name__))
 
-    def _glove_mask(self, caption, banned=None, attention=False):
-        """_vocab_mask for a batch without article ids: the banned set alone (an empty article)."""
+    def _no_article(self, caption):
+        """The `context` of a batch without article ids, for _vocab_mask: an empty article - the mask is the banned set alone."""
         ids = caption[self.index]
-        return self._vocab_mask({self.index: ids.new_zeros(ids.shape[0], 0)}, banned, None, attention)
+        return {self.index: ids.new_zeros(ids.shape[0], 0)}
     _vectors = staticmethod(BaselineGloveModel._vectors)
     _glove_forward = BaselineGloveModel._forward
 
@@ -275,10 +275,9 @@ class TransformerGloveModel(CaptionModel):
         loss = (loss_sum / math.log(2) / sample_size.to(torch.float32)).reshape(())
         out = {'loss': loss, 'sample_size': sample_size.reshape(())}
         if not self.training and self.evaluate_mode:
-            vm = self._glove_mask(caption)
+            vm = self._vocab_mask(self._no_article(caption))
             guide = self._check_guidance()
-            _, gen_ids, _ = self._generate(caption_ids, contexts, **({'vmask': vm} if vm is not None else {}),
-                                           **({'guide': guide} if guide is not None else {}))
+            _, gen_ids, _ = self._generate(caption_ids, contexts, vmask=vm, guide=guide)
             out['gen_ids'] = gen_ids.cpu().numpy()
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
@@ -290,22 +289,8 @@ class TransformerGloveModel(CaptionModel):
         if attention:
             self._check_attention(beam_size)
         self._check_grounding(ground)
-        vm = self._glove_mask(caption, banned, attention)
-        guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
-        self._check_options(beam_size, attention, n_best)
-        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
-        ts = self._check_token_stats(token_stats, beam_size, n_best, guide)
-        pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
+        plan = self._plan(beam_size, attention, n_best, prefix, n_samples, rank_by, rank_len_penalty, banned, ground, guidance,
+                          guidance_drop, token_stats, self._no_article(caption), caption[self.index].shape[0])
         caption_ids, _, contexts = self._glove_forward(self._vectors(context_vectors, metadata), image, caption)
         contexts = {k: v for k, v in contexts.items() if v is not None}
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=beam_size, attention=attention,
-                                                   **({'n_best': n_best} if n_best != 1 else {}),
-                                                   **({'prefix': pfx} if pfx is not None else {}),
-                                                   **({'samples': ns} if ns is not None else {}),
-                                                   **({'vmask': vm} if vm is not None else {}),
-                                                   **({'guide': guide} if guide is not None else {}),
-                                                   **({'token_stats': ts} if ts else {}))
-        out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
-        if pfx is not None:
-            out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)
-        return out
+        return self._generated(plan, *self._generate(caption_ids, contexts, **plan.keywords()))

@@ -264,7 +264,7 @@ class _DynamicConvDecoderBase(Decoder):
                 X = ops.grad_ready_marker(X, 'decoder.layers.%d.' % i)    # DP: layer i's gradients are final here
                 X, attn = layer(X, contexts, incremental_state, contexts_t,
                                 None if kv_cache is None else kv_cache[i], None if kv_packed is None else kv_packed[i],
-                                **({} if attn_sink is None else {'attn_sink': (attn_sink, i, sink_idx)}))
+                                attn_sink=None if attn_sink is None else (attn_sink, i, sink_idx))
                 inner_states.append(X)
             attns.append(attn)
         if self.normalize:                                                         # :125-126

@@ -336,7 +336,7 @@ class PointerModelBase(CaptionModel):
         H = self.copy_heads
         kv = dec.project_contexts(contexts)
         sampling = self._sampling()
-        step = self._decode_stepper(B, kv, contexts, gen_len, sample=sampling, hidden=True, **({'hyp': n} if n > 1 else {}))
+        step = self._decode_stepper(B, kv, contexts, gen_len, sample=sampling, hidden=True, hyp=n)
         k_src = self._copy_k(self._article_2(enc)).transpose(0, 1)           # [B, S, E], once per batch
         S, dtype = k_src.shape[1], k_src.dtype
         ea = self.entity_attn
@@ -403,7 +403,7 @@ class PointerModelBase(CaptionModel):
             ent = ops.entity_logits(x_entity, fc.weight_g, fc.weight_v, fc.bias)
             ops.copy_decide(self._copy_q(xt[0]), k_article, self.bias_k, cp['mask'], cp['proper'], cp['ctx_ids'], ent,
                             gen_tok.reshape(B), fin8, cp['hist'], cp['copied'], cp['probs'], i, H, cp['scratch'], cp['tok'],
-                            step_dev, **({'per_image': n} if n > 1 else {}))
+                            step_dev, per_image=n)
             # the bookkeeping of the plain greedy decode, on the copy decision's token; the log-prob stays the generator's
             ops.call('tell_greedy_update', cp['tok'], lp.reshape(B), fin8, ids, ids.stride(0), lps, lps.stride(0), done_step,
                      next_cur, B, int(i), int(eos), inv_temp, step.counter_out, step_dev)

@@ -1,14 +1,22 @@
 """tell/models/transformer_faces_objects.py:23-517 and tell/models/transformer_flattened.py:24-443
 on the MI355X path (training forward + loss, greedy generation)."""
-import math
 import os
-from collections import defaultdict, namedtuple
+from collections import defaultdict
 
 import torch
 import torch.nn as nn
 
 from .. import graphs, ops, streams
 from ..common.registrable import Registrable
+# (the option code and the host definitions live in gen_options.py / definitions.py; their names stay importable from here)
+from .definitions import (_id_order_draw, advantage_definition, caption_reward_definition, minp_definition,  # noqa: F401
+                          nucleus_definition, sample_rank_definition, token_stats_definition, typical_definition)
+from .gen_options import (DEFAULT_GEN_LEN, GUIDANCE_CONTEXTS, MAX_N_SAMPLES, MAX_NO_REPEAT_NGRAM,  # noqa: F401
+                          MAX_SAMPLING_TOPK, MIN_ALLOWED_TOKENS, PENALTY_KEYS, RANK_BY, TOKEN_STATS_KEYS, AttnMaps, AttnMapsStats,
+                          DecodeInfo, DecodePlan, OptionChecks, check_beam_options, check_caption_weights, check_guidance,
+                          check_mask_keys, check_n_samples, check_penalties, check_per_image, check_prefix, check_sampling,
+                          check_token_stats, check_vocab_mask, draw_seed, encode_prefix, guided_batch, inv_norm_table,
+                          token_stats_neutral)
 from .stepper import TOKEN_STATS_REFUSALS, DecodeStepper
 
 _OVERLAP = os.environ.get('TELL_ENCODER_OVERLAP', '1') != '0'
@@ -61,562 +69,11 @@ class Model(nn.Module, Registrable):
         return output_dict
 
 
-MAX_SAMPLING_TOPK = 64          # tell_adaptive_logprob_sample's exact top-k
-
-
-def check_sampling(sampling_topk, sampling_temp, sampling_topp=None, sampling_minp=None, sampling_typical=None):
-    """The caption models' `sampling_topk` / `sampling_temp` (transformer_faces_objects.py:38-55): top-k sampling with a
-    temperature, 1 <= k <= 64 (k = 1: the arg-max token) and T > 0.  -> (k, T); ValueError otherwise.
-    With `sampling_topp` = p (nucleus sampling, 0 < p <= 1): k is 0 (no top-k cut) or 2..64 -> (k, T, p).
-    With `sampling_minp` = m (min-p, 0 < m <= 1) or `sampling_typical` = tau (locally typical sampling, 0 < tau <= 1;
-    DESIGN.md section 19): at most one of the three, and sampling_topk must be 0 -> (0, T, m, 'minp') / (0, T, tau, 'typical')."""
-    rules = [(n, v) for n, v in (('sampling_topp', sampling_topp), ('sampling_minp', sampling_minp),
-                                 ('sampling_typical', sampling_typical)) if v is not None]
-    if len(rules) > 1:
-        raise ValueError('%s do not combine: one truncation rule per model' % ' and '.join('%s=%r' % r for r in rules))
-    if sampling_minp is not None or sampling_typical is not None:
-        name, v = rules[0]
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) <= 1.0:
-            raise ValueError('%s must be a number with 0 < %s <= 1, or None (got %r)'
-                             % (name, 'm' if name == 'sampling_minp' else 'tau', v))
-        k = sampling_topk
-        if isinstance(k, bool) or not isinstance(k, (int, float)) or k != 0:
-            raise ValueError('with %s, sampling_topk must be 0: the rule takes no top-k cut (got sampling_topk=%r)' % (name, k))
-        _, temp = check_sampling(2, sampling_temp)
-        return 0, temp, float(v), name[len('sampling_'):]
-    if sampling_topp is not None:
-        p = sampling_topp
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
-            raise ValueError('sampling_topp must be a number with 0 < p <= 1, or None (got %r)' % (p,))
-        k = sampling_topk
-        if not isinstance(k, bool) and isinstance(k, (int, float)) and k == 1:
-            raise ValueError('sampling_topk=1 (the arg-max token) and sampling_topp=%r do not combine: pass sampling_topk=0 '
-                             'for a nucleus without a top-k cut' % (p,))
-        if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or \
-                not (int(k) == 0 or 2 <= int(k) <= MAX_SAMPLING_TOPK):
-            raise ValueError('with sampling_topp, sampling_topk must be 0 (no top-k cut) or an integer in 2..%d (got %r)'
-                             % (MAX_SAMPLING_TOPK, k))
-        _, temp = check_sampling(2, sampling_temp)
-        return int(k), temp, float(p)
-    if isinstance(sampling_topk, bool) or not isinstance(sampling_topk, (int, float)) or int(sampling_topk) != sampling_topk \
-            or not 1 <= int(sampling_topk) <= MAX_SAMPLING_TOPK:
-        raise ValueError('sampling_topk must be an integer in 1..%d (got %r)' % (MAX_SAMPLING_TOPK, sampling_topk))
-    if isinstance(sampling_temp, bool) or not isinstance(sampling_temp, (int, float)) or not float(sampling_temp) > 0.0 \
-            or float(sampling_temp) == float('inf'):
-        raise ValueError('sampling_temp must be a finite number > 0 (got %r)' % (sampling_temp,))
-    return int(sampling_topk), float(sampling_temp)
-
-
-MAX_NO_REPEAT_NGRAM = 8         # tell_decode_ban_list's longest n-gram
-DEFAULT_GEN_LEN = 100           # `_generate`'s gen_len: what the constructor checks min_len against
-
-
-def check_beam_options(beam_len_penalty=0.0, no_repeat_ngram_size=0, min_len=0, gen_len=DEFAULT_GEN_LEN):
-    """The search options of the cached generators: `beam_len_penalty` alpha >= 0 (score =
-    sum of log-probs * len ** -alpha; beam search), `no_repeat_ngram_size` 0 (off) or 1..8, `min_len` 0..gen_len - 1 (no
-    </s> before that step) - the last two for greedy and beam search.  -> (alpha, n, min_len); ValueError otherwise."""
-    a = beam_len_penalty
-    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) < float('inf'):
-        raise ValueError('beam_len_penalty must be a finite number >= 0 (got %r)' % (a,))
-    n = no_repeat_ngram_size
-    if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or not 0 <= int(n) <= MAX_NO_REPEAT_NGRAM:
-        raise ValueError('no_repeat_ngram_size must be 0 (off) or an integer in 1..%d (got %r)' % (MAX_NO_REPEAT_NGRAM, n))
-    m = min_len
-    if isinstance(m, bool) or not isinstance(m, (int, float)) or int(m) != m or not 0 <= int(m) <= int(gen_len) - 1:
-        raise ValueError('min_len must be an integer in 0..%d (gen_len - 1; got %r)' % (int(gen_len) - 1, m))
-    return float(a), int(n), int(m)
-
-
-PENALTY_KEYS = ('repetition_penalty', 'presence_penalty', 'frequency_penalty')
-
-
-def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
-    """The soft repetition controls of the cached generators: `repetition_penalty` theta, finite and
-    >= 1; `presence_penalty` alpha and `frequency_penalty` beta, finite and >= 0.  A token that the caption already holds
-    c >= 1 times scores min(lp, 0) * theta - (alpha + beta * c) instead of its log-prob lp.  -> (theta, alpha, beta);
-    ValueError naming the option otherwise."""
-    out = []
-    for name, v, lo in zip(PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty), (1.0, 0.0, 0.0)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) < float('inf'):
-            raise ValueError('%s must be a finite number >= %g (got %r)' % (name, lo, v))
-        out.append(float(v))
-    return tuple(out)
-
-
-MIN_ALLOWED_TOKENS = MAX_SAMPLING_TOPK       # every row of a vocabulary mask keeps that many tokens: a pick has k real candidates
-
-
-def check_mask_keys(suppress_tokens=(), ground_names=False):
-    """The constructor / config keys of the vocabulary masks: `suppress_tokens`, a list of token ids
-    that no caption may contain (folded into the banned set), and `ground_names`, a bool (generate(ground=True)).
-    -> (tuple of ids, bool); ValueError naming the key otherwise."""
-    st = suppress_tokens
-    if st is None:
-        st = ()
-    if isinstance(st, (str, bytes)) or not isinstance(st, (list, tuple)) or \
-            any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in st):
-        raise ValueError('suppress_tokens must be a list of token ids >= 0 (got %r)' % (suppress_tokens,))
-    if not isinstance(ground_names, bool):
-        raise ValueError('ground_names must be a bool (got %r)' % (ground_names,))
-    return tuple(sorted(set(int(t) for t in st))), ground_names
-
-
-GUIDANCE_CONTEXTS = ('image', 'article', 'faces', 'obj')
-
-
-def check_guidance(guidance_scale=1.0, guidance_drop=('image',)):
-    """The keys of context guidance: `guidance_scale` gamma, a finite number >= 0 (1.0: off), and
-    `guidance_drop`, a non-empty list of context names out of image / article / faces / obj - the contexts the unconditional
-    pass decodes without.  -> (gamma, names in the order above)."""
-    g = guidance_scale
-    if isinstance(g, bool) or not isinstance(g, (int, float)) or not math.isfinite(g) or g < 0:
-        raise ValueError('guidance_scale must be a finite number >= 0 (got %r)' % (guidance_scale,))
-    d = (guidance_drop,) if isinstance(guidance_drop, str) else guidance_drop
-    if not isinstance(d, (list, tuple)) or not d or any(not isinstance(n, str) for n in d):
-        raise ValueError('guidance_drop must be a non-empty list of context names out of %s (got %r)'
-                         % (' / '.join(GUIDANCE_CONTEXTS), guidance_drop))
-    unknown = [n for n in d if n not in GUIDANCE_CONTEXTS]
-    if unknown:
-        raise ValueError('guidance_drop: unknown context %s (the contexts are %s)'
-                         % (' / '.join(repr(n) for n in unknown), ' / '.join(GUIDANCE_CONTEXTS)))
-    return float(g), tuple(n for n in GUIDANCE_CONTEXTS if n in d)
-
-
-def guided_batch(caption_ids, contexts, drop):
-    """The batch of a guided decode: images B .. 2B - 1 are copies of 0 .. B - 1 whose dropped contexts
-    have an all-masked key-padding mask - they attend to the bias key and the zero key only.  Contexts are [S, B, E] views of
-    [B, S, E] storage and stay that; masks are [B, S].  -> (caption_ids [2B, T], contexts)."""
-    for n in drop:
-        if n not in contexts or n + '_mask' not in contexts:
-            raise ValueError('guidance_drop: the decoder has no context %r (it has %s)'
-                             % (n, ' / '.join(k for k in contexts if not k.endswith('_mask'))))
-    out = {}
-    for k, v in contexts.items():
-        if not torch.is_tensor(v):
-            out[k] = v
-        elif k.endswith('_mask'):
-            twin = torch.ones_like(v) if k[:-5] in drop else v
-            out[k] = torch.cat([v, twin], 0)
-        else:
-            out[k] = torch.cat([v.transpose(0, 1), v.transpose(0, 1)], 0).transpose(0, 1)
-    return torch.cat([caption_ids, caption_ids], 0), out
-
-
-def check_vocab_mask(banned, ground, vocab_size, batch_size, eos=2, suppress=()):
-    """generate(banned=, ground=) (DESIGN.md section 22).  banned: bool [V] or [B, V], True = the token may not be generated;
-    ground: bool [V], the grounded class - its tokens may be generated only if they occur in the row's own article; `suppress`:
-    ids folded into the banned set (the model's `suppress_tokens`).  </s> may not be banned (it is never in the class: the mask
-    kernel clears it), and every row must keep at least 64 allowed tokens - the sampler's largest k, so every pick has k real
-    candidates; for `ground` that is counted on the class's complement, for `banned` it is one reduction and one sync per call.
-    -> (deny bool [1 or B, V] or None, cls bool [V] or None); ValueError naming the option otherwise."""
-    V, B = int(vocab_size), int(batch_size)
-    cls = deny = None
-    if ground is not None:
-        if not torch.is_tensor(ground) or ground.dtype != torch.bool or tuple(ground.shape) != (V,):
-            raise ValueError('ground must be a bool tensor [%d] (the grounded class) or True (got %s)' % (
-                V, '%s %s' % (ground.dtype, tuple(ground.shape)) if torch.is_tensor(ground) else repr(ground)))
-        cls = ground.clone()
-        if 0 <= int(eos) < V:
-            cls[int(eos)] = False
-        if V - int(cls.sum()) < MIN_ALLOWED_TOKENS:
-            raise ValueError('ground: the class leaves %d tokens outside it, at least %d must stay allowed'
-                             % (V - int(cls.sum()), MIN_ALLOWED_TOKENS))
-    if banned is not None:
-        if not torch.is_tensor(banned) or banned.dtype != torch.bool or banned.dim() not in (1, 2) or \
-                banned.shape[-1] != V or (banned.dim() == 2 and banned.shape[0] != B):
-            raise ValueError('banned must be a bool tensor [%d] or [%d, %d] (got %s)' % (
-                V, B, V, '%s %s' % (banned.dtype, tuple(banned.shape)) if torch.is_tensor(banned) else repr(banned)))
-        deny = banned.view(1, V) if banned.dim() == 1 else banned
-        if 0 <= int(eos) < V and bool(deny[:, int(eos)].any()):
-            raise ValueError('banned: </s> (%d) may not be banned - a caption could never end' % int(eos))
-    sup = [int(t) for t in suppress]
-    if sup:
-        if max(sup) >= V:
-            raise ValueError('suppress_tokens: token ids must lie in 0..%d (got %d)' % (V - 1, max(sup)))
-        if int(eos) in sup:
-            raise ValueError('suppress_tokens: </s> (%d) may not be suppressed - a caption could never end' % int(eos))
-        dev = deny.device if deny is not None else (cls.device if cls is not None else 'cpu')
-        deny = deny.clone() if deny is not None else torch.zeros(1, V, dtype=torch.bool, device=dev)
-        deny[:, torch.tensor(sup, dtype=torch.long, device=deny.device)] = True
-    if deny is not None:
-        gone = deny if cls is None else (deny | cls.to(deny.device).view(1, V))
-        left = V - int(gone.sum(1).max())                    # (the one reduction and sync of the non-default path)
-        if left < MIN_ALLOWED_TOKENS:
-            raise ValueError('%s: a row keeps %d allowed tokens, at least %d must stay allowed'
-                             % ('banned' if banned is not None else 'suppress_tokens', left, MIN_ALLOWED_TOKENS))
-    return deny, cls
-
-
-def check_prefix(prefix, batch_size, vocab_size, gen_len=DEFAULT_GEN_LEN, pad=1, eos=2):
-    """The forced caption prefix of the cached generators: int64 [B, P], the caption tokens AFTER <s>,
-    right-padded with `pad`; plen[r] = the number of leading non-pad tokens (0: the row decodes freely).  </s> may only be
-    the last token of a row's prefix, ids lie in 0..vocab_size - 1, P <= gen_len, B = batch_size.
-    -> (prefix int64 [B, P] on the CPU, plen int32 [B]), or None for prefix = None; ValueError otherwise."""
-    if prefix is None:
-        return None
-    if not torch.is_tensor(prefix) or prefix.dtype != torch.long or prefix.dim() != 2:
-        raise ValueError('prefix must be an int64 tensor [B, P] of the caption tokens after <s> (got %s)' % (
-            '%s %s' % (prefix.dtype, tuple(prefix.shape)) if torch.is_tensor(prefix) else type(prefix).__name__))
-    B, P = prefix.shape
-    if B != int(batch_size):
-        raise ValueError('prefix has %d rows, the batch has %d' % (B, int(batch_size)))
-    if P > int(gen_len):
-        raise ValueError('prefix is %d tokens wide, generation stops after gen_len = %d' % (P, int(gen_len)))
-    pf = prefix.detach().cpu().contiguous()
-    real = pf != int(pad)
-    plen = real.sum(1)
-    if P and not bool((real == (torch.arange(P).unsqueeze(0) < plen.unsqueeze(1))).all()):
-        raise ValueError('prefix: a token follows a pad (rows are right-padded with %d)' % int(pad))
-    if P and bool((real & ((pf < 0) | (pf >= int(vocab_size)))).any()):
-        raise ValueError('prefix: token ids must lie in 0..%d' % (int(vocab_size) - 1))
-    if P and bool(((pf == int(eos)) & real & (torch.arange(P).unsqueeze(0) != (plen - 1).unsqueeze(1))).any()):
-        raise ValueError('prefix: </s> (%d) may only be the last token of a row\'s prefix' % int(eos))
-    return pf, plen.to(torch.int32)
-
-
-def encode_prefix(texts, bpe=None, pad=1):
-    """Caption starts as a `prefix` tensor: every string is encoded as the indexer encodes a caption
-    (data/indexers.RobertaTokenIndexer.encode) without <s> and without the closing </s>; '' or None gives a free row.
-    bpe: a RobertaBPE (default: the installed roberta-base files).  -> int64 [len(texts), P] right-padded with `pad`."""
-    from ..data.indexers import RobertaTokenIndexer
-    indexer = RobertaTokenIndexer(bpe=bpe, padding_value=pad)
-    rows = [indexer.encode(t)[0][1:-1] if t else [] for t in texts]
-    P = max([len(r) for r in rows] + [1])
-    out = torch.full((len(rows), P), int(pad), dtype=torch.long)
-    for i, r in enumerate(rows):
-        out[i, :len(r)] = torch.tensor(r, dtype=torch.long)
-    return out
-
-
-def inv_norm_table(alpha, L):
-    """The length-penalty table of tell_beam_update_norm: fp32 [L + 1], [0] = 1, [l] = float32(float64(l) ** -alpha)."""
-    import numpy as np
-    t = np.ones(int(L) + 1, dtype=np.float32)
-    t[1:] = (np.arange(1, int(L) + 1, dtype=np.float64) ** -float(alpha)).astype(np.float32)
-    return torch.from_numpy(t)
-
-
-MAX_N_SAMPLES = 16              # tell_sample_rank's hypotheses per image
-RANK_BY = ('draw', 'score', 'consensus')
-
-
-def check_n_samples(n_samples=1, rank_by='score', rank_len_penalty=0.0):
-    """generate(n_samples=, rank_by=, rank_len_penalty=): n an integer in 1..16, the rank rule one of
-    'draw' / 'score' / 'consensus', alpha a finite number >= 0 (score = sum of log-probs * len ** -alpha, as beam_len_penalty).
-    -> (n, rule, alpha); ValueError otherwise."""
-    n = n_samples
-    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_N_SAMPLES:
-        raise ValueError('n_samples must be an integer in 1..%d (got %r)' % (MAX_N_SAMPLES, n))
-    if not isinstance(rank_by, str) or rank_by not in RANK_BY:
-        raise ValueError('rank_by must be one of %s (got %r)' % (', '.join(repr(r) for r in RANK_BY), rank_by))
-    a = rank_len_penalty
-    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) < float('inf'):
-        raise ValueError('rank_len_penalty must be a finite number >= 0 (got %r)' % (a,))
-    return n, rank_by, float(a)
-
-
-def check_per_image(per_image, caption_rows, images):
-    """forward(per_image=n): n a positive integer with caption_rows == images * n -> n; ValueError otherwise."""
-    n = per_image
-    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
-        raise ValueError('per_image must be a positive integer (got %r)' % (n,))
-    if caption_rows != images * n:
-        raise ValueError('per_image=%d: %d images need %d captions (got %d)' % (n, images, images * n, caption_rows))
-    return n
-
-
-def check_caption_weights(w, target_ids):
-    """forward(caption_weights=w): fp32 [rows] or [rows, T] on the device of the targets [rows, T] -> fp32 [rows, T]
-    contiguous and detached; ValueError otherwise."""
-    rows, T = target_ids.shape
-    if not torch.is_tensor(w) or w.dtype != torch.float32 or w.device != target_ids.device or \
-            tuple(w.shape) not in ((rows,), (rows, T)):
-        raise ValueError('caption_weights must be an fp32 tensor [%d] or [%d, %d] on the device of the captions (got %s)'
-                         % (rows, rows, T, (tuple(w.shape), w.dtype, str(w.device)) if torch.is_tensor(w)
-                            else type(w).__name__))
-    w = w.detach()
-    return (w.unsqueeze(1).expand(rows, T) if w.dim() == 1 else w).contiguous()
-
-
 def refuse_weighted_forward(model, caption_weights=None, per_image=1):
     """The models outside the weighted / per-image training pass (copy, GloVe, LSTM) say so by name."""
     if caption_weights is not None or per_image != 1:
         raise ValueError('%s does not take caption_weights / per_image: the weighted training pass (self-critical '
                          'training) covers the transformer_faces_objects family only' % type(model).__name__)
-
-
-def caption_reward_definition(ids, ref, n, steps, ref_steps, pad, eos, max_order=4, baseline=None):
-    """The contract of tell_caption_reward (include/tell_hip.h) in numpy on the host - what the kernel is tested against and
-    what scores hypotheses that live on the CPU.  ids [B * n, > steps], ref [B, > ref_steps], baseline fp32 [B] or None.
-    -> dict: reward, adv fp32 [B, n]; counts int32 [B * n, 3] = (match, th, tr)."""
-    from collections import Counter
-    import numpy as np
-    ids, ref = np.asarray(ids), np.asarray(ref)
-    n, steps, ref_steps, K = int(n), int(steps), int(ref_steps), int(max_order)
-    R = ids.shape[0]
-    B = R // n
-
-    def cut(row, L):
-        out = []
-        for t in row[1:1 + L]:
-            if int(t) == int(eos) or int(t) == int(pad):
-                break
-            out.append(int(t))
-        return tuple(out)
-
-    def grams(t):
-        return [Counter(zip(*[t[i:] for i in range(k)])) for k in range(1, K + 1)]
-
-    def total(t):
-        return sum(max(len(t) - k + 1, 0) for k in range(1, K + 1))
-    reward, counts = np.zeros(R, dtype=np.float32), np.zeros((R, 3), dtype=np.int32)
-    for b in range(B):
-        rt_ = cut(ref[b], ref_steps)
-        rg, tr = grams(rt_), total(rt_)
-        for j in range(n):
-            h = cut(ids[b * n + j], steps)
-            match = sum(sum((a & c).values()) for a, c in zip(grams(h), rg))
-            th = total(h)
-            den = max(th, tr)
-            counts[b * n + j] = (match, th, tr)
-            reward[b * n + j] = np.float32(match) / np.float32(den) if den else np.float32(0.0)
-    reward = reward.reshape(B, n)
-    return {'reward': reward, 'adv': advantage_definition(reward, baseline), 'counts': counts}
-
-
-def advantage_definition(reward, baseline=None):
-    """reward fp32 [B, n] -> adv fp32 [B, n] by tell_caption_reward's rule: minus baseline[b] when given; else, for n > 1,
-    minus the leave-one-out mean s / (n - 1), s summed over the OTHER rewards in ascending j in one fp32 accumulator; else
-    the reward itself."""
-    import numpy as np
-    reward = np.asarray(reward, dtype=np.float32)
-    B, n = reward.shape
-    adv = np.zeros((B, n), dtype=np.float32)
-    for b in range(B):
-        for j in range(n):
-            if baseline is not None:
-                base = np.float32(np.asarray(baseline, dtype=np.float32).reshape(-1)[b])
-            elif n > 1:
-                s = np.float32(0.0)
-                for e in range(n):
-                    if e != j:
-                        s = np.float32(s + reward[b, e])
-                base = np.float32(s / np.float32(n - 1))
-            else:
-                base = np.float32(0.0)
-            adv[b, j] = np.float32(reward[b, j] - base)
-    return adv
-
-
-def sample_rank_definition(ids, lps, done_step, n, steps, eos, rule, inv_norm=None):
-    """The contract of tell_sample_rank (include/tell_hip.h) in numpy on the host - what the kernel is tested against and what
-    ranks hypotheses that live on the CPU.  ids [B * n, > steps], lps [B * n, >= steps], done_step [B * n]; rule 'draw' /
-    'score' / 'consensus' (or 0 / 1 / 2); inv_norm fp32 [>= steps + 1] or None.
-    -> dict of [B, n] arrays: len int32, score fp32 (sequential fp32 sum, one fp32 multiply), dup uint8, cons fp32, order int32."""
-    import functools
-    from collections import Counter
-    import numpy as np
-    ids, done = np.asarray(ids), np.asarray(done_step).reshape(-1)
-    lps = np.asarray(lps, dtype=np.float32)
-    rule = RANK_BY.index(rule) if isinstance(rule, str) else int(rule)
-    n, steps = int(n), int(steps)
-    R = ids.shape[0]
-    B = R // n
-    ln = np.clip(done, 0, steps).astype(np.int32)
-    score = np.zeros(R, dtype=np.float32)
-    with np.errstate(all='ignore'):
-        for r in range(R):
-            acc = np.float32(0.0)
-            for p in range(int(ln[r])):
-                acc = np.float32(acc + lps[r, p])
-            if inv_norm is not None:
-                acc = np.float32(acc * np.float32(inv_norm[int(ln[r])]))
-            score[r] = acc
-    dup, cons, order = np.zeros(R, dtype=np.uint8), np.zeros(R, dtype=np.float32), np.zeros(R, dtype=np.int32)
-    for b in range(B):
-        toks = [tuple(int(t) for t in ids[b * n + j, 1:1 + int(ln[b * n + j])]) for j in range(n)]
-        big = []
-        for j, t in enumerate(toks):
-            dup[b * n + j] = any(toks[e] == t for e in range(j))
-            g = t[:-1] if t and t[-1] == int(eos) else t
-            big.append(Counter(zip(g, g[1:])))
-        for i in range(n):
-            acc = np.float32(0.0)
-            for j in range(n):
-                if j == i:
-                    continue
-                den = sum(big[i].values()) + sum(big[j].values())
-                inter = sum((big[i] & big[j]).values())
-                acc = np.float32(acc + (np.float32(2 * inter) / np.float32(den) if den else np.float32(0.0)))
-            cons[b * n + i] = np.float32(acc / np.float32(n - 1)) if n > 1 else np.float32(0.0)
-        sc = score[b * n:(b + 1) * n]
-        key = (cons if rule == 2 else score)[b * n:(b + 1) * n].copy()
-        key[np.isnan(key)] = -np.inf
-        dp = dup[b * n:(b + 1) * n]
-
-        def cmp(e, j):                              # < 0: e ranks before j
-            if dp[e] != dp[j]:
-                return -1 if dp[e] < dp[j] else 1
-            if key[e] > key[j] or key[e] < key[j]:
-                return -1 if key[e] > key[j] else 1
-            if rule == 2 and (sc[e] > sc[j] or sc[e] < sc[j]):
-                return -1 if sc[e] > sc[j] else 1
-            return -1 if e < j else 1
-        order[b * n:(b + 1) * n] = list(range(n)) if rule == 0 else sorted(range(n), key=functools.cmp_to_key(cmp))
-    return {k_: v_.reshape(B, n) for k_, v_ in (('len', ln), ('score', score), ('dup', dup), ('cons', cons), ('order', order))}
-
-
-class DecodeInfo(list):
-    """Third result of the cached generators without attention maps: the empty list it always was, carrying what
-    `generate` reports beside the best hypothesis - scores [B] (beam: the normalised score of hypothesis 0) and, with
-    n_best > 1, nbest = (ids [B, n, L], log_probs [B, n, L - 1], scores [B, n]), best first; with n_samples > 1, samples =
-    the '*_samples' / 'sample_index' / 'duplicate' entries of the output dict, in rank order."""
-    scores = None
-    nbest = None
-    samples = None
-    token_stats = None             # generate(token_stats=n): the five per-token arrays of the output dict (first rank)
-
-
-def nucleus_definition(lp, temp, topp, topk=0, u=None):
-    """The definition of nucleus sampling (include/tell_hip.h tell_adaptive_logprob_nucleus, steps 1-4) on one row of
-    log-probs, in fp64 on the CPU - what the kernel is tested against.  lp: [V] log-probs; temp = T; topp = p; topk = 0 or
-    the size of the top-k cut; u in [0, 1) or None.
-    -> dict: members (token ids of the nucleus, ascending), boundary (the smallest member log-prob), margin
-    (|cum - p * total| / total at the boundary: the smaller of the distances by which the prefix reaches p * total and by
-    which the prefix without its last member misses it), cdf (running weight of the members in id order, normalised),
-    token (the pick for u, or None)."""
-    import numpy as np
-    lp = np.asarray(lp, dtype=np.float64).reshape(-1)
-    p = float(topp)
-    order = np.lexsort((np.arange(lp.size), -lp))             # value descending, lower id first on ties
-    if topk:
-        order = order[:int(topk)]
-    w = np.exp((lp[order] - lp[order[0]]) / float(temp))
-    cum = np.cumsum(w)
-    total = cum[-1]
-    n = min(int(np.searchsorted(cum, p * total, side='left')) + 1, order.size)
-    members = np.sort(order[:n])
-    margin = min(cum[n - 1] - p * total, p * total - (cum[n - 2] if n > 1 else 0.0)) / total
-    wm = np.exp((lp[members] - lp[order[0]]) / float(temp))
-    run = np.cumsum(wm)
-    out = {'members': members, 'boundary': float(lp[order[n - 1]]), 'margin': float(abs(margin)), 'cdf': run / run[-1],
-           'token': None}
-    if u is not None:
-        hit = np.nonzero(run > float(u) * run[-1])[0]
-        out['token'] = int(members[hit[0]] if hit.size else members[-1])
-    return out
-
-
-TOKEN_STATS_KEYS = ('alt_ids', 'alt_log_probs', 'token_rank', 'token_entropy', 'token_model_lp')
-
-
-def check_token_stats(token_stats=0):
-    """generate(token_stats=n): n alternatives per token, 0 (off) .. 8 (the K of the top-k kernels) -> int."""
-    if isinstance(token_stats, bool) or not isinstance(token_stats, int) or not 0 <= token_stats <= 8:
-        raise ValueError('token_stats must be an integer in 0..8 (alternatives per token; 0: off), got %r' % (token_stats,))
-    return token_stats
-
-
-def token_stats_neutral(B, steps, n, pad, device=None):
-    """What positions behind a row's </s> hold: alt_ids = pad, alt_log_probs = 0, token_rank = -1, token_entropy = 0,
-    token_model_lp = 0 - the five arrays of generate(token_stats=n) filled with them."""
-    return {'alt_ids': torch.full((B, steps, n), int(pad), dtype=torch.long, device=device),
-            'alt_log_probs': torch.zeros(B, steps, n, dtype=torch.float32, device=device),
-            'token_rank': torch.full((B, steps), -1, dtype=torch.long, device=device),
-            'token_entropy': torch.zeros(B, steps, dtype=torch.float32, device=device),
-            'token_model_lp': torch.zeros(B, steps, dtype=torch.float32, device=device)}
-
-
-def token_stats_definition(lp_full, chosen, n):
-    """The definition of the per-token statistics (include/tell_hip.h tell_adaptive_logprob_stats) on
-    one full row of log-probs, in torch on the CPU and in the row's own dtype - what the kernel and the generators are tested
-    against.  lp_full: [V] log-probs of the model's own distribution; chosen: the token the step took; n alternatives.
-    -> dict: alt_ids int64 [n] / alt_log_probs [n] (value descending, lower id first on ties; (0x7fffffff, -inf) past the
-    vocabulary), token_rank (#{t: lp_t > lp_c or (lp_t == lp_c and t < c)}; -1 for a token outside the vocabulary),
-    token_entropy (-sum p log p in nats, terms with p = 0 dropped), token_model_lp (lp_c; 0 outside the vocabulary)."""
-    lp = torch.as_tensor(lp_full).detach().cpu().reshape(-1)
-    V, n, c = lp.numel(), int(n), int(chosen)
-    order = torch.sort(-lp, stable=True).indices               # (stable: equal values keep id order)
-    alt = order[:n]
-    alt_ids = torch.full((n,), 0x7fffffff, dtype=torch.long)
-    alt_lp = torch.full((n,), float('-inf'), dtype=lp.dtype)
-    alt_ids[:alt.numel()] = alt
-    alt_lp[:alt.numel()] = lp[alt]
-    p = lp.exp()
-    ent = -(torch.where(p > 0, p * lp, torch.zeros_like(lp))).sum()
-    if 0 <= c < V:
-        ids = torch.arange(V)
-        rank = int(((lp > lp[c]) | ((lp == lp[c]) & (ids < c))).sum())
-        lp_c = lp[c].clone()
-    else:
-        rank, lp_c = -1, lp.new_zeros(())
-    return {'alt_ids': alt_ids, 'alt_log_probs': alt_lp, 'token_rank': rank, 'token_entropy': ent, 'token_model_lp': lp_c}
-
-
-def _id_order_draw(out, members, wm, u):
-    import numpy as np
-    run = np.cumsum(wm)
-    out['cdf'] = run / run[-1]
-    out['token'] = None
-    if u is not None:
-        hit = np.nonzero(run > float(u) * run[-1])[0]
-        out['token'] = int(members[hit[0]] if hit.size else members[-1])
-    return out
-
-
-def minp_definition(lp, temp, minp, u=None):
-    """The definition of min-p sampling (include/tell_hip.h tell_adaptive_logprob_minp) on one row of log-probs.  The member
-    set is the kernel's float32 statement - a = (lp - max lp) * float32(1 / T), one fp32 subtract and one fp32 multiply; member
-    iff a >= float32(log(m)) - so lp is taken as fp32; the weights of the draw are fp64.
-    -> dict: members (ascending ids), a (fp32 [V]), threshold (float32(log m)), cdf (running weight of the members in id order,
-    normalised), token (the pick for u, or None)."""
-    import numpy as np
-    lp32 = np.asarray(lp, dtype=np.float32).reshape(-1)
-    a = (lp32 - lp32.max()) * np.float32(1.0 / float(temp))
-    thr = np.float32(math.log(float(minp)))
-    members = np.nonzero(a >= thr)[0]
-    lp64 = lp32.astype(np.float64)
-    wm = np.exp((lp64[members] - lp64.max()) / float(temp))
-    return _id_order_draw({'members': members, 'a': a, 'threshold': thr}, members, wm, u)
-
-
-def typical_definition(lp, temp, tau, c=None, u=None):
-    """The definition of locally typical sampling (include/tell_hip.h tell_adaptive_logprob_typical) on one row of log-probs:
-    a = (lp - max lp) / T, w = exp(a), c = -(sum w a) / (sum w), d = |a + c|; the members are the shortest prefix of the order
-    (d ascending, lower id first on ties) whose weight reaches tau * (total weight).  Mass sums in fp64.  c = None: everything
-    in fp64.  c given (the kernel's fp32 c): the ORDER is taken from the kernel's fp32 d = |(lp - max lp) * float32(1 / T) + c|
-    (fp32 subtract, multiply, add), so that only the masses differ from the kernel's.
-    -> dict: members (ascending ids), order (all ids, best first), c (the fp64 c), boundary (d of the worst member), key
-    (~bits of float32(boundary): the kernel's nuc_key), margin (as nucleus_definition's, relative to the total weight), cdf,
-    token."""
-    import numpy as np
-    lp64 = np.asarray(lp, dtype=np.float64).reshape(-1)
-    a = (lp64 - lp64.max()) / float(temp)
-    w = np.exp(a)
-    total = w.sum()
-    c64 = -float((w * a).sum() / total)
-    if c is None:
-        d = np.abs(a + c64)
-    else:
-        lp32 = np.asarray(lp, dtype=np.float32).reshape(-1)
-        d = np.abs((lp32 - lp32.max()) * np.float32(1.0 / float(temp)) + np.float32(c))
-        assert d.dtype == np.float32
-    order = np.lexsort((np.arange(d.size), d))
-    cum = np.cumsum(w[order])
-    target = float(tau) * cum[-1]
-    n = min(int(np.searchsorted(cum, target, side='left')) + 1, order.size)
-    members = np.sort(order[:n])
-    margin = min(cum[n - 1] - target, target - (cum[n - 2] if n > 1 else 0.0)) / cum[-1]
-    bound = d[order[n - 1]]
-    out = {'members': members, 'order': order, 'c': c64, 'boundary': float(bound), 'margin': float(abs(margin)),
-           'key': int(~np.array([bound], dtype=np.float32).view(np.uint32)[0] & np.uint32(0xFFFFFFFF))}
-    return _id_order_draw(out, members, w[members], u)
-
-
-def draw_seed():
-    """The seed of one batch's sampled decode: 31 bits from torch's default CPU generator (torch.manual_seed makes the
-    captions reproducible)."""
-    return int(torch.randint(0, 1 << 31, (1,)).item())
 
 
 def set_sampling(model, sampling_topk, sampling_temp, sampling_topp=None, sampling_minp=None, sampling_typical=None):
@@ -628,19 +85,7 @@ def set_sampling(model, sampling_topk, sampling_temp, sampling_topp=None, sampli
     model.sampling_typical = None if sampling_typical is None else float(sampling_typical)
 
 
-class AttnMaps(namedtuple('AttnMaps', 'maps steps')):
-    """Third result of the cached generator with attention=True (without: the empty list it always was).
-    maps: {context name: fp32 [B, steps, n_layers, S + 2]} on the device; steps: [B] long, the row's `done_step` - the
-    number of decode steps it took part in, the one that produced its </s> included."""
-    __slots__ = ()
-
-
-class AttnMapsStats(AttnMaps):
-    """AttnMaps of a generation that also kept per-token statistics (attention=True, token_stats=n): .token_stats as DecodeInfo's."""
-    token_stats = None
-
-
-class CaptionModel(Model):
+class CaptionModel(OptionChecks, Model):
     USE_FACES_OBJECTS = False
     EVAL_ATTENTION = True        # forward() in evaluate mode honours `eval_attention` (commands/evaluate.py attention_maps=True)
     EXTRA_CONTEXTS = ()          # which of ('faces', 'obj') the model feeds to its decoder
@@ -687,190 +132,6 @@ class CaptionModel(Model):
         # re-home those copies (a checkpoint load, a trainer re-flagging requires_grad) drops the captures
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.reset_graphs())
 
-    def _sampling(self):
-        """-> (k, T) when generation samples (sampling_topk > 1), None for the arg-max decode (sampling_topk = 1);
-        (k, T, p) with nucleus sampling (sampling_topp = p; k = 0: no top-k cut); (0, T, m, 'minp') with sampling_minp = m and
-        (0, T, tau, 'typical') with sampling_typical = tau."""
-        k = int(self.sampling_topk)
-        for rule in ('minp', 'typical'):
-            v = getattr(self, 'sampling_' + rule, None)
-            if v is not None:
-                return (0, float(self.sampling_temp), float(v), rule)
-        p = getattr(self, 'sampling_topp', None)
-        if p is not None:
-            return (k, float(self.sampling_temp), float(p))
-        return (k, float(self.sampling_temp)) if k > 1 else None
-
-    def _truncation(self):
-        """-> 'sampling_minp=0.1' / 'sampling_typical=0.9' when one of the two rules is set, else None."""
-        for name in ('sampling_minp', 'sampling_typical'):
-            if getattr(self, name, None) is not None:
-                return '%s=%r' % (name, getattr(self, name))
-        return None
-
-    def _check_truncation(self):
-        """sampling_minp / sampling_typical: the cached DynamicConv generator only."""
-        what = self._truncation()
-        if what and (not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts')):
-            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); min-p and '
-                             'typical sampling cover the cached DynamicConv generator only' % (what, type(self).__name__))
-
-    def _check_beam(self, beam_size):
-        if int(beam_size) > 1 and self._truncation():
-            raise ValueError('beam search (beam_size %d) and %s do not combine' % (int(beam_size), self._truncation()))
-        if int(beam_size) > 1 and getattr(self, 'sampling_topp', None) is not None:
-            raise ValueError('beam search (beam_size %d) and nucleus sampling (sampling_topp %r) do not combine'
-                             % (int(beam_size), self.sampling_topp))
-        if int(beam_size) > 1 and self._sampling() is not None:
-            raise ValueError('beam search (beam_size %d) and top-k sampling (sampling_topk %d) do not combine: the reference '
-                             'samples without a beam' % (int(beam_size), int(self.sampling_topk)))
-
-    SEARCH_OPTIONS = True        # the class decodes through the cached generator below (False: the options are refused)
-
-    def _search_options(self, gen_len=DEFAULT_GEN_LEN):
-        """-> (alpha, n, min_len) of the model's attributes, checked; None when all three are at their defaults."""
-        opts = check_beam_options(getattr(self, 'beam_len_penalty', 0.0), getattr(self, 'no_repeat_ngram_size', 0),
-                                  getattr(self, 'min_len', 0), gen_len)
-        return None if opts == (0.0, 0, 0) else opts
-
-    def _check_options(self, beam_size=1, attention=False, n_best=1, gen_len=DEFAULT_GEN_LEN):
-        """What the search options and n_best combine with: the arg-max / beam decode of the cached DynamicConv generator -
-        no sampling, no attention maps, not the LSTM decoders nor the copy models."""
-        if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= max(int(beam_size), 1):
-            raise ValueError('n_best must be an integer in 1..beam_size (got n_best=%r with beam_size=%d)'
-                             % (n_best, int(beam_size)))
-        opts = self._search_options(gen_len)
-        used = [name for name, v in zip(('beam_len_penalty', 'no_repeat_ngram_size', 'min_len'), opts or ()) if v]
-        if n_best > 1:
-            used.append('n_best')
-        if not used:
-            return None
-        what = ' / '.join('%s=%r' % (u, n_best if u == 'n_best' else getattr(self, u)) for u in used)
-        if self._truncation():
-            raise ValueError('%s and %s do not combine: the search options apply to the arg-max and beam decodes'
-                             % (what, self._truncation()))
-        if getattr(self, 'sampling_topp', None) is not None or int(getattr(self, 'sampling_topk', 1)) > 1:
-            raise ValueError('%s and sampling (sampling_topk %r, sampling_topp %r) do not combine: the search options '
-                             'apply to the arg-max and beam decodes' % (what, self.sampling_topk, self.sampling_topp))
-        if attention:
-            raise ValueError('%s and attention=True do not combine: attention maps are exported without search options'
-                             % what)
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
-                             'search options cover the cached DynamicConv generator only' % (what, type(self).__name__))
-        return opts
-
-    def _penalties(self):
-        """-> (theta, alpha, beta) of the model's attributes, checked; None when all three are at their defaults."""
-        pen = check_penalties(getattr(self, 'repetition_penalty', 1.0), getattr(self, 'presence_penalty', 0.0),
-                              getattr(self, 'frequency_penalty', 0.0))
-        return None if pen == (1.0, 0.0, 0.0) else pen
-
-    def _check_penalties(self, attention=False):
-        """What the penalties combine with: the arg-max, beam and top-k sampling decodes of the cached
-        DynamicConv generator - no truncation rule, no ban options, no attention maps, not the LSTM decoders nor the copy
-        models.  -> (theta, alpha, beta) or None."""
-        pen = self._penalties()
-        if pen is None:
-            return None
-        what = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, pen, (1.0, 0.0, 0.0)) if v != d)
-        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
-            if getattr(self, name, None) is not None:
-                raise ValueError('%s and %s=%r do not combine: the penalties cover the arg-max, beam and top-k sampling decodes'
-                                 % (what, name, getattr(self, name)))
-        for name in ('no_repeat_ngram_size', 'min_len'):
-            if getattr(self, name, 0):
-                raise ValueError('%s and %s=%r do not combine: one list per pick launch' % (what, name, getattr(self, name)))
-        if attention:
-            raise ValueError('%s and attention=True do not combine: attention maps are exported without penalties' % what)
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); the '
-                             'penalties cover the cached DynamicConv generator only' % (what, type(self).__name__))
-        return pen
-
-    def _mask_options(self, banned=None, ground=None):
-        """-> the names of the vocabulary-mask options in force ('banned', 'ground', 'suppress_tokens', 'ground_names'), the
-        call's arguments and the model's attributes alike; empty: nothing set."""
-        st, gn = check_mask_keys(getattr(self, 'suppress_tokens', ()), getattr(self, 'ground_names', False))
-        used = []
-        if banned is not None:
-            used.append('banned')
-        if ground is not None and ground is not False:
-            used.append('ground')
-        if st:
-            used.append('suppress_tokens')
-        if gn and 'ground' not in used:
-            used.append('ground_names')
-        return used
-
-    def _check_mask_options(self, banned=None, ground=None, attention=False):
-        """What a vocabulary mask combines with: the arg-max, beam and top-k sampling decodes of the
-        cached DynamicConv generator, with or without the search options, n_samples and a prefix - no truncation rule, no
-        penalties, no attention maps, not the LSTM decoders nor the copy models.  -> the option names in force (may be empty)."""
-        used = self._mask_options(banned, ground)
-        if not used:
-            return used
-        what = ' / '.join(used)
-        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
-            if getattr(self, name, None) is not None:
-                raise ValueError('%s and %s=%r do not combine: a vocabulary mask covers the arg-max, beam and top-k sampling '
-                                 'decodes' % (what, name, getattr(self, name)))
-        if self._penalties() is not None:
-            pen = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, self._penalties(), (1.0, 0.0, 0.0)) if v != d)
-            raise ValueError('%s and %s do not combine: the penalties\' bitmap means "listed", not "banned"' % (what, pen))
-        if attention:
-            raise ValueError('%s and attention=True do not combine: attention maps are exported without a vocabulary mask' % what)
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); vocabulary '
-                             'masks cover the cached DynamicConv generator only' % (what, type(self).__name__))
-        return used
-
-    def _check_guidance(self, guidance=None, guidance_drop=None, attention=False, prefix=None, n_samples=1, banned=None,
-                        ground=None):
-        """Context guidance of one call: the arguments, or where they are None the model's
-        `guidance_scale` / `guidance_drop`, checked (check_guidance; every name a context of this decoder).  -> None for
-        gamma = 1.0 (off: the call of before), else (drop, gamma) after what guidance combines with: the arg-max and beam decodes
-        of the cached DynamicConv generator with beam_len_penalty and n_best - no sampling rule, no no_repeat_ngram_size /
-        min_len, no penalties, no vocabulary mask, no prefix, no n_samples, no attention maps, not the LSTM decoders nor the
-        copy models."""
-        gamma, drop = check_guidance(getattr(self, 'guidance_scale', 1.0) if guidance is None else guidance,
-                                     getattr(self, 'guidance_drop', ('image',)) if guidance_drop is None else guidance_drop)
-        layers = getattr(getattr(self, 'decoder', None), 'layers', None)
-        have = getattr(layers[0], 'context_names', None) if layers is not None and len(layers) else None
-        if have is not None and (gamma != 1.0 or guidance_drop is not None):   # (the default drop of a model that is off: unread)
-            for n in drop:
-                if n not in have:
-                    raise ValueError('guidance_drop: the decoder has no context %r (it has %s)' % (n, ' / '.join(have)))
-        if gamma == 1.0:
-            return None
-        what = 'guidance=%r' % gamma
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('%s: %s has a decode step with its own decision launch (LSTM decoders, copy models); context '
-                             'guidance covers the cached DynamicConv generator only' % (what, type(self).__name__))
-        if int(getattr(self, 'sampling_topk', 1)) > 1:
-            raise ValueError('%s and sampling_topk=%r do not combine: guidance covers the arg-max and beam decodes'
-                             % (what, self.sampling_topk))
-        for name in ('sampling_topp', 'sampling_minp', 'sampling_typical'):
-            if getattr(self, name, None) is not None:
-                raise ValueError('%s and %s=%r do not combine: guidance covers the arg-max and beam decodes'
-                                 % (what, name, getattr(self, name)))
-        for name in ('no_repeat_ngram_size', 'min_len'):
-            if getattr(self, name, 0):
-                raise ValueError('%s and %s=%r do not combine: the guided pick takes no ban list' % (what, name, getattr(self, name)))
-        if self._penalties() is not None:
-            pen = ' / '.join('%s=%r' % (k_, v) for k_, v, d in zip(PENALTY_KEYS, self._penalties(), (1.0, 0.0, 0.0)) if v != d)
-            raise ValueError('%s and %s do not combine: the guided pick takes no penalty list' % (what, pen))
-        used = self._mask_options(banned, ground)
-        if used:
-            raise ValueError('%s and %s do not combine: the guided pick takes no vocabulary mask' % (what, ' / '.join(used)))
-        if prefix is not None:
-            raise ValueError('%s and prefix do not combine: a forced token has no guided log-prob' % what)
-        if isinstance(n_samples, int) and n_samples > 1:
-            raise ValueError('%s and n_samples=%d do not combine: guidance covers the arg-max and beam decodes' % (what, n_samples))
-        if attention:
-            raise ValueError('%s and attention=True do not combine: attention maps are exported without guidance' % what)
-        return drop, gamma
-
     def name_tokens(self):
         """The grounded class of generate(ground=True): data.bpe.capitalised_tokens over the installed roberta-base vocabulary -
         bool [vocab], the BPE pieces that start a capitalised word (per token, not per word: continuation pieces are
@@ -906,71 +167,6 @@ class CaptionModel(Model):
         cls_bits = None if cls is None else ops.pack_mask_bits(cls).to(dev)
         deny8 = None if deny is None else deny.to(device=dev, dtype=torch.uint8).contiguous()
         return ctx_ids, cls_bits, deny8
-
-    def _check_prefix(self, prefix, batch_size, gen_len=DEFAULT_GEN_LEN, eos=2):
-        """generate(prefix=...): check_prefix against this model; the cached DynamicConv generators only - the LSTM decoders
-        and the copy models end their decode step in a decision launch of their own.  -> (prefix, plen) or None."""
-        if prefix is None:
-            return None
-        if not self.SEARCH_OPTIONS or not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('prefix: %s has a decode step with its own decision launch (LSTM decoders, copy models such as '
-                             'transformer_pointer / transformer_pointer_2); a forced prefix is out of scope there: it covers '
-                             'the cached DynamicConv generator only' % type(self).__name__)
-        return check_prefix(prefix, batch_size, self.decoder.adaptive_softmax.vocab_size, gen_len, self.padding_idx, eos)
-
-    CACHED_N_SAMPLES = False       # a model with a decision launch of its own that still decodes n hypotheses per image
-
-    def _check_n_samples(self, n_samples=1, rank_by='score', rank_len_penalty=0.0, beam_size=1, attention=False,
-                         forward=False, cached=False):
-        """generate(n_samples=n): check_n_samples, and for n > 1 what it combines with - a sampling
-        decode of the cached DynamicConv generator, one seed per call; no beam search (n_best is the beam's own form), no
-        attention maps, not forward=True, not the arg-max decode, not the LSTM decoders nor the copy models - except, with
-        cached=True (the call decodes through the cached step), a copy model that samples (CACHED_N_SAMPLES, DESIGN.md
-        section 28).  -> (n, rule, alpha), or None for n = 1."""
-        n, rule, alpha = check_n_samples(n_samples, rank_by, rank_len_penalty)
-        if n == 1:
-            return None
-        if int(beam_size) > 1:
-            raise ValueError('n_samples=%d and beam search (beam_size %d) do not combine: n_best is the beam\'s own form'
-                             % (n, int(beam_size)))
-        if attention:
-            raise ValueError('n_samples=%d and attention=True do not combine: attention maps are exported for one hypothesis '
-                             'per sample' % n)
-        if forward:
-            raise ValueError('n_samples goes with generate, not with forward=True')
-        has_cache = hasattr(getattr(self, 'decoder', None), 'project_contexts')
-        if not has_cache or not (self.SEARCH_OPTIONS or (cached and self.CACHED_N_SAMPLES and self._sampling() is not None)):
-            raise ValueError('n_samples=%d: %s has a decode step with its own decision launch (LSTM decoders, copy models); '
-                             'several samples per image cover the cached DynamicConv generator only' % (n, type(self).__name__))
-        if self._sampling() is None:
-            raise ValueError('n_samples=%d needs a sampling model (sampling_topk > 1, sampling_topp, sampling_minp or '
-                             'sampling_typical): the arg-max decode (sampling_topk 1) would give %d identical captions' % (n, n))
-        return n, rule, alpha
-
-    def _check_token_stats(self, token_stats=0, beam_size=1, n_best=1, guide=None):
-        """generate(token_stats=n): check_token_stats, and for n > 0 what it combines with - the greedy
-        and sampling decodes of the cached DynamicConv generator; no beam search, no guidance, no LSTM decoder.  -> n."""
-        n = check_token_stats(token_stats)
-        if not n:
-            return 0
-        if int(beam_size) > 1 or int(n_best) > 1:
-            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['beam']))
-        if guide is not None:
-            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['guide']))
-        if not hasattr(getattr(self, 'decoder', None), 'project_contexts'):
-            raise ValueError('token_stats=%d: %s' % (n, TOKEN_STATS_REFUSALS['lstm']))
-        return n
-
-    def _check_attention(self, beam_size=1):
-        """generate(attention=True): what the attention-map export covers - the DynamicConv decoders, one hypothesis per
-        sample (greedy, top-k, nucleus)."""
-        if int(beam_size) > 1:
-            raise ValueError('attention=True: attention maps are exported for greedy / top-k / nucleus generation only, not '
-                             'for beam search (beam_size %d): the slots would have to follow the surviving hypotheses'
-                             % int(beam_size))
-        if not hasattr(self.decoder, 'project_contexts'):
-            raise ValueError('attention=True: %s is an LSTM decoder; attention maps are exported for the DynamicConv '
-                             'decoders only (its dot attention is not covered)' % type(self.decoder).__name__)
 
     @staticmethod
     def _attn_output(out, attns):
@@ -1182,12 +378,11 @@ class CaptionModel(Model):
                                                                 caption_weights, per_image)
         if not self.training and self.evaluate_mode:                       # :92-116
             # (eval_attention: commands/evaluate.py's opt-in - the captions come with their attention maps)
-            vm = self._vocab_mask(context, attention=bool(getattr(self, 'eval_attention', False)))
-            guide = self._check_guidance(attention=bool(getattr(self, 'eval_attention', False)))
+            attention = bool(getattr(self, 'eval_attention', False))
+            vm = self._vocab_mask(context, attention=attention)
+            guide = self._check_guidance(attention=attention)
             _, gen_ids, attns = self._generate(caption_ids, contexts, beam_size=getattr(self, 'eval_beam_size', 1),
-                                               **({'attention': True} if getattr(self, 'eval_attention', False) else {}),
-                                               **({'vmask': vm} if vm is not None else {}),
-                                               **({'guide': guide} if guide is not None else {}))
+                                               attention=attention, vmask=vm, guide=guide)
             self._forward_generated(output_dict, gen_ids, attns, metadata)
         self.n_samples += caption_ids.shape[0]
         self.n_batches += 1
@@ -1308,26 +503,17 @@ class CaptionModel(Model):
         </s> in gen_ids; `steps` for a row that never ended): maps[b, :attn_steps[b] - 1] are the steps of the words of an ended
         row, maps[b, attn_steps[b]:] what the static batch computed after it.  The tokens and log-probs are bit for bit those of attention=False.  `caption_attention` turns the maps into the
         reference's per-word view.  Default: 'attns' is [] on the cached generators."""
-        if attention:
-            self._check_attention(beam_size)
-        self._check_options(beam_size, attention, n_best)
-        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention)
         # (prefix=None reads nothing of the batch here: the default path is the path of before)
-        pfx = None if prefix is None else self._check_prefix(prefix, caption[self.index].shape[0])
-        vm = self._vocab_mask(context, banned, ground, attention)
-        guide = self._check_guidance(guidance, guidance_drop, attention, prefix, n_samples, banned, ground)
-        ts = self._check_token_stats(token_stats, beam_size, n_best, guide)
+        plan = self._plan(beam_size, attention, n_best, prefix, n_samples, rank_by, rank_len_penalty, banned, ground, guidance,
+                          guidance_drop, token_stats, context, None if prefix is None else caption[self.index].shape[0])
         caption_ids, _, contexts = self._forward(context, image, caption, face_embeds, obj_embeds, encoded)
-        log_probs, gen_ids, attns = self._generate(caption_ids, contexts, attn_idx, beam_size=beam_size, attention=attention,
-                                                   **({'n_best': n_best} if n_best != 1 else {}),
-                                                   **({'token_stats': ts} if ts else {}),
-                                                   **({'guide': guide} if guide is not None else {}),
-                                                   **({'samples': ns} if ns is not None else {}),
-                                                   **({'vmask': vm} if vm is not None else {}),
-                                                   prefix=pfx)
+        return self._generated(plan, *self._generate(caption_ids, contexts, attn_idx, **plan.keywords()))
+
+    def _generated(self, plan, log_probs, gen_ids, attns):
+        """generate's output dict from a generator's three results."""
         out = self._attn_output({'gen_ids': gen_ids, 'log_probs': log_probs}, attns)
-        if pfx is not None:
-            out['prefix_len'] = pfx[1].to(gen_ids.device, torch.long)
+        if plan.prefix is not None:
+            out['prefix_len'] = plan.prefix[1].to(gen_ids.device, torch.long)
         return out
 
     @torch.no_grad()
@@ -1345,7 +531,7 @@ class CaptionModel(Model):
         f = {k: (dict(v) if isinstance(v, dict) else v) for k, v in batch.items()
              if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds', 'encoded')}
         n_ts = check_token_stats(token_stats)
-        out = self.generate(**f, prefix=prefix, **({'token_stats': n_ts} if n_ts else {}))
+        out = self.generate(**f, prefix=prefix, token_stats=n_ts)
         plen = out['prefix_len']
         lp = out['log_probs']
         T = prefix.shape[1]
@@ -1399,25 +585,21 @@ class CaptionModel(Model):
             raise ValueError('token_stats=%d: %s' % (token_stats, TOKEN_STATS_REFUSALS['lanes']))
         if banned is not None and (not torch.is_tensor(banned) or banned.dim() != 1):
             raise ValueError('generate_lanes takes the shared form of banned: a bool tensor [V]')
-        ns = self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
-        guide = self._check_guidance(guidance, guidance_drop, attention, None, n_samples, banned, ground)
-        if forward and (guidance is not None or guidance_drop is not None):   # (forward=True decodes under the model's keys)
-            raise ValueError('guidance / guidance_drop as arguments go with generate, not with forward=True')
-        gkw = {'guide': guide} if guide is not None else {}
-        if attention:
-            if forward:
+        if forward:                                    # (forward=True decodes under the model's keys and eval_* attributes)
+            self._check_n_samples(n_samples, rank_by, rank_len_penalty, beam_size, attention, forward)
+            if guidance is not None or guidance_drop is not None:
+                raise ValueError('guidance / guidance_drop as arguments go with generate, not with forward=True')
+            if attention:
                 raise ValueError('attention=True goes with generate, not with forward=True')
-            self._check_attention(beam_size)
-        if forward:
             beam_size = getattr(self, 'eval_beam_size', 1)
-            if getattr(self, 'eval_attention', False) and not self.training and self.evaluate_mode:
-                self._check_attention(beam_size)
-                attention = True
+            attention = bool(getattr(self, 'eval_attention', False) and not self.training and self.evaluate_mode)
             if self.training or not self.evaluate_mode or not self.lanes_usable():
                 yield from self.generate_stream(batches, forward=True)  # nothing to decode / no static-batch decode loop
                 return
+        # (the prefix and the article ids a mask is grounded in come with every batch: the plan of a batch adds them)
+        plan = self._plan(beam_size, attention, n_best, None, n_samples, rank_by, rank_len_penalty, banned, ground, guidance,
+                          guidance_drop)
         self._check_beam(beam_size)
-        self._check_options(beam_size, attention, n_best)
         self._check_penalties(attention)
         it = iter(batches)
         main = torch.cuda.current_stream()
@@ -1430,7 +612,7 @@ class CaptionModel(Model):
                     group.append(b)
             if not group:
                 return
-            gens, outs, heads, thirds, plens = [], [None] * len(group), [], [None] * len(group), []
+            gens, outs, heads, thirds, plans = [], [None] * len(group), [], [None] * len(group), []
             for ln, b in enumerate(group):
                 f = {k: v for k, v in b.items() if k in ('context', 'image', 'caption', 'face_embeds', 'obj_embeds')}
                 if forward:
@@ -1443,19 +625,15 @@ class CaptionModel(Model):
                 if b.get('prefix') is not None and forward:
                     raise ValueError('prefix goes with generate, not with forward=True')
                 pfx = self._check_prefix(b.get('prefix'), caption_ids.shape[0])
-                if guide is not None and pfx is not None:
+                if plan.guide is not None and pfx is not None:
                     self._check_guidance(guidance, guidance_drop, prefix=pfx)
-                plens.append(pfx[1] if pfx is not None else None)
-                vm = self._vocab_mask(b['context'], banned, ground, attention)
-                vkw = {'vmask': vm} if vm is not None else {}
+                steps = self._beam_steps if beam_size > 1 else self._greedy_steps
+                plans.append(plan._replace(prefix=pfx, vmask=self._vocab_mask(b['context'], banned, ground, attention)))
                 ev = torch.cuda.Event()
                 ev.record(main)
                 lane_streams[ln].wait_event(ev)
                 with torch.cuda.stream(lane_streams[ln]), ops.hip.bound_stream():
-                    g = (self._beam_steps(caption_ids, contexts, int(beam_size), lane=ln, n_best=n_best, prefix=pfx, **vkw, **gkw)
-                         if beam_size > 1 else
-                         self._greedy_steps(caption_ids, contexts, lane=ln, seed=seed, attention=attention, prefix=pfx,
-                                            **({'n': ns[0], 'rank': ns[1:]} if ns is not None else {}), **vkw, **gkw))
+                    g = steps(caption_ids, contexts, lane=ln, seed=seed, plan=plans[ln])
                 gens.append(g)
             live = list(range(len(group)))
             while live:
@@ -1464,11 +642,7 @@ class CaptionModel(Model):
                         try:
                             next(gens[ln])
                         except StopIteration as done:
-                            lp, ids, attns = done.value
-                            outs[ln] = self._attn_output({'gen_ids': ids, 'log_probs': lp}, attns)
-                            if plens[ln] is not None:
-                                outs[ln]['prefix_len'] = plens[ln].to(ids.device, torch.long)
-                            thirds[ln] = attns
+                            outs[ln], thirds[ln] = self._generated(plans[ln], *done.value), done.value[2]
                             live.remove(ln)
             for ln in range(len(group)):
                 ev = torch.cuda.Event()
@@ -1504,15 +678,10 @@ class CaptionModel(Model):
         token_stats: refused here (0 only); `generate` keeps the per-token statistics."""
         if check_token_stats(token_stats):
             raise ValueError('token_stats=%d: %s' % (token_stats, TOKEN_STATS_REFUSALS['lanes']))
+        if forward and (attention or n_best != 1):
+            raise ValueError('%s goes with generate, not with forward=True' % ('attention=True' if attention else 'n_best'))
         if attention:
-            if forward:
-                raise ValueError('attention=True goes with generate, not with forward=True')
             self._check_attention(beam_size)
-        gen_kw = {'attention': True} if attention else {}
-        if n_best != 1:
-            if forward:
-                raise ValueError('n_best goes with generate, not with forward=True')
-            gen_kw['n_best'] = n_best
         it = iter(batches)
         cur = next(it, None)
         enc = None
@@ -1529,7 +698,7 @@ class CaptionModel(Model):
             extra = {'encoded': enc} if enc is not None else {}
             if forward and cur.get('prefix') is not None:
                 raise ValueError('prefix goes with generate, not with forward=True')
-            out = self(**{k_: v_ for k_, v_ in cur.items() if k_ != 'prefix'}, **extra) if forward else self.generate(**cur, beam_size=beam_size, **extra, **gen_kw)
+            out = self(**{k_: v_ for k_, v_ in cur.items() if k_ != 'prefix'}, **extra) if forward else self.generate(**cur, beam_size=beam_size, attention=attention, n_best=n_best, **extra)
             yield cur, out
             cur, enc = nxt, ahead
 
@@ -1538,34 +707,11 @@ class CaptionModel(Model):
 
     def _generate(self, caption_ids, contexts, attn_idx=None, gen_len=100, eos=2, beam_size=1, attention=False, n_best=1,
                   prefix=None, samples=None, vmask=None, guide=None, token_stats=0):
-        opts = self._check_options(beam_size, attention, n_best, gen_len)
-        # (n, as checked by _check_token_stats: lives in the cached greedy / sampling generator, like `opts`)
-        skw = {'stats': self._check_token_stats(token_stats, beam_size, n_best, guide)} if token_stats else {}
-        if guide is not None:                 # (drop, gamma) of _check_guidance: lives in the cached generators, like `opts`
-            self._check_guidance(guide[1], guide[0], attention, prefix, samples[0] if samples is not None else 1,
-                                 True if vmask is not None else None)
-            self._check_beam(beam_size)
-            if beam_size > 1:
-                return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, guide=guide)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, guide=guide)
-        if self._check_penalties(attention) is not None:      # (the penalties live in the cached generators, like `opts`)
-            opts = opts or (0.0, 0, 0)
-        if prefix is not None:                # (prefix, plen) of _check_prefix: lives in the cached generators, like `opts`
-            self._check_prefix(prefix[0], caption_ids.shape[0], gen_len, eos)
-        if vmask is not None:                 # (ctx_ids, cls_bits, deny8) of _vocab_mask: lives in the cached generators
-            self._check_mask_options(True, None, attention)
-            if not hasattr(self.decoder, 'project_contexts'):
-                raise ValueError('vocabulary masks cover the cached DynamicConv generator only')
-            self._check_beam(beam_size)
-            vkw = {'vmask': vmask}
-            if beam_size > 1:
-                return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix, **vkw)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **vkw, **skw)
-        if attention:
-            # attention maps: always the cached static-batch generator (fast_generation = False is the reference's control
-            # flow with the legacy need_attn export, which stays what it is)
-            self._check_attention(beam_size)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, attention=True, prefix=prefix, **skw)
+        """The generator of one decode call, chosen by its DecodePlan: the LSTM decoder's own loop; beam search; the cached
+        generator - with fast_generation, or whenever an option of the plan or of the model (search options, penalties) is
+        set, all of which live there; else the reference's control flow."""
+        plan = DecodePlan(beam_size, n_best, attention, prefix, samples, vmask, guide, token_stats)
+        _, opts, _, pen = plan.resolve(self, gen_len, eos, rows=None if prefix is None else caption_ids.shape[0])
         if not hasattr(self.decoder, 'project_contexts'):
             # a recurrent decoder behind this model class (expt/*/3_lstm_roberta: `lstm_decoder_flattened`): greedy
             # decode that carries the LSTM state.  (The reference's loop feeds such a decoder only the last token with
@@ -1575,12 +721,12 @@ class CaptionModel(Model):
             lps, ids = BaselineGloveModel._generate(self, caption_ids, contexts, gen_len, eos)
             return lps, ids, []
         self._check_beam(beam_size)
+        options = plan.options()
         if beam_size > 1:
-            return self._generate_beam(caption_ids, contexts, beam_size, gen_len, eos, n_best=n_best, prefix=prefix)
-        if samples is not None:
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, samples=samples, **skw)
-        if self.fast_generation or opts is not None or prefix is not None or skw:  # (the search options live in the cached generator)
-            return self._generate_cached(caption_ids, contexts, gen_len, eos, prefix=prefix, **skw)
+            return self._generate_beam(caption_ids, contexts, options.pop('beam_size'), gen_len, eos, **options)
+        # (attention maps too: fast_generation = False is the reference's control flow with the legacy need_attn export)
+        if self.fast_generation or opts is not None or pen is not None or options:
+            return self._generate_cached(caption_ids, contexts, gen_len, eos, **options)
         return self._generate_reference_flow(caption_ids, contexts, attn_idx, gen_len, eos)
 
     @staticmethod
@@ -1593,20 +739,15 @@ class CaptionModel(Model):
             return done.value
 
     @torch.no_grad()
-    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, attention=False, prefix=None,
-                         samples=None, vmask=None, guide=None, stats=0):
-        # (prefix only when given: a stand-in for _greedy_steps without that parameter keeps working - tests/test_attn_maps_host.py)
-        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, attention=attention,
-                                              **({'prefix': prefix} if prefix is not None else {}),
-                                              **({'n': samples[0], 'rank': samples[1:]} if samples is not None else {}),
-                                              **({'vmask': vmask} if vmask is not None else {}),
-                                              **({'guide': guide} if guide is not None else {}),
-                                              **({'stats': stats} if stats else {})))
+    def _generate_cached(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, **options):
+        """options: the fields of a DecodePlan (attention=, prefix=, samples=, vmask=, guide=, stats=)."""
+        return self._drive(self._greedy_steps(caption_ids, contexts, gen_len, eos, check_every, lane, plan=DecodePlan(**options)))
 
-    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, attention=False,
-                      prefix=None, n=1, rank=('score', 0.0), vmask=None, guide=None, stats=0):
+    def _greedy_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, plan=DecodePlan()):
         """A generator: yields after every issued decode step (generate_lanes interleaves two of these on two streams), returns
-        (log_probs, ids, []).  Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
+        (log_probs, ids, []).  plan: the DecodePlan of the call, resolved here once (its checks, the model's sampling rule, ban
+        list and penalties); attention, prefix, samples = (n,) + rank, vmask, guide and stats below are its fields.
+        Same greedy decode, restructured for the GPU: (1) context K/V projected once per caption,
         (2) the batch keeps its shape - finished rows are masked instead of compacted, so there is no
         per-step gather of the contexts and no per-step host synchronisation (the all-finished test
         runs every `check_every` steps), (3) fused arg-max over the adaptive softmax.  Rows are
@@ -1636,27 +777,20 @@ class CaptionModel(Model):
         the stepper's sink; behind the loop the slots become the five [rows, steps(, n_alt)] arrays, carried as .token_stats of
         the third result (a DecodeInfo, or an AttnMapsStats with attention=True)."""
         dec = self.decoder
-        n = int(n)
-        stats = int(stats)
-        if stats and guide is not None:
-            raise ValueError('token_stats=%d: %s' % (stats, TOKEN_STATS_REFUSALS['guide']))
+        # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
+        sampling, _, ban, pen = plan.resolve(self, gen_len, eos)
+        _, _, attention, prefix, samples, vmask, guide, stats = plan
+        n, rank = (int(samples[0]), samples[1:]) if samples is not None else (1, None)
         if guide is not None:
-            self._check_guidance(guide[1], guide[0], attention, prefix, n, True if vmask is not None else None)
             cond = caption_ids.shape[0]
             caption_ids, contexts = guided_batch(caption_ids, contexts, guide[0])
         images = caption_ids.shape[0]
         B = images * n                                           # decode rows
         dev = caption_ids.device
         kv = dec.project_contexts(contexts)
-        sampling = self._sampling()
-        opts = self._check_options(1, attention, 1, gen_len)
-        # greedy: the bans apply (no_repeat_ngram_size, min_len); the length penalty ranks hypotheses and there is one
-        ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
-        pen = self._check_penalties(attention)
         step = self._decode_stepper(B, kv, contexts, gen_len, lane=lane, sample=sampling, attention=attention, ban=ban,
-                                    prefix=prefix is not None, **({'pen': pen} if pen is not None else {}),
-                                    **({'hyp': n} if n > 1 else {}), **({'mask': True} if vmask is not None else {}),
-                                    **({'guide': guide[0]} if guide is not None else {}), **({'stats': stats} if stats else {}))
+                                    prefix=prefix is not None, pen=pen, hyp=n, mask=vmask is not None,
+                                    guide=None if guide is None else guide[0], stats=stats)
         if guide is not None:
             step.set_guidance(guide[1])
         if prefix is not None:
@@ -1726,8 +860,7 @@ class CaptionModel(Model):
         steps = max(steps, 1)
         ts = self._token_stats_arrays(step.stats, steps) if stats else None
         if n > 1:
-            return self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank,
-                                      **({'stats': ts} if ts is not None else {}))
+            return self._rank_samples(ids, lps, done_step, images, n, steps, gen_len, eos, rank, stats=ts)
         attns = []
         if ts is not None:
             attns = DecodeInfo()
@@ -1785,25 +918,20 @@ class CaptionModel(Model):
             info.token_stats = {k_: info.samples[k_ + '_samples'][:, 0].contiguous() for k_ in stats}
         return (info.samples['log_probs_samples'][:, 0].contiguous(), info.samples['gen_ids_samples'][:, 0].contiguous(), info)
 
-    def _decode_stepper(self, B, kv, contexts, gen_len, topk=0, lane=0, sample=None, attention=False, ban=None, opts=None,
-                        prefix=False, pen=None, hyp=1, mask=False, guide=None, hidden=False, stats=0):
+    def _decode_stepper(self, B, kv, contexts, gen_len, **kw):
         """-> the DecodeStepper (models/stepper.py) of the cached greedy / beam generators for this caption batch: a view over
         the cache entry of its signature in `_decode_graphs` (static buffers, captured graphs), or the eager step."""
-        return DecodeStepper(self, B, kv, contexts, gen_len, topk=topk, lane=lane, sample=sample, attention=attention, ban=ban,
-                             opts=opts, prefix=prefix, pen=pen, **({'hyp': hyp} if hyp != 1 else {}),
-                             **({'mask': True} if mask else {}), **({'guide': guide} if guide is not None else {}),
-                             **({'hidden': True} if hidden else {}), **({'stats': stats} if stats else {}))
+        return DecodeStepper(self, B, kv, contexts, gen_len, **kw)
 
     @torch.no_grad()
-    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
-                       vmask=None, guide=None):
-        return self._drive(self._beam_steps(caption_ids, contexts, beam_size, gen_len, eos, check_every, lane, n_best, prefix=prefix,
-                                            **({'vmask': vmask} if vmask is not None else {}),
-                                            **({'guide': guide} if guide is not None else {})))
+    def _generate_beam(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, **options):
+        """options: the fields of a DecodePlan (n_best=, prefix=, vmask=, guide=)."""
+        return self._drive(self._beam_steps(caption_ids, contexts, gen_len, eos, check_every, lane,
+                                            plan=DecodePlan(beam_size, **options)))
 
-    def _beam_steps(self, caption_ids, contexts, beam_size, gen_len=100, eos=2, check_every=8, lane=0, n_best=1, prefix=None,
-                    vmask=None, guide=None):
-        """A generator like _greedy_steps.  Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
+    def _beam_steps(self, caption_ids, contexts, gen_len=100, eos=2, check_every=8, lane=0, seed=None, plan=DecodePlan()):
+        """A generator like _greedy_steps; plan.beam_size = K, and n_best, prefix, vmask and guide below are the plan's fields.
+        Beam search on the cached static-shape generator (SURVEY 8-f1 / BASELINE config 5; the reference itself
         only samples top-1, transformer_faces_objects.py:443-464).  B*K rows (row = b*K + j) stay resident; the
         projected K/V of the static contexts are computed once per caption and replicated per beam; the DynamicConv
         input buffers are reordered by parent with the reference's `reorder_incremental_state` contract
@@ -1824,26 +952,23 @@ class CaptionModel(Model):
         (guided_batch), hypothesis row r's partner is row r + B * K; every pair's K candidates come from the guided pick and are
         the same for both rows, so tell_beam_update takes the same decisions in both halves; the results are the first half."""
         dec = self.decoder
+        _, opts, ban, pen = plan.resolve(self, gen_len, eos)
+        K, n_best, _, prefix, _, vmask, guide, _ = plan
         if guide is not None:
-            self._check_guidance(guide[1], guide[0], False, prefix, 1, True if vmask is not None else None)
             cond = caption_ids.shape[0]
             caption_ids, contexts = guided_batch(caption_ids, contexts, guide[0])
-        B, K = caption_ids.shape[0], int(beam_size)
+        B = caption_ids.shape[0]
         dev = caption_ids.device
         pad = self.padding_idx
-        opts = self._check_options(K, False, n_best, gen_len)
         alpha = opts[0] if opts is not None else 0.0
-        ban = (opts[1], opts[2], int(eos)) if opts is not None and (opts[1] or opts[2]) else None
         rep = lambda t, dim: t.repeat_interleave(K, dim=dim).contiguous()           # noqa: E731
         # contexts, masks and projected K/V stay at batch B: the attention modules present the K hypotheses of a
         # sample as K query positions of that sample (modules/attention.py), nothing is replicated per beam
         ctx = {k_: v_ for k_, v_ in contexts.items() if torch.is_tensor(v_)}
         kv = dec.project_contexts(contexts)
-        pen = self._check_penalties()
         step = self._decode_stepper(B * K, kv, ctx, gen_len, topk=K, lane=lane, ban=ban,
                                     opts=(opts + (int(eos),)) if opts is not None else None, prefix=prefix is not None,
-                                    **({'pen': pen} if pen is not None else {}), **({'mask': True} if vmask is not None else {}),
-                                    **({'guide': guide[0]} if guide is not None else {}))
+                                    pen=pen, mask=vmask is not None, guide=None if guide is None else guide[0])
         if guide is not None:
             step.set_guidance(guide[1])
         if prefix is not None:
@@ -2002,8 +1127,8 @@ class CaptionModel(Model):
             else:                                                                   # :443-470, topk + multinomial
                 rows = alive.nonzero().squeeze(1).to(torch.int32)
                 tok, lp = self.decoder.adaptive_softmax.sample(dec_out[0][:, -1:], sampling[0], sampling[1], seed_word, i,
-                                                               row_ids=rows, **({'topp': sampling[2]} if len(sampling) > 2 else {}),
-                                                               **({'rule': sampling[3]} if len(sampling) > 3 else {}))
+                                                               row_ids=rows, topp=sampling[2] if len(sampling) > 2 else None,
+                                                               rule=sampling[3] if len(sampling) > 3 else None)
             sel_ix = tok.long()
             sel_lp = lp / self.sampling_temp
             full_lp = sel_lp.new_zeros(B, 1)
